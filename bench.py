@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the NeRFMatch hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -22,7 +22,12 @@ each (SURVEY.md section 8d defines two metrics):
 Queries shard over ranks with no data-path collective; the per-query pose-candidate records are all-gathered once at
 the end of each region (RCCL over xGMI), inside the timed region.
 
-Extra legs, each an object of its own in the line (never `value`):
+A plain run (no --full) measures region A alone -- set-up, W warm-up steps, the K timed steps, the line -- with `roofline` taken from the
+launches of those K steps.  --full adds region B, the legs below, `roofline.peak_sustained` and `cpu_baseline`.
+--dump-outputs DIR writes what region A's LAST timed step returned (.npy: float32, a seeded sample of the pt_feat rows; see dump_outputs);
+the random draws of the render come from a seeded generator, so the same arguments give the same inputs in every run.
+
+Extra legs (--full), each an object of its own in the line (never `value`):
   variants.zero_tail_skip  region A with the fine pass skipping the zero-width intervals the reference's resampler leaves
                       (identical outputs, SURVEY 8a quirk 2) -- round 1/2's headline definition;
   variants.coarse_fp16x1   region B with the coarse pass of the lean render on ONE fp16 product (opt-in, narrower arithmetic);
@@ -42,7 +47,7 @@ Extra legs, each an object of its own in the line (never `value`):
 Prints ONE JSON line on rank 0 (see the task contract): metric rays*samples/sec (whole job), plus
   roofline     : dominant kernel, FLOP/launch / mean launch duration measured with HIP events on the launch stream
                  around the launches of the K TIMED steps (warm-up launches excluded), against the MFMA peak;
-  cpu_baseline : the oracle (CPU restatement of the reference, torch-CPU fp32) timed on the host, one full 4800-ray query
+  cpu_baseline : (--full) the oracle (CPU restatement of the reference, torch-CPU fp32) timed on the host, one full 4800-ray query
                  (rank 0, N=1 only).
 """
 import argparse
@@ -83,9 +88,13 @@ def parse():
                          "fp32 = v_mfma_f32_32x32x2_f32; the matcher's contractions run on bf16x3 unless fp32 is chosen")
     ap.add_argument("--variant", choices=["7scenes", "cambridge"], default="7scenes",
                     help="NeRF of regions A/B: 7scenes (BASELINE config 3, the headline) or cambridge (appearance embedding, white bg)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the other-precision / full-evaluation / cambridge / mini legs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-match", action="store_true", help="render only")
+    ap.add_argument("--full", action="store_true",
+                    help="besides region A (the headline), run region B, every extra leg, the MFMA probe and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what region A's last timed step returned as DIR/<name>.npy (float32; pt_feat as a seeded sample of its rows)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the other-precision / full-evaluation / cambridge / mini legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-match", action="store_true", help="with --full: render only")
     return ap.parse_args()
 
 
@@ -232,6 +241,30 @@ def pmc_traffic(names, applicable=True):
     return tot
 
 
+DUMP_ROWS = 32768  # rows of pt_feat (256 floats each) in a dump: 32 MB
+
+
+def dump_outputs(out, outdir):
+    """Writes what one render_novel_views call returned as <outdir>/<name>.npy, float32, under 64 MB: pt_feat as a sample of
+    DUMP_ROWS of its Q*R rows (numpy seed 0; the row numbers in pt_feat_rows), pt3d and im_pred whole -- or the same sample of rows
+    when whole they would take more than 16 MB."""
+    import numpy as np
+
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    pf = out["pt_feat"].reshape(-1, out["pt_feat"].shape[-1])
+    n = pf.shape[0]
+    rows = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_ROWS), replace=False))
+    sel = torch.from_numpy(rows).to(pf.device)
+    arrays = {"pt_feat": pf[sel], "pt_feat_rows": torch.from_numpy(rows.astype(np.float64))}
+    rest = {k: out[k] for k in ("pt3d", "im_pred") if out.get(k) is not None}
+    whole = sum(v.numel() for v in rest.values()) * 4 <= 16 << 20
+    for k, v in rest.items():
+        arrays[k] = v if whole else v.reshape(n, -1)[sel]
+    for k, v in arrays.items():
+        np.save(outdir / f"{k}.npy", v.detach().cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or os.environ.get("NM_FORCE_DIST") == "1"):
@@ -270,6 +303,7 @@ def main():
 
     S, Q, Ksteps, Wsteps = args.samples, args.queries, args.steps, args.warmup
     R = (H // DS) * (W // DS)
+    torch.manual_seed(0)  # the render's random draws (stratified and resampling jitter): the same inputs in every run
     unnorm = synth.unnorm_scene()
     poses = [unnorm @ synth.camera_pose(seed=s_) for s_ in range(64)]
 
@@ -325,8 +359,8 @@ def main():
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         return float(el.item())
 
-    def region_a(renderer, Ksteps=Ksteps, Wsteps=Wsteps, lean=False, hw=None):
-        """Render-only region.  Returns (elapsed, kernel events of the timed steps)."""
+    def region_a(renderer, Ksteps=Ksteps, Wsteps=Wsteps, lean=False, hw=None, last=None):
+        """Render-only region.  Returns (elapsed, kernel events of the timed steps); `last` (a dict) receives what the last step returned."""
         h_, w_ = hw or (H, W)
         kmat = synth.intrinsics(h_, w_)
         n_rec = (Ksteps + Wsteps) * Q
@@ -336,6 +370,8 @@ def main():
             q0 = (i * world + rank) * Q  # batches of Q consecutive queries, dealt round-robin over ranks
             c2ws = torch.stack([poses[(q0 + j) % 64] for j in range(Q)])
             out = renderer.render_novel_views((h_, w_), kmat, c2ws, unnorm, dev, lean=lean, want_im_pred=True)
+            if last is not None and i == Wsteps + Ksteps - 1:
+                last.update(out)
             r_ = records[i * Q:(i + 1) * Q]
             r_[:, 0] = torch.arange(q0, q0 + Q, device=dev)
             r_[:, 1:17] = c2ws.reshape(Q, 16).to(dev, non_blocking=True)
@@ -378,13 +414,17 @@ def main():
 
     ops.nerf_fwd = timed_fwd
     rmod.ops.nerf_fwd = timed_fwd
-    extra = not args.no_extra_legs
+    extra = args.full and not args.no_extra_legs
     bf = args.precision in ("bf16x3", "fp16x3")  # the split kernels (three 16-bit MFMAs per product)
     mprec = "fp32" if args.precision == "fp32" else "bf16x3"  # arithmetic of the matcher's contractions (nerfmatch_amd.set_precision)
 
     # ---- region A (metric i, `value`): EVERY sample of both passes goes through the MLP, like the reference
     ren.skip_zero_tail = False
-    elapsed, main_events = region_a(ren)
+    last_out = {}
+    elapsed, main_events = region_a(ren, last=last_out)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out, args.dump_outputs)
+    del last_out
     # the other arithmetic path, same region definition (extra fields, never `value`)
     other = "fp32" if bf else "fp16x3"
     elapsed_other = other_events = None
@@ -467,7 +507,7 @@ def main():
 
     # ---- region B (metric ii): the evaluator's localisation loop, both passes of its lean render on `--precision`
     elapsed_loc = elapsed_loc_fp16 = attn_stats = None
-    if not args.no_match:
+    if args.full and not args.no_match:
         nerfmatch_amd.set_precision(mprec)  # the matcher's contractions follow the same arithmetic choice
         assert ren.coarse_precision == "same"
         kprobe.events.clear()
@@ -836,7 +876,7 @@ def main():
                             f"batches pipelined across the matcher's one synchronisation point",
                 "rays": R, "samples_coarse": S, "samples_fine": S, "queries_per_step_per_gpu": Q, "variant": args.variant, "image_hw": [H, W],
                 "sharding": "query batches round-robin over ranks; one all_gather of pose-candidate records at shard end",
-                "world_size": world, "collectives": ("gloo, all ranks on ONE GPU (NM_BENCH_SHARE_GPU dry run: not a measurement)" if share else "RCCL (torch.distributed nccl)") if use_dist else "none (single process)",
+                "full": args.full, "world_size": world, "collectives": ("gloo, all ranks on ONE GPU (NM_BENCH_SHARE_GPU dry run: not a measurement)" if share else "RCCL (torch.distributed nccl)") if use_dist else "none (single process)",
             },
             "query_images_per_sec": (world * Ksteps * Q / elapsed_loc) if elapsed_loc else None,
             "localize_ms_per_query": (elapsed_loc / (Ksteps * Q) * 1e3) if elapsed_loc else None,
@@ -857,7 +897,7 @@ def main():
             ex = evald * BF16X3_EXEC_FLOP_PER_SAMPLE_PASS / avg_s / 1e12
             line["roofline"].update(executed_mfma_tflops=ex, frac_executed=ex / peak,
                                     executed_note="16-bit MFMA FLOP actually issued: 3 per fp32 product (w_hi*x_hi + w_hi*x_lo + w_lo*x_hi), padded K")
-            sustained = mfma_probe(dev)
+            sustained = mfma_probe(dev) if args.full else None
             if sustained:
                 line["roofline"].update(peak_sustained=sustained, frac_executed_of_sustained=ex / sustained,
                                         peak_sustained_note="measured on THIS box after the timed regions: a bare v_mfma_f32_32x32x16_f16 stream on every SIMD "
@@ -1003,7 +1043,7 @@ def main():
             line["variants"] = variants
         if mini is not None:
             line["mini"] = mini
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(S, sd if args.variant == "7scenes" else synth.nerf_state_dict(seed=0, density_bias=3.0))
     else:
         line = None

@@ -3,7 +3,7 @@
 # aggregated per kernel name -> gpurun_out/r6_traffic_by_kernel.txt.  A screen for kernels that move bytes their arithmetic does not explain (scratch, re-fetches).
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; R=$PWD; O=gpurun_out/pmc_all; rm -rf $O; mkdir -p $O
 for c in FETCH_SIZE WRITE_SIZE; do
-  ( cd /tmp && timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$O/$c -o all -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $R/$O/$c.log 2>&1 )
+  ( cd "$TMPDIR" && timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$O/$c -o all -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $R/$O/$c.log 2>&1 )
 done
 python3 - <<PY
 import csv, glob, collections

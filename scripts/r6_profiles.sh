@@ -24,7 +24,7 @@ for mode in 0 1; do
   python3 scripts/loop_trace_summarize.py $f $O/r6_loop_q1_$tag.json > $O/loop_q1_${tag}_trace.txt 2>&1
   rm -rf $O/trace_$tag
 done
-( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/bench -o bench -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $R/$O/bench.log 2>&1 )
+( cd "$TMPDIR" && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/bench -o bench -- python3 $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline > $R/$O/bench.log 2>&1 )
 cp $(find $O/bench -name "*kernel_stats.csv" | head -1) $O/r6_bench_kernel_stats.csv
 cat $O/loop_q1_*.log $O/loop_q1_*_trace.txt
 python -c "import json; print(json.load(open('$O/r6_pmc_nerf_fwd_fp16x3_q16.json'))['derived'])"

@@ -33,7 +33,7 @@ REPO = Path(__file__).resolve().parents[2]
 REF = Path("/root/reference")
 import os  # noqa: E402
 
-OUT = Path(os.environ.get("NM_GOLDEN_OUT", Path(__file__).resolve().parent))  # (tests/test_golden_regen_cpu.py regenerates into a temp dir)
+OUT = Path(os.environ.get("NM_GOLDEN_OUT", Path(__file__).resolve().parent))  # (NM_GOLDEN_OUT=<dir>: regenerate elsewhere, to compare with the committed files)
 sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REF))
 
@@ -899,7 +899,7 @@ if __name__ == "__main__":
     assert REF.exists(), "the reference is only present in the build container"
     install_stubs()
     torch.set_num_threads(8)
-    if sys.argv[1:] == ["check"]:  # round 6: the three fixtures tests/test_golden_regen_cpu.py regenerates and compares bit for bit
+    if sys.argv[1:] == ["check"]:  # round 6: the three fixtures regenerated (into NM_GOLDEN_OUT) for a bit-for-bit comparison
         nerf_fixture("r32_s32", "7scenes", H=32, W=64, S=32, stop_layer=3, seed=0)
         matcher_fixtures(seed=0)
         postnorm_fixture()

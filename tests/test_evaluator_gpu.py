@@ -363,7 +363,7 @@ def test_bench_with_rccl_on_one_gpu(gpu, built_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NM_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--queries", "2",
-                          "--no-cpu-baseline", "--no-extra-legs"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-extra-legs"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     last = out.stdout.strip().splitlines()[-1]
     assert last.startswith('{"metric"'), last[:200]  # the JSON line is the LAST line of stdout
@@ -394,7 +394,7 @@ def test_bench_two_ranks_sharing_the_gpu(gpu, built_lib):
     env.update(NM_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--queries", "2",
-                          "--no-cpu-baseline", "--no-extra-legs"], env=env, capture_output=True, text=True, timeout=1200)
+                          "--full", "--no-cpu-baseline", "--no-extra-legs"], env=env, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, out.stdout[-2000:]  # rank 0 alone prints
@@ -405,6 +405,39 @@ def test_bench_two_ranks_sharing_the_gpu(gpu, built_lib):
     units = 2 * 2 * 2 * 4800 * 128
     assert abs(line["value"] * line["ms_per_step"] * 1e-3 * 2 - units) < 1e-6 * units, (line["value"], line["ms_per_step"])
     assert line["query_images_per_sec"] > 0 and "cpu_baseline" not in line  # the CPU leg is rank 0 at N = 1 only
+
+
+def test_bench_plain_run_and_dumped_outputs(gpu, built_lib, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: region A alone (K timed steps, `ms_per_step` of one of them, no region B,
+    no CPU baseline); --dump-outputs writes what the last timed step returned, and two runs with the same arguments write the same arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    import numpy as np
+
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NM_FORCE_DIST")}
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--queries", "1",
+                              "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"]
+        assert line["query_images_per_sec"] is None and "cpu_baseline" not in line and "variants" not in line and not line["config"]["full"]
+        assert line["roofline"]["launches_timed"] == 6  # 3 timed steps x (coarse + fine)
+        units = 3 * 1 * 4800 * (64 + 64)  # steps x queries x rays x samples
+        assert abs(line["value"] * line["ms_per_step"] * 1e-3 * 3 - units) < 1e-6 * units
+        dumps.append({p.stem: np.load(p) for p in (tmp_path / run).glob("*.npy")})
+    a, b = dumps
+    assert set(a) == {"im_pred", "pt3d", "pt_feat", "pt_feat_rows"} and a["pt_feat"].shape == (4800, 256) and a["pt3d"].shape == (1, 4800, 3)
+    assert a["im_pred"].shape == (1, 60, 80, 3) and all(v.dtype == np.float32 for k, v in a.items() if k != "pt_feat_rows")
+    for k in a:
+        assert np.isfinite(a[k]).all(), k
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-6, atol=1e-6, err_msg=k)
 
 
 def test_benchmark_cli_synthetic_run(gpu, built_lib, tmp_path):
