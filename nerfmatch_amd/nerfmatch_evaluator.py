@@ -266,9 +266,17 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
         return c2w_est, R_err, t_err
 
     # -- localisation of one batch ------------------------------------------------------------------------------------------
-    def _render_into(self, batch, renderer, poses, unnorm_scene, side=None):
+    def _render_into(self, batch, renderer, poses, unnorm_scene, side=None, queries=None):
         """Render the points / features seen from `poses` (Q world poses) into the batch (reference :556-574).  Only pt3d and
-        pt_feat are read afterwards, so the render skips the colour heads."""
+        pt_feat are read afterwards, so the render skips the colour heads.  `queries`: the
+        batch rows `poses` belong to, when only some queries of the batch are rendered; the other rows keep their points."""
+        Q = batch["image"].shape[0]
+        if queries is not None and len(queries) < Q:
+            Ks = self._host(batch, "K").reshape(-1, 3, 3)
+            part = dict(image=batch["image"][:len(queries)], _host=dict(K=Ks[[min(q, len(Ks) - 1) for q in queries]]))
+            self._render_into(part, renderer, poses, unnorm_scene)
+            self._replace_rows(batch, queries, part["pt3d"], part["pt_feat"])
+            return
         hw = batch["image"].shape[-2:]
         Ks = self._host(batch, "K").reshape(-1, 3, 3)
         poses = torch.stack([torch.as_tensor(p).detach().float().cpu() for p in poses])
@@ -295,6 +303,25 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
         batch["pt3d"], batch["pt_feat"] = pt3d, pt_feat
         batch["pt_mask"] = self._ones_mask(pt3d)
         batch["_render_tok"] = getattr(renderer, "__dict__", {}).get("_stale_last")  # (ParamGuard's flag copy behind this render, see _localize_finish)
+
+    def _replace_rows(self, batch, queries, pt3d, pt_feat):
+        """batch["pt3d"] / ["pt_feat"] with the rows of `queries` replaced by freshly rendered ones (new tensors: the old ones may be
+        the caller's, e.g. cached points), and those rows marked valid in batch["pt_mask"]."""
+        old3, oldf = batch["pt3d"], batch["pt_feat"]
+        if old3.shape[1:] != pt3d.shape[1:] or oldf.shape[1:] != pt_feat.shape[1:]:
+            raise ValueError(f"cannot re-render some queries of a batch whose points have another shape ({tuple(old3.shape)} / "
+                             f"{tuple(oldf.shape)}) than a render ({tuple(pt3d.shape)} / {tuple(pt_feat.shape)}): use batches of one query")
+        idx = torch.as_tensor(queries, device=old3.device)
+        dt3, dtf = torch.promote_types(old3.dtype, pt3d.dtype), torch.promote_types(oldf.dtype, pt_feat.dtype)  # (widening: exact)
+        batch["pt3d"] = old3.to(dt3).index_copy(0, idx, pt3d.to(dt3))
+        batch["pt_feat"] = oldf.to(dtf).index_copy(0, idx, pt_feat.to(dtf))
+        mask = batch.get("pt_mask")
+        ones = self._ones_mask(batch["pt3d"])
+        if mask is None or mask is ones or mask.shape != ones.shape:
+            batch["pt_mask"] = ones
+        else:
+            batch["pt_mask"] = mask.clone()
+            batch["pt_mask"][idx] = 1
 
     def _render_beside_image_side(self, batch, renderer, poses, unnorm_scene):
         """The render on one compute-unit partition and the matcher's image side on another, side by side; the caller's stream continues
@@ -380,23 +407,27 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
         return st
 
     def _localize_finish(self, st):
-        """Completes iteration 0 (count read-back, fine stage, PnP), then runs the remaining iterations / the refinement."""
+        """Completes iteration 0 (count read-back, fine stage, PnP), then runs the remaining iterations / the refinement.
+
+        Every query of the batch follows the reference's one-query loop (:548-614) on its own: it is re-rendered from the pose its
+        last solve returned, a query without one (a failed solve, cached points never solved) matches its old points again, and the
+        solver is called once per query and iteration.  A batch of Q queries thus gives each query the trace a batch of one gives it
+        (tests/test_localize_loop_cpu.py against oracle/localize_oracle.py)."""
         batch, renderer, o, Q, unnorm_scene, poses = st["batch"], st["renderer"], st["o"], st["Q"], st["unnorm_scene"], st["poses"]
         inf = torch.tensor(float("inf"))
         R_errs, t_errs, nums = [inf] * Q, [inf] * Q, [0] * Q
-        iter_t_errs, iter_R_errs = [], []
-        last_pose = list(poses)
+        trace_t, trace_R = [[] for _ in range(Q)], [[] for _ in range(Q)]  # one `cache_iters` trace per query
         for itr in range(o["iters"]):
             if o["retrieval_only"]:
                 for q in range(Q):
                     R_errs[q], t_errs[q] = pose_err(self._host(batch, "c2w").reshape(-1, 4, 4)[q], poses[q].cpu())
             else:
                 if itr > 0:
-                    # Q == 1 is the reference's loop: no pose -> no re-render, the old points are matched again (:556).  In a
-                    # batch, a query whose PnP failed is re-rendered from its last valid pose so that the others can proceed.
-                    have = poses if Q == 1 else [p if p is not None else lp for p, lp in zip(poses, last_pose)]
-                    if all(p is not None for p in have):
-                        self._render_into(batch, renderer, have, unnorm_scene)
+                    # reference :555-573: no pose -> no re-render, the old points are matched again.  In a batch, the queries that have a
+                    # pose are rendered as a batch of their own and the others keep their rows.
+                    qs = [q for q in range(Q) if poses[q] is not None]
+                    if qs:
+                        self._render_into(batch, renderer, [poses[q] for q in qs], unnorm_scene, queries=qs)
                     if not o["match_oracle"]:
                         st["ms"] = self._match_begin(batch, o["mutual"], o["match_thres"])
                 if not o["match_oracle"]:
@@ -413,36 +444,35 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
                     R_errs[q], t_errs[q], nums[q] = R_err, t_err, n
                     if pose is not None or o["solver"] not in (None, "none"):
                         poses[q] = pose  # solver "none": keep the pose the points were rendered from
-                    if pose is not None:
-                        last_pose[q] = pose
-                if o["inerf_conf"] and o["cache_iters"]:
-                    iter_t_errs.append(t_errs[0])
-                    iter_R_errs.append(R_errs[0])
+                    if o["inerf_conf"] and o["cache_iters"]:
+                        trace_t[q].append(t_errs[q])
+                        trace_R[q].append(R_errs[q])
             if o["inerf_conf"]:
                 # The reference refines batch element 0 only (its loop is batch 1: `batch["image"].clone()[0]`, :323); a batch of Q queries
-                # is refined query by query, each on its own one-query view of the batch.
+                # is refined query by query, each on its own one-query view of the batch (and with its own trace).
                 for q in range(Q):
                     if poses[q] is None:
                         continue
                     sub = batch if Q == 1 else self._query_view(batch, q, Q)
                     res = self.inerf_refinement(sub, renderer, unnorm_scene, poses[q], o["inerf_conf"], mutual=o["mutual"],
                                                 match_thres=o["match_thres"], solver=o["solver"], rthres=o["rthres"],
-                                                center_subpixel=o["center_subpixel"], cache_iters=o["cache_iters"] and q == 0,
-                                                iter_t_errs=iter_t_errs, iter_R_errs=iter_R_errs, debug=o["debug"])
+                                                center_subpixel=o["center_subpixel"], cache_iters=o["cache_iters"],
+                                                iter_t_errs=trace_t[q], iter_R_errs=trace_R[q], debug=o["debug"])
                     if res[1] != float("inf"):  # take the refined pose only if it could be evaluated (reference :608-610)
                         poses[q], R_errs[q], t_errs[q] = res
             if o["cache_iters"]:
-                iter_t_errs.append(t_errs[0] if Q == 1 else list(t_errs))
-                iter_R_errs.append(R_errs[0] if Q == 1 else list(R_errs))
+                for q in range(Q):
+                    trace_t[q].append(t_errs[q])
+                    trace_R[q].append(R_errs[q])
             if o["debug"]:
                 print(f">> iter={itr} matches={nums} t={[float(t) * 100 for t in t_errs]}cm R={[float(r) for r in R_errs]}")
-            if all(p is None for p in poses) and all(p is None for p in last_pose):
-                break  # nothing to render from: further iterations would repeat this one
         # per-query wall time of the step; in the pipelined loop it starts when the previous batch finished (st["ts"] is
         # moved there by eval_data_loader), i.e. it is the steady-state time per query, not begin-to-finish across the overlap
         self.timer["localize_time"].append((time.time() - st["ts"]) / Q)
-        return dict(R_err=list(R_errs), t_err=list(t_errs), iter_t_errs=iter_t_errs, iter_R_errs=iter_R_errs, num_matches=list(nums),
-                    c2w_est=poses[0] if Q == 1 else list(poses), c2w_ests=list(poses))
+        # traces: the reference's flat list for one query, one such list per query (Q rows) for a batch
+        return dict(R_err=list(R_errs), t_err=list(t_errs), iter_t_errs=trace_t[0] if Q == 1 else trace_t,
+                    iter_R_errs=trace_R[0] if Q == 1 else trace_R, num_matches=list(nums), c2w_est=poses[0] if Q == 1 else list(poses),
+                    c2w_ests=list(poses))
 
     _PER_QUERY = ("image", "im_mask", "K", "c2w", "rc2w", "pt2d", "pt3d", "pt_feat", "pt_mask", "unnorm_scene", "pt2d_proj", "conf_gt", "idx")
 
@@ -545,7 +575,7 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
                    solver="colmap", rthres=1, center_subpixel=False, visualize=False, overlay_ims=None, query2query=False,
                    retrieval_only=False, cached_pt=True, cache_iters=False, debug=False):
         """reference :502-629.  The batch may hold Q >= 1 queries; per-query lists come back (`R_err`, `t_err`, `num_matches`,
-        `c2w_ests`; `c2w_est` is the pose itself when Q == 1)."""
+        `c2w_ests`, and `iter_t_errs` / `iter_R_errs` as one trace per query; `c2w_est` and the traces are the query's own when Q == 1)."""
         if visualize:
             raise NotImplementedError("overlay visualisation is out of scope (SURVEY.md section 2)")
         o = self._opts(inerf_conf=inerf_conf, iters=iters, mutual=mutual, match_thres=match_thres, solver=solver, rthres=rthres,
@@ -612,9 +642,9 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
                 if idx is not None:
                     q0 = int(idx[q]) - q
                 recs.append(nmdist.make_record(q0 + q, m["c2w_ests"][q], float(m["R_err"][q]), float(m["t_err"][q]), m["num_matches"][q]))
-            if cache_iters:
-                iter_t.append(m["iter_t_errs"])
-                iter_R.append(m["iter_R_errs"])
+                if cache_iters:  # one row per query, as the reference's batches of one give them
+                    iter_t.append((q0 + q, [float(v) for v in (m["iter_t_errs"] if Q == 1 else m["iter_t_errs"][q])]))
+                    iter_R.append((q0 + q, [float(v) for v in (m["iter_R_errs"] if Q == 1 else m["iter_R_errs"][q])]))
 
         pending = None
         done = 0
@@ -674,7 +704,11 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
         out = dict(R_err=allrec[:, 17].numpy(), t_err=allrec[:, 18].numpy(), num_matches=allrec[:, 19].numpy(),
                    query_idx=allrec[:, 0].long().numpy(), c2w_est=allrec[:, 1:17].reshape(-1, 4, 4).numpy())
         if cache_iters:  # rank-local (like the timers): the iteration traces are diagnostics, not part of the gathered record
-            out.update(iter_t_errs=iter_t, iter_R_errs=iter_R)
+            # (n_queries, L) in query order, np.stack-ed like the reference's (:716-721); rows of different lengths (a refinement that ran
+            # in some iterations only) stay a list of rows, as the reference then returns them unstacked
+            for k, rows in (("iter_t_errs", iter_t), ("iter_R_errs", iter_R)):
+                rows = [r for _, r in sorted(rows, key=lambda e: e[0])]
+                out[k] = np.array(rows, dtype=np.float64) if len({len(r) for r in rows}) <= 1 else rows
         return out
 
     # -- all scenes of a benchmark -----------------------------------------------------------------------------------------
