@@ -9,6 +9,7 @@ kernels of csrc/ (LayerNorm, fp32-MFMA linear layers, flash attention, dual-soft
 fine expectation); torch is used for allocation and index plumbing only.
 """
 import math
+import weakref
 
 import torch
 import torch.nn as nn
@@ -396,6 +397,13 @@ class NeRFMatcherMS(_MatcherBase):
         self.coarse_dthres = getattr(config, "coarse_dthres", 20)
         self.fine_loss = getattr(config, "fine_loss", "match")
         self.win_sz = int(getattr(config, "win_sz", 5))
+        # (the reference accepts any window and width; the kernels do not -- refuse here, not at the first launch)
+        if not 2 <= self.win_sz <= 8:
+            raise ValueError(f"win_sz {self.win_sz}: the fine stage supports 2..8 (win_sz**2 window positions: at most 64, one wavefront "
+                             "lane each in the expectation kernels and one query each in the small-window attention kernels)")
+        if config.fine_sa > 0 and self.ffeat_dim not in (128, 256):
+            raise ValueError(f"ffeat_dim {self.ffeat_dim}: with fine_sa > 0 the fine stage supports 128 and 256 (8 heads of dim "
+                             "ffeat_dim // 8: the small-window attention kernels take head dims 16 and 32; LayerNorm widths 64-512)")
         self.cat_c_feat = getattr(config, "cat_c_feat", True)
         self.fine_preprocess = FinePreprocess(win_sz=self.win_sz, stride=4, d_model_f=self.ffeat_dim, d_model_c=self.cfeat_dim,
                                               cat_c_feat=self.cat_c_feat)
@@ -624,12 +632,13 @@ class NeRFMatcherMS(_MatcherBase):
 
     def _gt_ids(self, conf_gt):
         """torch.where(conf_gt) of the step's ground-truth mask -- a scan of B*M*N bytes plus a count read-back --, made once per tensor
-        state and kept for the second caller of the same step."""
-        key = (conf_gt.data_ptr(), conf_gt._version, tuple(conf_gt.shape))
+        state and kept for the second caller of the same step.  The cache is tied to the tensor OBJECT (a weak reference): a key of
+        address and version alone matched the next step's mask when it was allocated where the freed one had been."""
         hit = self.__dict__.get("_gt_ids_cache")
-        if hit is None or hit[0] != key:
-            hit = self.__dict__["_gt_ids_cache"] = (key, torch.where(conf_gt))
-        return hit[1]
+        key = (conf_gt._version, tuple(conf_gt.shape))
+        if hit is None or hit[0]() is not conf_gt or hit[1] != key:
+            hit = self.__dict__["_gt_ids_cache"] = (weakref.ref(conf_gt), key, torch.where(conf_gt))
+        return hit[2]
 
     def _train_preds(self, img, pt_feat, pt3d, im_mask, pt_mask, conf_gt, ret_feats=False, mutual=False, match_thres=0.0, alpha=0.25,
                      gamma=2.0, train_percent=0.3, pad_gt=True):

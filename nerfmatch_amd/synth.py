@@ -214,6 +214,46 @@ def matcher_variant(name, seed=0):
     return cfg, sd
 
 
+FINE_VARIANTS = ("win3", "win4", "win7", "win8", "ffeat256", "fsa0", "fsa2", "fsa_lsa")
+
+
+def fine_variant(name, seed=0):
+    """(config, state dict) of the fine-stage option values outside the shipped yamls that the reference's constructor accepts
+    (nerfmatch_c2f_trainer.py:205-223) and the fine-stage kernels support -- all of them take the generic (unfused) kernels:
+      win3 / win4 / win7 / win8  window sides 3, 4 (even: the reference's unfold grid is one cell wider), 7, 8 (64 positions: the limit)
+      ffeat256                   256-d fine features (heads of dim 32): ffeat_proj 128 -> 256 on the backbone's fine map, pt_ffeat_proj 256 -> 256
+      fsa0 / fsa2                no fine self-attention layer / two of them
+      fsa_lsa                    the fine layer with locality self-attention (learnable log-scale)"""
+    rng = np.random.default_rng(2000 + seed)
+    cfg = matcher_config("c2f")
+    sd = matcher_state_dict("c2f", seed=seed, temperature=15.0, style="aligned")  # (peaked: the planted border / corner tokens are matched)
+    if name.startswith("win"):
+        cfg.win_sz = int(name[3:])
+    elif name == "ffeat256":
+        Cf = cfg.ffeat_dim = 256
+        for k in [k for k in sd if k.startswith(("pt_ffeat_proj.", "fine_preprocess.", "fine_sa."))]:
+            del sd[k]
+        _linear(sd, rng, "ffeat_proj", Cf, 128)
+        _linear(sd, rng, "pt_ffeat_proj.0", Cf, 256)
+        _linear(sd, rng, "pt_ffeat_proj.1", Cf, Cf)
+        _linear(sd, rng, "fine_preprocess.down_proj", Cf, 256)
+        _linear(sd, rng, "fine_preprocess.merge_feat", Cf, 2 * Cf)
+        _encoder_layer(sd, rng, "fine_sa.layers.0", Cf)
+    elif name == "fsa0":
+        cfg.fine_sa = 0
+        for k in [k for k in sd if k.startswith("fine_sa.")]:
+            del sd[k]
+    elif name == "fsa2":
+        cfg.fine_sa = 2
+        _encoder_layer(sd, rng, "fine_sa.layers.1", 128)
+    elif name == "fsa_lsa":
+        cfg.fsa_type = "lsa"
+        sd["fine_sa.layers.0.attention.attend.scale"] = torch.log(torch.tensor(16**-0.5)) + 0.1
+    else:
+        raise ValueError(name)
+    return cfg, sd
+
+
 # --------------------------------------------------------------------------------------
 # inputs
 # --------------------------------------------------------------------------------------

@@ -234,6 +234,9 @@ def c2f_forward_match(p, cfg, cfeat_map, ffeat_map, pt_feat, pt3d, im_mask=None,
     :319-328 (sequential cross attention, same weights), :330-351 (matching + fine stage).
     cfeat_map (B,256,h,w), ffeat_map (B,128,4h,4w) are the backbone's two outputs."""
     b, c, h, w = cfeat_map.shape
+    if "ffeat_proj.weight" in p:  # (ffeat_dim != the backbone's 128: a linear layer on the fine map's pixels, c2f_trainer.py:242-246)
+        ff = F.linear(ffeat_map.flatten(-2).permute(0, 2, 1), p["ffeat_proj.weight"], p["ffeat_proj.bias"])
+        ffeat_map = ff.permute(0, 2, 1).reshape(b, -1, *ffeat_map.shape[-2:])
     im = cfeat_map.flatten(-2).permute(0, 2, 1)
     if getattr(cfg, "im_pe", True):
         im = (cfeat_map + sine_pe_table(c, h, w)[None]).flatten(-2).permute(0, 2, 1)

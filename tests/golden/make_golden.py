@@ -801,6 +801,116 @@ def train_fixture(seed=5):
     np.savez_compressed(OUT / "matcher_train.npz", **to_np(fx))
 
 
+def fine_envelope_fixture(seed=0):
+    """The fine-stage option values beyond the shipped yamls (synth.FINE_VARIANTS: window sides 3 / 4 / 7 / 8, 256-d fine features,
+    0 / 2 fine layers, locality self-attention) through the reference's own NeRFMatcherMS.  B = 2 pairs with different masks, a 4 x 6
+    coarse grid (fine map 16 x 24: height != width), image tokens planted on points -- the four corner tokens and the border tokens
+    among them, so windows hang off the map.  Per variant:
+      fwd_*   forward(mutual=True) on the batch of 2 and on pair 0 alone (`p0_*`): match lists, mconf, expec_f, mpt2d_f, mpt3d;
+      f64_*   the same two forward passes of the reference in float64 (default dtype float64, model.double()) -- the bars of the
+              GPU tests are stated against these;
+      trn_*   one training step (GT padding on the numpy global RNG, seed `np_seed`): coarse / fine loss, padded ids, expec_f,
+              gradient norms + strided samples of every fine_sa.* / pt_ffeat_proj.* / ffeat_proj.* parameter and of ffeat / pt_feat."""
+    import nerfmatch.nerfmatch_c2f_trainer as c2f
+    from nerfmatch.utils.geometry import get_pixel_coords_grid
+    from nerfmatch.utils.metrics import compute_fine_match_loss_l2_std, compute_matching_loss
+
+    g = torch.Generator().manual_seed(577 + seed)
+    B, h, w, N = 2, 4, 6, 48
+    M = h * w
+    Himg, Wimg = h * 8, w * 8
+    cfeat = torch.randn(B, 256, h, w, generator=g)
+    ffeat = torch.randn(B, 128, h * 4, w * 4, generator=g)
+    pt_feat = torch.randn(B, N, 256, generator=g)
+    pt3d = torch.randn(B, N, 3, generator=g) * 2.0
+    pt2d = get_pixel_coords_grid(Wimg, Himg, ds=8).reshape(1, -1, 2).repeat(B, 1, 1)
+    conf_gt = torch.zeros(B, M, N, dtype=torch.bool)
+    pt2d_proj = torch.rand(B, N, 2, generator=g) * torch.tensor([Wimg, Himg])
+    border = [t for t in range(M) if t // w in (0, h - 1) or t % w in (0, w - 1)]  # (the four corners included)
+    tok = cfeat.flatten(-2).permute(0, 2, 1)
+    for b in range(B):
+        perm = torch.randperm(N, generator=g)
+        inner = [t for t in torch.randperm(M, generator=g).tolist() if t not in border][: 6 + 3 * b]
+        planted = border + inner
+        n_pl = len(planted)
+        pt_feat[b, perm[:n_pl]] = tok[b, planted] + 0.25 * torch.randn(n_pl, 256, generator=g)
+        conf_gt[b, torch.tensor(planted), perm[:n_pl]] = True
+        pt2d_proj[b, perm[:n_pl]] = pt2d[b, planted] + (torch.rand(n_pl, 2, generator=g) - 0.5) * 6.0
+    im_mask = torch.ones(B, M, dtype=torch.bool)
+    pt_mask = torch.ones(B, N, dtype=torch.bool)
+    im_mask[1, 9:12] = False
+    pt_mask[0, -4:] = False
+    img = torch.zeros(B, 3, Himg, Wimg)
+    NP_SEED = 4321
+    fx = dict(cfeat=cfeat, ffeat=ffeat, pt_feat=pt_feat, pt3d=pt3d, pt2d=pt2d, conf_gt=conf_gt, pt2d_proj=pt2d_proj, im_mask=im_mask,
+              pt_mask=pt_mask, weights_seed=seed, np_seed=NP_SEED)
+
+    def build(cfg, sd, cf, ff, dtype):
+        c2f.init_backbone_8_2 = lambda *a, **k: FixedBackbone((cf, ff), [256, 128])
+        model = c2f.NeRFMatcherMS(cfg)
+        res = model.load_state_dict(sd, strict=False)
+        assert not res.unexpected_keys and all(k.startswith("im_sa.") for k in res.missing_keys), res
+        return model.to(dtype)
+
+    def forward(model, tag, dtype):
+        torch.set_grad_enabled(False)
+        cf, ff = model.backbone.outs
+        for pre, sl in (("", slice(0, B)), ("p0_", slice(0, 1))):
+            model.backbone.outs = (cf[sl], ff[sl])
+            data = dict(image=img[sl].to(dtype), im_mask=im_mask[sl], pt3d=pt3d[sl].to(dtype), pt_feat=pt_feat[sl].to(dtype), pt_mask=pt_mask[sl],
+                        pt2d=pt2d[sl].to(dtype))
+            model.forward(data, ret_feats=False, mutual=True, match_thres=0.0)
+            b, i, j = data["match_ids"]
+            fx.update({f"{tag}_{pre}b_ids": b, f"{tag}_{pre}i_ids": i, f"{tag}_{pre}j_ids": j, f"{tag}_{pre}mconf": data["mconf"],
+                       f"{tag}_{pre}expec_f": data["expec_f"], f"{tag}_{pre}mpt2d_f": data["mpt2d_f"], f"{tag}_{pre}mpt3d": data["mpt3d"]})
+        return b, i
+
+    for name in synth.FINE_VARIANTS:
+        cfg, sd = synth.fine_variant(name, seed)
+        torch.set_default_dtype(torch.float32)
+        model = build(cfg, sd, cfeat, ffeat, torch.float32).eval()
+        b0, i0 = forward(model, f"{name}_fwd", torch.float32)
+        b2 = fx[f"{name}_fwd_b_ids"]
+        i2 = fx[f"{name}_fwd_i_ids"]
+        corners = [0, w - 1, (h - 1) * w, M - 1]
+        print(f"fine_envelope {name}: {len(b2)} matches (pair 0 alone {len(b0)}), border tokens matched "
+              f"{sum(int(t) in border for t in i2)}, corners {sorted(set(int(t) for t in i2) & set(corners))}")
+        torch.set_default_dtype(torch.float64)
+        m64 = build(cfg, {k: v.double() for k, v in sd.items()}, cfeat.double(), ffeat.double(), torch.float64).eval()
+        forward(m64, f"{name}_f64", torch.float64)
+        torch.set_default_dtype(torch.float32)
+        # one training step
+        torch.set_grad_enabled(True)
+        cf, ff, pf = cfeat.clone().requires_grad_(), ffeat.clone().requires_grad_(), pt_feat.clone().requires_grad_()
+        model = build(cfg, sd, cf, ff, torch.float32).train()
+        np.random.seed(NP_SEED)
+        data = dict(image=img, im_mask=im_mask, pt3d=pt3d.clone(), pt_feat=pf, pt_mask=pt_mask, pt2d=pt2d, conf_gt=conf_gt, pt2d_proj=pt2d_proj)
+        model.forward(data, training=True, ret_feats=True)
+        coarse_loss = compute_matching_loss(data["conf_matrix"], conf_gt)
+        mpt2d_f_gt, mpt2d_f, mpt2d_c, expec_f = data["mpt2d_f_gt_train"], data["mpt2d_f_train"], data["mpt2d_c_train"], data["expec_f"]
+        coarse_pos = (mpt2d_f_gt - mpt2d_c).norm(dim=-1) < model.coarse_dthres
+        fine_loss = compute_fine_match_loss_l2_std(mpt2d_f, mpt2d_f_gt, expec_f[:, 2], mask=coarse_pos)
+        loss = coarse_loss + fine_loss
+        loss.backward()
+        b, i, j = data["match_ids"]
+        t = f"{name}_trn_"
+        fx.update({t + "coarse_loss": coarse_loss, t + "fine_loss": fine_loss, t + "loss": loss, t + "b_ids": b, t + "i_ids": i, t + "j_ids": j,
+                   t + "pred_num": data["pred_num"], t + "expec_f": expec_f,
+                   t + "g_ffeat_norm": ff.grad.norm(), t + "g_ffeat_sub": ff.grad.flatten()[::211],
+                   t + "g_pt_feat_norm": pf.grad.norm(), t + "g_pt_feat_sub": pf.grad.flatten()[::37]})
+        for k, v in model.named_parameters():
+            if not k.startswith(("fine_sa.", "pt_ffeat_proj.", "ffeat_proj.")):
+                continue
+            assert v.grad is not None, (name, k)
+            key = k.replace(".", "__")
+            gflat = v.grad.flatten()
+            fx[f"{t}gn__{key}"] = gflat.norm()
+            fx[f"{t}gs__{key}"] = gflat if v.numel() <= 512 else gflat[::97]
+        print(f"  train: coarse {float(coarse_loss):.6f} fine {float(fine_loss):.6f} windows {len(b)} (pred {data['pred_num']})")
+    torch.set_grad_enabled(False)
+    np.savez_compressed(OUT / "matcher_fine_envelope.npz", **to_np(fx))
+
+
 # ----------------------------------------------------------------------------- multi-pair (SURVEY 8f rank 3) and scene cache (rank 2)
 def multi_pair_fixture(seed=0, k=3):
     """Top-k reference frames: the reference's own forward_multi_pair (nerfmatch_c2f_trainer.py:371-427,
@@ -910,6 +1020,9 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["envelope"]:  # round 6: option values beyond the shipped yamls
         envelope_fixture()
         sys.exit(0)
+    if sys.argv[1:] == ["fine_envelope"]:  # fine-stage option values beyond the shipped yamls (window side, width, layer count, lsa)
+        fine_envelope_fixture()
+        sys.exit(0)
     if sys.argv[1:] == ["smooth"]:  # only the three smooth NeRF fixtures
         nerf_fixture("r32_s32", "7scenes", H=32, W=64, S=32, stop_layer=3, seed=0)
         nerf_fixture("r128_s64_app", "cambridge", H=64, W=128, S=64, stop_layer=3, seed=1, sub_rays=2)
@@ -963,6 +1076,7 @@ if __name__ == "__main__":
     train_fixture(seed=5)
     postnorm_fixture()
     envelope_fixture()
+    fine_envelope_fixture()
     layer_grads_fixture()
     multi_pair_fixture(seed=0)
     scene_cache_fixture(seed=6)

@@ -1,5 +1,6 @@
 """CPU: host-side logic added in round 5 (no kernel calls): the calibration probe bundle, the speculative fine stage's capacity rule,
 the padding rule of ops.nerf_fwd, the timing proxy's choice of entry points."""
+import pytest
 import torch
 
 from nerfmatch_amd import _lib, latency, synth
@@ -202,3 +203,49 @@ def test_scene_cache_writer_thread_contents_and_errors(tmp_path, monkeypatch):
     except OSError as e:
         raised = "disk full" in str(e)
     assert raised
+
+
+@pytest.mark.parametrize("opt,val", [("win_sz", 1), ("win_sz", 9), ("win_sz", 11), ("ffeat_dim", 64), ("ffeat_dim", 136), ("ffeat_dim", 512)])
+def test_unsupported_fine_stage_options_refused_at_construction(opt, val):
+    """Fine-stage values the reference accepts but the kernels cannot run raise at construction, naming the option: win_sz**2 <= 64
+    (the expectation kernels' wavefront, the small-window attention's 64 tokens), ffeat_dim in {128, 256} with fine layers (head dims
+    16 / 32 of the small-window attention, LayerNorm widths)."""
+    cfg = synth.matcher_config("c2f")
+    setattr(cfg, opt, val)
+    with pytest.raises(ValueError, match=opt):
+        NeRFMatcherMS(cfg)
+
+
+@pytest.mark.parametrize("name", synth.FINE_VARIANTS)
+def test_supported_fine_stage_options_construct(name):
+    cfg, sd = synth.fine_variant(name)
+    m = NeRFMatcherMS(cfg)
+    res = m.load_state_dict(sd, strict=False)
+    assert not res.unexpected_keys and all(k.startswith(("im_sa.", "backbone.")) for k in res.missing_keys), res
+    cfg = synth.matcher_config("c2f")
+    cfg.fine_sa, cfg.ffeat_dim = 0, 64  # no fine layer: no attention / LayerNorm on the fine features, any width
+    NeRFMatcherMS(cfg)
+
+
+def test_gt_ids_follow_the_current_mask():
+    """_gt_ids caches torch.where(conf_gt) for the second caller of a step.  A mask freed and the next one allocated at the same address
+    (same shape, same _version after zeros + one index assignment) must not be served the previous step's ids."""
+    m = NeRFMatcherMS(synth.matcher_config("c2f"))
+    g = torch.Generator().manual_seed(0)
+    ptrs = set()
+    for step in range(8):
+        c = torch.zeros(2, 48, 64, dtype=torch.bool)
+        rows = torch.randperm(48, generator=g)[:20]
+        c[step % 2, rows, torch.randperm(64, generator=g)[:20]] = True
+        ptrs.add(c.data_ptr())
+        ids = m._gt_ids(c)
+        want = torch.where(c)
+        assert all(torch.equal(a, b) for a, b in zip(ids, want)), step
+        assert m._gt_ids(c) is ids  # the second caller of the same step is served from the cache
+        del c, ids
+    assert len(ptrs) < 8  # (the allocator did hand out a freed address again: the hazard was exercised)
+    c = torch.zeros(2, 48, 64, dtype=torch.bool)
+    c[1, 3, 4] = True
+    m._gt_ids(c)
+    c[0, 0, 0] = True  # an in-place change of the same tensor is seen too
+    assert all(torch.equal(a, b) for a, b in zip(m._gt_ids(c), torch.where(c)))

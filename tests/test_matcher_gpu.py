@@ -69,7 +69,11 @@ def test_layernorm(gpu, built_lib, dim):
     assert maxdiff(y, F.layer_norm(x, (dim,), g, b)) < 1e-5
 
 
-@pytest.mark.parametrize("B,L,S,H,D", [(1, 80, 96, 8, 32), (2, 200, 333, 8, 32), (1, 4800, 4800, 8, 32), (7, 25, 25, 8, 16), (3, 25, 25, 8, 32)])
+@pytest.mark.parametrize("B,L,S,H,D", [(1, 80, 96, 8, 32), (2, 200, 333, 8, 32), (1, 4800, 4800, 8, 32), (7, 25, 25, 8, 16), (3, 25, 25, 8, 32),
+                                       # the small-window kernel at the other window sides (3x3 .. 8x8), L != S, and the 64 / 65 switch
+                                       (2, 9, 9, 8, 16), (2, 16, 16, 8, 32), (2, 49, 49, 8, 16), (2, 49, 49, 8, 32), (2, 64, 64, 8, 16),
+                                       (2, 64, 64, 8, 32), (2, 64, 49, 8, 16), (2, 49, 64, 8, 32), (1, 65, 65, 8, 32), (1, 64, 65, 8, 32),
+                                       (1, 65, 64, 8, 32)])
 def test_attention(gpu, built_lib, B, L, S, H, D):
     q, k, v = rnd(B, L, H * D, seed=1), rnd(B, S, H * D, seed=2), rnd(B, S, H * D, seed=3)
     scale = D**-0.5

@@ -424,3 +424,46 @@ def test_option_envelope_oracle_vs_reference(name):
     assert torch.equal(i, fx[f"{name}_i_ids"]) and torch.equal(j, fx[f"{name}_j_ids"]) and len(i) > 5
     close(out["mconf"], fx[f"{name}_mconf"], 1e-6)
     close(out["conf_matrix"], fx[f"{name}_conf"], 1e-6)
+
+
+@pytest.mark.parametrize("name", synth.FINE_VARIANTS)
+def test_fine_envelope_oracle_vs_reference(name):
+    """Fine-stage option values beyond the shipped yamls (window sides 3 / 4 / 7 / 8, 256-d fine features, 0 / 2 fine layers, lsa): the
+    oracle against the reference's own NeRFMatcherMS (tests/golden/matcher_fine_envelope.npz) -- forward on the batch of 2 pairs and on
+    pair 0 alone, the reference's float64 evaluation, and the GT-padded training step's windows."""
+    fx = load_golden("matcher_fine_envelope")
+    cfg, p = synth.fine_variant(name, int(fx["weights_seed"]))
+    for pre, sl in (("", slice(0, 2)), ("p0_", slice(0, 1))):
+        args = (fx["cfeat"][sl], fx["ffeat"][sl], fx["pt_feat"][sl].clone(), fx["pt3d"][sl].clone(), fx["im_mask"][sl], fx["pt_mask"][sl])
+        out = mo.c2f_forward_match(p, cfg, *args, mutual=True)
+        b, i, j = out["match_ids"]
+        t = f"{name}_fwd_{pre}"
+        assert torch.equal(b, fx[t + "b_ids"]) and torch.equal(i, fx[t + "i_ids"]) and torch.equal(j, fx[t + "j_ids"]) and len(i) > 20
+        close(out["mconf"], fx[t + "mconf"], 1e-6)
+        close(out["expec_f"], fx[t + "expec_f"], 1e-5)
+        asm = mo.c2f_assemble(out, fx["pt2d"][sl], fx["pt3d"][sl], win_sz=cfg.win_sz)
+        close(asm["mpt2d_f"], fx[t + "mpt2d_f"], 1e-5)
+        close(asm["mpt3d"], fx[t + "mpt3d"], 0)
+        # the reference in float64 found the same matches; the oracle in float64 agrees with it to rounding
+        t64 = f"{name}_f64_{pre}"
+        assert torch.equal(i, fx[t64 + "i_ids"]) and torch.equal(j, fx[t64 + "j_ids"])
+        torch.set_default_dtype(torch.float64)
+        try:
+            o64 = mo.c2f_forward_match({k: v.double() for k, v in p.items()}, cfg, *(a.double() if a.is_floating_point() else a for a in args),
+                                       mutual=True)
+        finally:
+            torch.set_default_dtype(torch.float32)
+        assert torch.equal(o64["match_ids"][1], i) and torch.equal(o64["match_ids"][2], j)
+        close(o64["expec_f"], fx[t64 + "expec_f"], 1e-12)
+    # windows hang off the map: corner tokens are among the matches
+    h, w = fx["cfeat"].shape[-2:]
+    assert {0, w - 1, (h - 1) * w, h * w - 1} <= set(fx[f"{name}_fwd_i_ids"].tolist())
+    # training step: the same GT-padded windows from the same numpy draws
+    np.random.seed(int(fx["np_seed"]))
+    out = mo.c2f_forward_match(p, cfg, fx["cfeat"], fx["ffeat"], fx["pt_feat"].clone(), fx["pt3d"].clone(), fx["im_mask"], fx["pt_mask"],
+                               conf_gt=fx["conf_gt"])
+    t = f"{name}_trn_"
+    b, i, j = out["match_ids"]
+    assert torch.equal(b, fx[t + "b_ids"]) and torch.equal(i, fx[t + "i_ids"]) and torch.equal(j, fx[t + "j_ids"])
+    assert out["pred_num"] == int(fx[t + "pred_num"])
+    close(out["expec_f"], fx[t + "expec_f"], 1e-5)

@@ -98,7 +98,10 @@ def attn_precision(request):
 
 
 @pytest.mark.parametrize("B,L,S,H,D", [(1, 80, 96, 8, 32), (2, 200, 333, 8, 32), (1, 33, 1000, 8, 32), (7, 25, 25, 8, 16), (1, 1, 1, 8, 32),
-                                       (3, 129, 64, 8, 32), (1, 385, 127, 5, 32)])
+                                       (3, 129, 64, 8, 32), (1, 385, 127, 5, 32),
+                                       # the small-window shapes of window sides 3 .. 8, L != S, and the 64 / 65 switch
+                                       (2, 9, 9, 8, 16), (2, 16, 16, 8, 32), (2, 49, 49, 8, 16), (2, 49, 49, 8, 32), (2, 64, 64, 8, 16),
+                                       (2, 64, 64, 8, 32), (2, 64, 49, 8, 16), (2, 49, 64, 8, 32), (1, 65, 65, 8, 32), (1, 64, 65, 8, 32)])
 def test_attention_backward(gpu, built_lib, attn_precision, B, L, S, H, D):
     q, k, v = (rnd(B, n, H * D, seed=s).requires_grad_() for n, s in ((L, 1), (S, 2), (S, 3)))
     d_o = rnd(B, L, H * D, seed=4)
@@ -111,6 +114,10 @@ def test_attention_backward(gpu, built_lib, attn_precision, B, L, S, H, D):
     # a single key makes dq exactly 0 (P (dP - D) with dP = D): floor of 0.1, i.e. 2e-6 absolute in fp32; the split-bf16
     # products (16 significand bits per operand) leave ~3e-6 of |dO||V| ~ 10 there
     tol = 5e-4 if (S == 1 and attn_precision == "bf16x3") else 2e-5
+    if attn_precision == "bf16x3" and D == 32 and 1 < S <= 65 and L <= 65:
+        # the window-sized shapes on the split-bf16 kernel: 3-term products of 16-bit operand halves round at ~2^-16 = 1.5e-5 relative,
+        # and the largest dK entries (sums of L such products) reach 2-3 x that against the fp32 reference
+        tol = 5e-5
     assert rel(dq, q.grad, 0.1) < tol and rel(dk, k.grad, 0.1) < tol and rel(dv, v.grad, 0.1) < tol
 
 
@@ -270,6 +277,49 @@ def test_training_step_vs_reference(gpu, built_lib, coarse_only):
         assert abs(gf.norm().item() - float(fx[key])) < 1e-3 * float(fx[key]) + 1e-6, name
         checked += 1
     assert checked >= (50 if coarse_only else 65)
+
+
+@pytest.mark.parametrize("pad_gt", [True, False])
+def test_training_step_after_a_freed_mask_at_the_same_address(gpu, built_lib, pad_gt):
+    """Two consecutive steps of one model: step 1 on a decoy ground-truth mask of the fixture's shape, step 2 on the fixture's mask
+    written into the SAME device memory (zero_ + index assignment on a fresh tensor object: same address, same _version, same shape).
+    Step 2 must use its own ground-truth ids: GT padding (pad_gt, training) and feat_l2 (both) against the reference / the oracle."""
+    fx = load_golden("matcher_train")
+    model, cfeat, ffeat = build_model(fx, gpu)
+    buf = torch.empty(fx["conf_gt"].shape, dtype=torch.uint8, device=gpu)
+
+    def mask(ids):
+        m = torch.from_dlpack(buf).view(torch.bool)  # (a new tensor object with its own version counter over the same memory)
+        m.zero_()
+        m[ids] = True
+        return m
+
+    decoy = mask(torch.where(fx["conf_gt"].flip(2)))
+    d1 = batch(fx, gpu)
+    d1["conf_gt"] = decoy
+    np.random.seed(3)
+    model.forward_with_metrics(d1, training=pad_gt)
+    ptr, ver = decoy.data_ptr(), decoy._version
+    del d1, decoy
+    conf = mask(torch.where(fx["conf_gt"]))
+    assert conf.data_ptr() == ptr and conf._version == ver  # the hazard is exercised: the old (address, version, shape) key matched
+    data = batch(fx, gpu)
+    data["conf_gt"] = conf
+    np.random.seed(int(fx["np_seed"]))
+    metrics = model.forward_with_metrics(data, training=pad_gt)
+    p = {k: v.clone() for k, v in synth.matcher_state_dict("c2f", seed=int(fx["weights_seed"])).items()}
+    np.random.seed(int(fx["np_seed"]))
+    ref = to.c2f_train_step(p, synth.matcher_config("c2f"), fx["cfeat"], fx["ffeat"], fx["pt_feat"].clone(), fx["pt3d"], fx["pt2d"],
+                            fx["pt2d_proj"], fx["conf_gt"], fx["im_mask"], fx["pt_mask"])
+    assert abs(metrics["feat_l2"].item() - ref["feat_l2"].item()) < 1e-5
+    if pad_gt:
+        assert abs(metrics["coarse_loss"].item() - float(fx["coarse_loss"])) < 2e-6 * float(fx["coarse_loss"]) + 1e-6
+        b, i, j = data["match_ids"]
+        assert torch.equal(b.cpu(), fx["b_ids"]) and torch.equal(i.cpu(), fx["i_ids"]) and torch.equal(j.cpu(), fx["j_ids"])
+        assert data["pred_num"] == int(fx["pred_num"])
+        assert (data["expec_f"].detach().cpu() - fx["expec_f"]).abs().max() < 1e-4
+        assert abs(metrics["fine_loss"].item() - float(fx["fine_loss"])) < 1e-4 * float(fx["fine_loss"])
+        assert abs(metrics["loss"].item() - float(fx["loss"])) < 1e-4 * float(fx["loss"])
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
