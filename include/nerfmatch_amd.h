@@ -34,6 +34,8 @@ enum {
   NM_ERR_WORKSPACE = 4    /* workspace too small */
 };
 
+/* Bumped on every removed or re-signed symbol; nm_abi_version() of a loaded library must equal the binding's own number. */
+#define NM_ABI_VERSION 2
 int nm_abi_version(void);
 const char* nm_error_string(int code);
 
@@ -90,20 +92,16 @@ int nm_sample_coarse(const float* rays, const float* t_rand, int R, int S, float
 /* Hierarchical re-sampling: t_out[R,S+1] from t_in[R,S+1], weights[R,S], jitter[R,S+1].
  * Replaces resample_gaus_along_rays + sorted_piecewise_constant_pdf
  * (nerfmatch/nerf/render_utils.py:453-552, :583-597) including the `u + u + jitter` behaviour of the
- * randomized branch.  jitter may be NULL when randomized == 0. */
-int nm_resample(const float* t_in, const float* weights, const float* jitter, int R, int S, float padding,
-                int randomized, float* t_out, nmStream_t stream);
-/* Same, and additionally reports whether the result has the zero-width tail NM_NERF_ZERO_TAIL relies on:
+ * randomized branch.  jitter may be NULL when randomized == 0.  The jitter is given UNSCALED: the kernel multiplies it by
+ * `jitter_scale` where it reads it (one fp32 product, what the reference's `torch.rand_like(u) * (1 / n - eps)` computes,
+ * render_utils.py:472-476) -- saves the caller an elementwise launch; 1.0f for a jitter that is already scaled.
+ * The call also reports whether the result has the zero-width tail NM_NERF_ZERO_TAIL relies on:
  * *zero_tail_violation (device int, may be NULL) is set to 0 before the launch and raised (non-zero) when some fence post
  * j > S/2 does not sit at u = 1 - eps (cannot happen for 0 <= jitter; always raised when randomized == 0).  Hand the same
- * pointer to nm_nerf_fwd_bf16x3_ex: the decision "skip the tail or evaluate everything" is then taken on the device, with
+ * pointer to nm_nerf_fwd_bf16x3: the decision "skip the tail or evaluate everything" is then taken on the device, with
  * no host synchronisation and no promise by the caller. */
-int nm_resample_ex(const float* t_in, const float* weights, const float* jitter, int R, int S, float padding,
-                   int randomized, float* t_out, int* zero_tail_violation, nmStream_t stream);
-/* The same with the jitter given UNSCALED: the kernel multiplies it by `jitter_scale` where it reads it (one fp32 product, what the reference's
- * `torch.rand_like(u) * (1 / n - eps)` computes, render_utils.py:472-476) -- saves the caller an elementwise launch. */
-int nm_resample_scaled(const float* t_in, const float* weights, const float* jitter, float jitter_scale, int R, int S, float padding,
-                       int randomized, float* t_out, int* zero_tail_violation, nmStream_t stream);
+int nm_resample(const float* t_in, const float* weights, const float* jitter, float jitter_scale, int R, int S, float padding,
+                int randomized, float* t_out, int* zero_tail_violation, nmStream_t stream);
 
 /* Weights of one NeRF MLP in the reference's (torch nn.Linear, [out,in]) layout, HOST pointers.
  * Keys: {nerf_coarse|nerf_fine}.{pts_linears.i, alpha_linear, feature_linear, views_linears.0, rgb_linear}
@@ -130,8 +128,8 @@ enum {
   NM_NERF_SKIP_RGB = 1, /* do not evaluate the views layer (with feature_linear folded into it) and the rgb head; rgb output is not written */
   NM_NERF_FEAT_MAX = 2, /* feat/pts of the max-weight sample instead of the weighted sum (feat_comb == "max") */
   /* Premise: every interval s > S/2 of every ray has zero width (t[s+1] == t[s]) -- what nm_resample with
-   * randomized = 1 produces for any jitter >= 0 (a promise of the caller with nm_nerf_fwd_bf16x3; verified on the device
-   * when the flag of nm_resample_ex is handed to nm_nerf_fwd_bf16x3_ex), because the reference's `u + u + jitter` saturates at the upper half of the fence posts
+   * randomized = 1 produces for any jitter >= 0 (a promise of the caller when the split kernels get zero_tail_violation == NULL;
+   * verified on the device when they are handed the flag nm_resample wrote), because the reference's `u + u + jitter` saturates at the upper half of the fence posts
    * (nerfmatch/nerf/render_utils.py:477-496).  Such samples have alpha = 0, i.e. weight exactly 0 in every output, so
    * nm_nerf_fwd_bf16x3 evaluates samples 0 .. S/2 only and writes weight 0 for the rest: same results, ~half the
    * matrix work.  Honoured for S in {64, 128} and multiples of 256, raw == sample_feat == NULL, without NM_NERF_FEAT_MAX; ignored otherwise and by
@@ -155,7 +153,7 @@ int nm_nerf_fwd(const float* blob, const float* rays, const float* t, const floa
                 int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
                 float* rgb, float* depth, float* acc, float* raw, float* sample_feat, nmStream_t stream);
 /* Guarded form: the launch does nothing unless bit 0 of run_if[0] (device int32[16], required) is set when the kernel starts --
- * the decision is taken on the device, no host synchronisation.  Used as the fall-back of nm_nerf_fwd_fp16x3_ex: hand it the
+ * the decision is taken on the device, no host synchronisation.  Used as the fall-back of nm_nerf_fwd_fp16x3: hand it the
  * same outputs and that call's `status`; when an fp16 operand saturated there, this pass rewrites every output in fp32.
  * The flag is CONSUMED: after the rewrite bit 0 of run_if[0] is cleared and run_if[11] (a count of such events, sticky) goes up
  * by one; run_if[12] is scratch of this call.  NM_NERF_ZERO_TAIL is ignored (every sample is evaluated).
@@ -176,59 +174,49 @@ int nm_nerf_fwd_guarded(const float* blob, const float* rays, const float* t, co
 size_t nm_nerf_blob_bytes_bf16x3(void);
 size_t nm_nerf_workspace_bytes_bf16x3(void);
 int nm_nerf_pack_bf16x3(const nmNerfWeights* w, void* blob_host);
+/* The zero-tail decision can be taken on the device: `zero_tail_violation` is the flag nm_resample wrote for the very `t` passed here
+ * (device int, may be NULL = trust the NM_NERF_ZERO_TAIL flag, a promise of the caller).  With NM_NERF_ZERO_TAIL set and the flag
+ * raised the kernel evaluates every sample. */
 int nm_nerf_fwd_bf16x3(const void* blob, const float* rays, const float* t, const float* app_row, int R, int S,
                        int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
                        float* rgb, float* depth, float* acc, float* raw, float* sample_feat, void* workspace,
-                       nmStream_t stream);
-/* Same with the zero-tail decision taken on the device: `zero_tail_violation` is the flag nm_resample_ex wrote for the very
- * `t` passed here (device int, may be NULL = trust the NM_NERF_ZERO_TAIL flag as nm_nerf_fwd_bf16x3 does).  With
- * NM_NERF_ZERO_TAIL set and the flag raised the kernel evaluates every sample. */
-int nm_nerf_fwd_bf16x3_ex(const void* blob, const float* rays, const float* t, const float* app_row, int R, int S,
-                          int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
-                          float* rgb, float* depth, float* acc, float* raw, float* sample_feat, void* workspace,
-                          const int* zero_tail_violation, nmStream_t stream);
+                       const int* zero_tail_violation, nmStream_t stream);
 
 /* Same pass with the operands split into fp16 hi / lo parts instead of bf16 ones (22 mantissa bits instead of 16; the three
  * products run on v_mfma_f32_32x32x16_f16 at the bf16 rate; operands beyond +-65504 saturate): fp32-class results also on
  * trained-like scenes (densities of +-1e4, opacity saturating within a few samples), where the bf16 split leaves the
  * compositing weights 7e-4 off -- tests/golden/nerf_surface_r512_s128.npz, DESIGN.md section 3.1b.  Same blob size, workspace
- * and arguments as nm_nerf_fwd_bf16x3_ex; the blob comes from nm_nerf_pack_fp16x3.  Replaces the same reference lines:
- * nerfmatch/nerf/renderer.py:119-180, nerf/models/nerf.py:94-144, nerf/render_utils.py:176-230. */
-int nm_nerf_pack_fp16x3(const nmNerfWeights* w, void* blob_host);
-/* Round 4 -- power-of-two operand scaling, range telemetry and a saturation flag for the fp16 split.
- * An fp16 hi/lo pair carries 22 significant bits only while its lo part is a normal fp16 number (|x| >~ 2^-3); the pack step
+ * and arguments as nm_nerf_fwd_bf16x3, plus `status`; the blob comes from nm_nerf_pack_fp16x3.  Replaces the same reference lines:
+ * nerfmatch/nerf/renderer.py:119-180, nerf/models/nerf.py:94-144, nerf/render_utils.py:176-230.
+ * Power-of-two operand scaling, range telemetry and a saturation flag for the fp16 split:
+ * an fp16 hi/lo pair carries 22 significant bits only while its lo part is a normal fp16 number (|x| >~ 2^-3); the pack step
  * therefore multiplies every weight group by a power of two chosen from its own maximum (constants: cannot saturate) and the
  * kernel carries the hidden activations of layer l at 2^act_log2[l] times their value; the re-packing of a finished layer
  * folds the change of scale into its bias add (one fma, exact) and every output leaves the kernel in true units.
- *   act_log2 (host, 12 ints, NULL = {12, 0,...,0, 12, 0}): [0] IPE input (|x| <= 1, <= 15), [1..7] hidden input of pts layers
- *   1..7, [8] layer 7's output = input of the density head and of the views layer (feature_linear has no activation: the pack
- *   step multiplies it into the views layer's hidden columns, the kernels never run it as a layer), [9] ignored (kept for the
- *   12-int layout), [10] direction PE (<= 15), [11] appearance row.
- * nm_nerf_pack_fp16x3 == nm_nerf_pack_fp16x3_scaled(w, NULL, blob): scaled weights, activations as they are (round 3).
- * nm_nerf_fwd_fp16x3_ex = nm_nerf_fwd_fp16x3 + `status` (device int32[16], zeroed by the caller, may be NULL):
+ *   act_log2 (host, 12 ints, NULL = {12, 0,...,0, 12, 0}: scaled weights, activations as they are): [0] IPE input (|x| <= 1, <= 15),
+ *   [1..7] hidden input of pts layers 1..7, [8] layer 7's output = input of the density head and of the views layer (feature_linear
+ *   has no activation: the pack step multiplies it into the views layer's hidden columns, the kernels never run it as a layer),
+ *   [9] ignored (kept for the 12-int layout), [10] direction PE (<= 15), [11] appearance row.
+ * `status` (device int32[16], zeroed by the caller, may be NULL):
  *   status[0] |= 1   when some operand of the launch reached +-65504 (it was clamped): the results are NOT to be trusted --
  *                    launch nm_nerf_fwd_guarded(fp32 blob, same arguments, run_if = status) behind it (which clears the bit again
  *                    and counts the event in status[11]);
  *   status[1 + k]    = max over the launch of the bit pattern of |value| re-packed to fp16 in range slot k (k = 0..7: output of
  *                    pts layer k at the scale act_log2[k + 1]; k = 8: unused, stays 0; k = 9: views-layer extra inputs): divide by
  *                    2^act_log2 to get activation ranges, choose act_log2 with >= 2^4 headroom (NeRF.calibrate does). */
-int nm_nerf_pack_fp16x3_scaled(const nmNerfWeights* w, const int* act_log2, void* blob_host);
-int nm_nerf_fwd_fp16x3_ex(const void* blob, const float* rays, const float* t, const float* app_row, int R, int S,
-                          int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
-                          float* rgb, float* depth, float* acc, float* raw, float* sample_feat, void* workspace,
-                          const int* zero_tail_violation, int* status, nmStream_t stream);
+int nm_nerf_pack_fp16x3(const nmNerfWeights* w, const int* act_log2, void* blob_host);
 int nm_nerf_fwd_fp16x3(const void* blob, const float* rays, const float* t, const float* app_row, int R, int S,
                        int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
                        float* rgb, float* depth, float* acc, float* raw, float* sample_feat, void* workspace,
-                       const int* zero_tail_violation, nmStream_t stream);
+                       const int* zero_tail_violation, int* status, nmStream_t stream);
 
 /* Pointwise forward / backward of ONE NeRF MLP on the fused kernel's K-loop machinery (round 4): the fine pass of the iNeRF
  * refinement (nerfmatch/nerfmatch_evaluator.py:348-430), where only d loss / d (ray origin, view
  * direction) is needed -- dX of every layer, no dW.  bf16 hi/lo split (three products, fp32 accumulate).
- *   forward : xi [n,96] (IPE, nm_inerf_encode), xd [n,48] -> out4 [n,4] = (rgb logits r g b, raw sigma) for nm_inerf_composite(_ex)
+ *   forward : xi [n,96] (IPE, nm_inerf_encode), xd [n,48] -> out4 [n,4] = (rgb logits r g b, raw sigma) for nm_inerf_composite
  *             (logit = out4, sig = out4 + 3, ld = 4) and `gates` (device, nm_nerf_points_gate_bytes(n)): one bit per ReLU
  *             activation of the nine layers -- all the backward pass needs from the forward one;  blob: nm_nerf_pack_bf16x3
- *   backward: g4 [n,4] = d loss / d (logits, sigma) (nm_inerf_composite_bwd(_ex) with ld = 4) -> g_xi0, g_xi5 [n,96]: the two
+ *   backward: g4 [n,4] = d loss / d (logits, sigma) (nm_inerf_composite_bwd with ld = 4) -> g_xi0, g_xi5 [n,96]: the two
  *             contributions to d loss / d xi (through layer 0 and through the skip connection; their sum feeds
  *             nm_inerf_encode_bwd), g_xd [n,48];  blob_bwd: the transposed weights, nm_nerf_pack_bwd_bf16x3 (host -> host). */
 size_t nm_nerf_blob_bytes_bwd_bf16x3(void);
@@ -236,19 +224,17 @@ size_t nm_nerf_points_gate_bytes(int n);
 int nm_nerf_pack_bwd_bf16x3(const nmNerfWeights* w, void* blob_host);
 int nm_nerf_points_fwd_bf16x3(const void* blob, const float* xi, const float* xd, int n, float* out4, void* gates, nmStream_t stream);
 /* forward, "from rays" form: sample n = (ray n / S_act, interval n % S_act) is encoded inside the kernel (nm_inerf_encode's formulas:
- * frustum Gaussian of [z[s], z[s+1]], IPE with exact sine / exponential, direction PE, appearance row) -- no xi / xd arrays. */
+ * frustum Gaussian of [z[s], z[s+1]], IPE with exact sine / exponential, direction PE, appearance row) -- no xi / xd arrays.
+ * With a TAPPED layer (the matching term of the refinement, `use_match_loss`, nerfmatch/nerfmatch_evaluator.py:420-441, reads the rendered
+ * features pt_feat = sum_s w_s h_tap(s)): additionally feats [R S_act, 256] row-major <- the post-ReLU activations of pts layer `tap_layer`
+ * (0..7): the `feats` operand of nm_inerf_ray_sums / nm_inerf_ray_sums_bwd.  No tap: feats NULL and tap_layer -1 (any other mix: NM_ERR_ARG). */
 int nm_nerf_points_fwd_rays_bf16x3(const void* blob, const float* rays, const float* z, int R, int S, int S_act, const float* app_row,
-                                   float* out4, void* gates, nmStream_t stream);
+                                   int tap_layer, float* out4, void* gates, float* feats, nmStream_t stream);
 int nm_nerf_points_bwd_bf16x3(const void* blob_bwd, const float* g4, const void* gates, int n, float* g_xi0, float* g_xi5, float* g_xd,
                               nmStream_t stream);
-/* The same two passes with a TAPPED layer (round 5): the matching term of the refinement (`use_match_loss`,
- * nerfmatch/nerfmatch_evaluator.py:420-441) reads the rendered features pt_feat = sum_s w_s h_tap(s) and sends a gradient back into them.
- *   forward : additionally feats [R S_act, 256] row-major <- the post-ReLU activations of pts layer `tap_layer` (0..7): the `feats` operand of
- *             nm_inerf_ray_sums / nm_inerf_ray_sums_bwd (feats NULL and tap_layer -1: exactly nm_nerf_points_fwd_rays_bf16x3)
- *   backward: d loss / d h_tap(n) += tap_weights[n] * g_pt_feat[n / S_act][:] (product, then sum) before that layer's ReLU gate, i.e. what the
- *             GEMM chain receives as nm_inerf_ray_sums_bwd's g_feats -- which then need not exist (pass g_feats NULL there). */
-int nm_nerf_points_fwd_rays_tap_bf16x3(const void* blob, const float* rays, const float* z, int R, int S, int S_act, const float* app_row,
-                                       int tap_layer, float* out4, void* gates, float* feats, nmStream_t stream);
+/* The backward pass with the TAPPED layer of nm_nerf_points_fwd_rays_bf16x3, which sends a gradient back into the rendered features:
+ * d loss / d h_tap(n) += tap_weights[n] * g_pt_feat[n / S_act][:] (product, then sum) before that layer's ReLU gate, i.e. what the
+ * GEMM chain receives as nm_inerf_ray_sums_bwd's g_feats -- which then need not exist (pass g_feats NULL there). */
 int nm_nerf_points_bwd_tap_bf16x3(const void* blob_bwd, const float* g4, const void* gates, int R, int S_act, int tap_layer,
                                   const float* tap_weights, const float* g_pt_feat, float* g_xi0, float* g_xi5, float* g_xd, nmStream_t stream);
 
@@ -277,15 +263,14 @@ int nm_unnormalize_points(const float* pts, const float* unnorm_host, int n, flo
  *                        xd [n,48] = [dir PE (27) | appearance row (16) | zero padding]; var from the (detached) frustum
  *   nm_inerf_encode_bwd  d loss / d xi, d loss / d xd  ->  g_o [R,3] (ray origins), g_v [R,3] (rays[:, 8:11])
  *   nm_inerf_composite   rgb logits / raw sigma (column 0..2 / 0 of row-major [n, ld] buffers) -> rgb_map [R,3],
- *                        white background, delta = dz * |rays[:, 3:6]| (render_utils.py:187-230)
+ *                        white background, delta = dz * |rays[:, 3:6]| (render_utils.py:187-230); also writes the
+ *                        compositing weights [R, S_act] (may be NULL: not wanted)
  *   nm_inerf_composite_bwd  G = d loss / d rgb_map -> g_logit [n,ld], g_sigma [n,ld] (unused columns zeroed),
- *                        g_d [R,3] (rays[:, 3:6], through |d|)
+ *                        g_d [R,3] (rays[:, 3:6], through |d|); g_weights [R, S_act] is added to the weights' gradient (NULL: none)
  * Matching term (`use_match_loss`, nerfmatch_evaluator.py:420-441): the fine weights also feed the matcher.
- *   nm_inerf_composite_ex      additionally writes the compositing weights [R, S_act] (NULL: as nm_inerf_composite)
  *   nm_inerf_ray_sums          pt_feat [R,C] = sum_s w_s feats[r S_act + s], pts [R,3] = sum_s w_s (o + t_mean d): :423-425
  *                              (the Gaussian means are the detached sampler's: constants of the backward pass)
  *   nm_inerf_ray_sums_bwd      d loss / d pt_feat [R,C], d loss / d pts [R,3] -> g_feats [n,C] (may be NULL: not written), g_weights [R, S_act]
- *   nm_inerf_composite_bwd_ex  as nm_inerf_composite_bwd with g_weights added to the weights' gradient (NULL: none)
  * ---------------------------------------------------------------------------------------------- */
 int nm_inerf_encode(const float* rays, const float* z, int R, int S, int S_act, const float* app_row, float* xi, float* xd,
                     nmStream_t stream);
@@ -301,18 +286,13 @@ int nm_inerf_encode_bwd2(const float* rays, const float* z, int R, int S, int S_
 int nm_inerf_pose_grad(const float* Kinv_host, const float* pose_host, int H, int W, int ds, const float* g_o, const float* g_v,
                        const float* g_d, int R, float* g_pose, nmStream_t stream);
 int nm_inerf_composite(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays, int R, int S,
-                       int S_act, float* rgb_map, nmStream_t stream);
+                       int S_act, float* rgb_map, float* weights, nmStream_t stream);
 int nm_inerf_composite_bwd(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays,
-                           const float* g_rgb_map, int R, int S, int S_act, float* g_logit, float* g_sigma, float* g_d,
-                           nmStream_t stream);
-int nm_inerf_composite_ex(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays, int R, int S,
-                          int S_act, float* rgb_map, float* weights, nmStream_t stream);
-int nm_inerf_composite_bwd_ex(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays,
-                              const float* g_rgb_map, const float* g_weights, int R, int S, int S_act, float* g_logit,
-                              float* g_sigma, float* g_d, nmStream_t stream);
+                           const float* g_rgb_map, const float* g_weights, int R, int S, int S_act, float* g_logit,
+                           float* g_sigma, float* g_d, nmStream_t stream);
 /* The same two passes on the fused fine field's own output (round 6): out4 [n, 4] = rgb logits | raw sigma per sample, as nm_nerf_points_fwd*_bf16x3
  * writes them; g_out4 [n, 4] = d loss / d (logits, sigma), what nm_nerf_points_bwd*_bf16x3 reads.  One wavefront per ray (prefix product / suffix
- * sum over lanes), 16-byte accesses; weights / g_weights as in the _ex forms (may be NULL).  S_act <= 1024. */
+ * sum over lanes), 16-byte accesses; weights / g_weights as above (may be NULL).  S_act <= 1024. */
 int nm_inerf_composite4(const float* out4, const float* z, const float* rays, int R, int S, int S_act, float* rgb_map, float* weights,
                         nmStream_t stream);
 int nm_inerf_composite4_bwd(const float* out4, const float* z, const float* rays, const float* g_rgb_map, const float* g_weights, int R, int S,
@@ -328,23 +308,20 @@ int nm_inerf_ray_sums_bwd(const float* weights, const float* feats, int C, const
 
 enum { NM_ACT_NONE = 0, NM_ACT_RELU = 1, NM_ACT_GELU = 2 };
 
-/* y[M,N] = act(x[M,K] . w[N,K]^T + bias[N]) + residual[M,N]   (bias / residual may be NULL).
+/* y[M,N] = (act(x[M,K] . w[N,K]^T + bias[N] + pre[M,N]) + residual[M,N]) * [gate[M,N] > 0]   (bias / pre / residual / gate may be NULL).
  * The nn.Linear calls of MultiHeadAttention / FeedForwardNetwork / pt_pe_proj / pt_ffeat_proj
- * (nerfmatch/modules/attention.py:101-103,114,145-147; nerfmatch/nerfmatch_c2f_trainer.py:152-160). */
-int nm_linear(const float* x, const float* w, const float* bias, const float* residual, int M, int N, int K, int act,
-              float* y, nmStream_t stream);
+ * (nerfmatch/modules/attention.py:101-103,114,145-147; nerfmatch/nerfmatch_c2f_trainer.py:152-160).
+ * `pre` lets a layer with a concatenated input be two GEMMs (the NeRF skip layer, the views layer); `gate` applies the ReLU
+ * derivative of a saved activation in the backward GEMMs of the iNeRF refinement. */
+int nm_linear(const float* x, const float* w, const float* bias, const float* pre, const float* residual, const float* gate,
+              int M, int N, int K, int act, float* y, nmStream_t stream);
 
-/* The same layer on the bf16 matrix cores with fp32-accurate hi/lo operand splitting (cf. nm_nerf_fwd_bf16x3).
+/* The same layer (same epilogue) on the bf16 matrix cores with fp32-accurate hi/lo operand splitting (cf. nm_nerf_fwd_bf16x3).
  * The weight matrix is split and laid out once: nm_linear_pack_bf16x3(w [N,K] device, blob device of
  * nm_linear_blob_bytes_bf16x3(N, K) bytes) -- a device-side kernel, asynchronous on `stream`.
  * Requires K % 8 == 0 and N % 8 == 0 (NM_ERR_UNSUPPORTED otherwise; use nm_linear). */
-/* General epilogue (both arithmetic paths): y = (act(x . w^T + bias + pre) + residual) * [gate > 0]; pre / residual / gate
- * are [M,N] or NULL.  `pre` lets a layer with a concatenated input be two GEMMs (the NeRF skip layer, the views layer);
- * `gate` applies the ReLU derivative of a saved activation in the backward GEMMs of the iNeRF refinement. */
-int nm_linear_ex(const float* x, const float* w, const float* bias, const float* pre, const float* residual, const float* gate,
-                 int M, int N, int K, int act, float* y, nmStream_t stream);
-int nm_linear_ex_bf16x3(const float* x, const void* blob, const float* bias, const float* pre, const float* residual,
-                        const float* gate, int M, int N, int K, int act, float* y, nmStream_t stream);
+int nm_linear_bf16x3(const float* x, const void* blob, const float* bias, const float* pre, const float* residual,
+                     const float* gate, int M, int N, int K, int act, float* y, nmStream_t stream);
 size_t nm_linear_blob_bytes_bf16x3(int N, int K);
 /* Fused q|k|v (n_q = 32 heads) or k|v (n_q = 0) projection of an attention layer, head_dim 32, split-bf16 path: the weight
  * blob packs the [n_q + 64 heads, K] stack of proj_q / proj_k / proj_v (attention.py:150-166); the q columns are written as
@@ -360,8 +337,6 @@ int nm_linear_pack_bf16x3(const float* w, int N, int K, void* blob, nmStream_t s
  * w^T, so that nm_linear_bf16x3(dy, blob) = dy . w is the layer's input gradient (autograd's dx = dy @ W, done by torch in the reference)
  * without a transposed copy of the weight in between.  nm_linear_blob_bytes_bf16x3(N, K) bytes. */
 int nm_linear_pack_t_bf16x3(const float* w, int N, int K, void* blob, nmStream_t stream);
-int nm_linear_bf16x3(const float* x, const void* blob, const float* bias, const float* residual, int M, int N, int K,
-                     int act, float* y, nmStream_t stream);
 
 /* Row-wise LayerNorm over `dim` (<= 1024, multiple of 64), eps as nn.LayerNorm (1e-5).
  * (nerfmatch/modules/attention.py:196-207, :229-230, :238). */
@@ -374,26 +349,21 @@ int nm_layernorm2(const float* x0, const float* gamma0, const float* beta0, int 
 
 /* Softmax multi-head attention without materialising the (L,S,H) score tensor.
  * q [B,L,H*D], k,v [B,S,H*D], out [B,L,H*D]; D in {16,32}; scores are (q*scale).k.
- * Replaces FullAttention.forward / LocalitySelfAttention.forward (nerfmatch/modules/attention.py:53-57, :71-81). */
-int nm_attention(const float* q, const float* k, const float* v, int B, int L, int S, int heads, int head_dim,
-                 float scale, float* out, nmStream_t stream);
-/* Same with explicit row strides (in floats, multiples of 4): q/k/v may be column slices of one fused projection
- * buffer, e.g. [B*L, 3*H*D] written by a single nm_linear with the concatenated proj_q|proj_k|proj_v weights. */
-int nm_attention_ld(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S,
-                    int heads, int head_dim, float scale, float* out, nmStream_t stream);
-/* Same with flags: NM_ATTN_BF16X3 evaluates QK^T and PV on the bf16 matrix cores with hi/lo operand splitting
- * (fp32-accurate: ~1e-6 on the tokens; head_dim 32 only, ignored for the small-sequence kernel).  That kernel streams
- * pre-split operands from a workspace, so the flag needs nm_attention_ws: nm_attention_ex returns NM_ERR_WORKSPACE for it. */
+ * Replaces FullAttention.forward / LocalitySelfAttention.forward (nerfmatch/modules/attention.py:53-57, :71-81).
+ * ldq / ldk / ldv: row strides in floats (>= H*D, multiples of 4): q/k/v may be column slices of one fused projection
+ * buffer, e.g. [B*L, 3*H*D] written by a single nm_linear with the concatenated proj_q|proj_k|proj_v weights.
+ * flags: NM_ATTN_BF16X3 evaluates QK^T and PV on the bf16 matrix cores with hi/lo operand splitting (fp32-accurate: ~1e-6 on
+ * the tokens; head_dim 32 only; ignored for head_dim 16 and for the small-sequence kernel of <= 64-token windows).  On that
+ * route K and V are split into bf16 hi/lo MFMA operands once per call into `workspace` (device,
+ * nm_attention_workspace_bytes(B, S, heads) bytes; one per stream) and streamed from there by LDS DMA (attention_v2.hip);
+ * workspace == NULL where the split kernel applies: NM_ERR_WORKSPACE.  The other routes take no workspace (may be NULL).
+ * nlse_out (may be NULL): the forward pass keeps what the backward pass needs -- the split-bf16 kernel also writes
+ * nlse_out[B][heads][L] = -(log-sum-exp of the query's scaled scores) in the log2 domain, for nm_attention_bwd's `nlse`.
+ * Only that route produces it: nlse_out != NULL on any other route is NM_ERR_UNSUPPORTED. */
 enum { NM_ATTN_BF16X3 = 1 };
-int nm_attention_ex(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S,
-                    int heads, int head_dim, float scale, int flags, float* out, nmStream_t stream);
-/* Same with a scratch buffer (device, nm_attention_workspace_bytes(B, S, heads) bytes; one per stream): with
- * NM_ATTN_BF16X3 and head_dim 32, K and V are split into bf16 hi/lo MFMA operands once per call into `workspace` and
- * streamed from there by LDS DMA (attention_v2.hip).  Other flags or shapes (head_dim 16, <= 64-token windows): identical to
- * nm_attention_ex without the flag; workspace == NULL where the split kernel applies: NM_ERR_WORKSPACE. */
 size_t nm_attention_workspace_bytes(int B, int S, int heads);
-int nm_attention_ws(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S,
-                    int heads, int head_dim, float scale, int flags, void* workspace, float* out, nmStream_t stream);
+int nm_attention(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S, int heads,
+                 int head_dim, float scale, int flags, void* workspace, float* out, float* nlse_out, nmStream_t stream);
 
 /* The part of a pre-norm encoder layer behind the attention as ONE launch:
  *     y = xh + W2 . gelu(W1 . LN2(xh + att . Wo^T) + b1) + b2          (rows x 256 everywhere, split-bf16 products)
@@ -469,7 +439,7 @@ int nm_cat_fourier_bwd(const float* dy, const float* pt3d, int n, int C, int num
  * modules/extract_matches.py:21-36.
  *   im [P,M,C], pt [P,N,C], im_mask [P,M] / pt_mask [P,N] uint8 or NULL; out_i / out_j / out_conf [P,M] (valid prefix:
  *   counts[p]; the slots behind it are written as index 0 / confidence 0); C in {64,128,256,512}; |scale| log2(e) <= 60 (cosine similarities are bounded by |scale|: one fixed shift
- *   serves both soft-maxes) -- otherwise NM_ERR_UNSUPPORTED: use nm_dual_softmax_match_ex per pair. */
+ *   serves both soft-maxes) -- otherwise NM_ERR_UNSUPPORTED: use nm_dual_softmax_match per pair. */
 size_t nm_match_fused_workspace_bytes(int P, int M, int N, int C);
 int nm_dual_softmax_match_fused(const float* im, const float* pt, int P, int M, int N, int C, float scale, const uint8_t* im_mask,
                                 const uint8_t* pt_mask, float threshold, int mutual, int64_t* out_i, int64_t* out_j,
@@ -484,22 +454,18 @@ int nm_dual_softmax_match_fused(const float* im, const float* pt, int P, int M, 
  *   conf [M,N] or NULL (not materialised in HBM when NULL... see DESIGN.md)
  *   im_norm [M,C], pt_norm[N,C] or NULL: the normalised features (ret_feats)
  *   out_i[M], out_j[M] int64, out_conf[M] f32: compacted matches sorted by i; count (dev int): number of matches
- *   workspace: nm_match_workspace_bytes(M,N,C) bytes of device scratch */
-size_t nm_match_workspace_bytes(int M, int N, int C);
-int nm_dual_softmax_match(const float* im, const float* pt, int M, int N, int C, float scale, const uint8_t* im_mask,
-                          const uint8_t* pt_mask, float threshold, int mutual, float* conf, float* im_norm,
-                          float* pt_norm, int64_t* out_i, int64_t* out_j, float* out_conf, int* count, void* workspace,
-                          size_t workspace_bytes, nmStream_t stream);
-/* Same with flags: NM_MATCH_BF16X3 computes the similarity matrix on the split-bf16 matrix-core path (cf.
+ *   workspace: nm_match_workspace_bytes(M,N,C) bytes of device scratch
+ * flags: NM_MATCH_BF16X3 computes the similarity matrix on the split-bf16 matrix-core path (cf.
  * nm_linear_bf16x3; needs N % 8 == 0, otherwise the fp32 path is taken).  The softmax sweeps and the equality tests of the
- * selection are unchanged.  NM_MATCH_STATS_ONLY (round 6) stops behind the similarity matrix and the four soft-max statistics -- what
+ * selection are unchanged.  NM_MATCH_STATS_ONLY stops behind the similarity matrix and the four soft-max statistics -- what
  * nm_match_focal_loss / nm_match_focal_loss_bwd read from the workspace: the loss of iNeRF's matching term consumes neither the confidence
  * matrix nor a match list (nerfmatch_evaluator.py:429-441) --; conf / out_i / out_j / out_conf / count may be NULL and are not written. */
 enum { NM_MATCH_BF16X3 = 1, NM_MATCH_STATS_ONLY = 2 };
-int nm_dual_softmax_match_ex(const float* im, const float* pt, int M, int N, int C, float scale, const uint8_t* im_mask,
-                             const uint8_t* pt_mask, float threshold, int mutual, int flags, float* conf, float* im_norm,
-                             float* pt_norm, int64_t* out_i, int64_t* out_j, float* out_conf, int* count, void* workspace,
-                             size_t workspace_bytes, nmStream_t stream);
+size_t nm_match_workspace_bytes(int M, int N, int C);
+int nm_dual_softmax_match(const float* im, const float* pt, int M, int N, int C, float scale, const uint8_t* im_mask,
+                          const uint8_t* pt_mask, float threshold, int mutual, int flags, float* conf, float* im_norm,
+                          float* pt_norm, int64_t* out_i, int64_t* out_j, float* out_conf, int* count, void* workspace,
+                          size_t workspace_bytes, nmStream_t stream);
 
 /* 5x5 (win x win) windows, stride 4, zero padding win/2, of the fine map ffeat[C,Hf,Wf] gathered at coarse cells
  * i_ids[K] (row-major over (Hf/4, Wf/4)): out[K, win*win, C].
@@ -569,13 +535,11 @@ int nm_fine_expectation(const float* pt_f, const float* win_f, const int* count,
 size_t nm_linear_wgrad_workspace_bytes(int M, int N, int K);
 int nm_linear_wgrad(const float* dy, const float* x, int M, int N, int K, int accumulate, float* dw, void* workspace,
                     size_t workspace_bytes, nmStream_t stream);
-/* The same product on the bf16 matrix cores with hi/lo operand splitting (round 6; the arithmetic of nm_linear_bf16x3, i.e. of the dX GEMMs of
- * the same backward pass): N even, K a multiple of 4; same workspace function.  dW of nn.Linear under loss.backward() with the split arithmetic selected. */
-int nm_linear_wgrad_bf16x3(const float* dy, const float* x, int M, int N, int K, int accumulate, float* dw, void* workspace,
+/* The same product on the bf16 matrix cores with hi/lo operand splitting (the arithmetic of nm_linear_bf16x3, i.e. of the dX GEMMs of
+ * the same backward pass): N even, K a multiple of 4; same workspace function.  dW of nn.Linear under loss.backward() with the split arithmetic selected.
+ * db (may be NULL): the bias gradient db [N] = column sums of dy from the same launch (dy is read once for both; accumulate applies to dw and db alike). */
+int nm_linear_wgrad_bf16x3(const float* dy, const float* x, int M, int N, int K, int accumulate, float* dw, float* db, void* workspace,
                            size_t workspace_bytes, nmStream_t stream);
-/* ... and the bias gradient db [N] = column sums of dy from the same launch (dy is read once for both; accumulate applies to dw and db alike). */
-int nm_linear_wgrad_bias_bf16x3(const float* dy, const float* x, int M, int N, int K, int accumulate, float* dw, float* db, void* workspace,
-                                size_t workspace_bytes, nmStream_t stream);
 /* bias gradient out[N] (+)= sum_m dy[m,:] (float atomics: order-dependent in the last bits). */
 int nm_col_sum(const float* dy, int M, int N, int accumulate, float* out, nmStream_t stream);
 /* exact-erf GELU (nn.GELU(), modules/attention.py:136-154) as a separate pass over the pre-activations u (training keeps
@@ -593,25 +557,18 @@ int nm_layernorm_bwd(const float* x, const float* gamma, const float* dy, int ro
 int nm_l2norm_bwd(const float* f, const float* dy, int rows, int dim, float* df, nmStream_t stream);
 
 /* Backward of softmax attention (autograd through FullAttention.forward, modules/attention.py:44-57).  q/k/v/o/d_o and the
- * three gradients are row-pitched like nm_attention_ld.  head_dim 32: flash-style recomputation on the fp32 matrix cores
+ * three gradients are row-pitched like nm_attention's q/k/v.  head_dim 32: flash-style recomputation on the fp32 matrix cores
  * (workspace: nm_attention_bwd_workspace_bytes(B,L,S,heads,flags)); flags & NM_ATTN_BF16X3: the same contractions on the
  * bf16 matrix cores with hi/lo operand splitting (attention_bwd_v2.hip; operands pre-split into the workspace);
- * head_dim 16 with L,S <= 64 (fine windows): one thread per row. */
+ * head_dim 16 with L,S <= 64 (fine windows): one thread per row.
+ * nlse (may be NULL): the array nm_attention wrote as nlse_out for the same q / k / scale (split-bf16 route only: NM_ERR_UNSUPPORTED
+ * with the fp32 kernels): the dQ kernel then makes ONE pass over the keys instead of two (7 instead of 8 tile products per key /
+ * query tile pair). */
 size_t nm_attention_bwd_workspace_bytes(int B, int L, int S, int heads, int flags);
-int nm_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* d_o, int ldq, int ldk,
-                     int ldv, int ldo, int lddo, int B, int L, int S, int heads, int head_dim, float scale, float* dq,
-                     float* dk, float* dv, int lddq, int lddk, int lddv, int flags, void* workspace, size_t workspace_bytes,
+int nm_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* d_o, int ldq, int ldk, int ldv,
+                     int ldo, int lddo, int B, int L, int S, int heads, int head_dim, float scale, float* dq, float* dk, float* dv,
+                     int lddq, int lddk, int lddv, int flags, const float* nlse, void* workspace, size_t workspace_bytes,
                      nmStream_t stream);
-/* Round 6: the forward pass keeps what the backward pass needs.  nm_attention_ws_lse = nm_attention_ws on the split-bf16 kernel (flags must
- * hold NM_ATTN_BF16X3, head_dim 32, not the <= 64-token window shapes: otherwise NM_ERR_UNSUPPORTED) that also writes nlse_out[B][heads][L] =
- * -(log-sum-exp of the query's scaled scores) in the log2 domain; nm_attention_bwd_lse = nm_attention_bwd given that array (NULL: as
- * nm_attention_bwd): the dQ kernel then makes ONE pass over the keys instead of two (7 instead of 8 tile products per key / query tile pair). */
-int nm_attention_ws_lse(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S, int heads,
-                        int head_dim, float scale, int flags, void* workspace, float* out, float* nlse_out, nmStream_t stream);
-int nm_attention_bwd_lse(const float* q, const float* k, const float* v, const float* o, const float* d_o, int ldq, int ldk, int ldv,
-                         int ldo, int lddo, int B, int L, int S, int heads, int head_dim, float scale, float* dq, float* dk, float* dv,
-                         int lddq, int lddk, int lddv, int flags, const float* nlse, void* workspace, size_t workspace_bytes,
-                         nmStream_t stream);
 
 /* Backward of nm_fine_windows (scatter-add of d out[K,win*win,C] into dffeat[C,Hf,Wf], which the caller zeroes or accumulates
  * onto; float atomics) and of nm_fine_expectation (d_expec[K,3] -> d_pt[K,C], d_win[K,win*win,C]); autograd through
@@ -623,7 +580,7 @@ int nm_fine_expectation_bwd(const float* pt_f, const float* win_f, const float* 
 
 /* Focal loss on the dual-softmax confidence (compute_matching_loss, nerfmatch/utils/metrics.py:372-380) and its gradient.
  * Protocol per training step:  zero acc[4] (double: sum_pos, sum_neg, n_pos, n_neg);  nm_focal_count over the WHOLE batch's
- * conf_gt (uint8 0/1, other values ignored);  then per batch element, right after nm_dual_softmax_match(_ex) on `workspace`
+ * conf_gt (uint8 0/1, other values ignored);  then per batch element, right after nm_dual_softmax_match on `workspace`
  * (which still holds the similarity matrix and the soft-max statistics):  nm_match_focal_loss adds the element's loss sums to
  * acc and writes row_t[M] / col_t[N];  loss = acc[0]/acc[2] + acc[1]/acc[3].  nm_match_focal_loss_bwd (same workspace
  * contents) writes ddot[M,N] = grad_loss * d loss / d (im_n . pt_n) and adds d loss / d scale to *dscale (double, may be

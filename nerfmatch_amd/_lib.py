@@ -14,6 +14,8 @@ import os
 
 LIB_PATH = Path(os.environ.get("NERFMATCH_AMD_LIB", PKG / "lib" / "libnerfmatch_amd.so"))  # env override: kernel A/B builds
 
+ABI_VERSION = 2  # NM_ABI_VERSION of include/nerfmatch_amd.h; lib() refuses a library that reports another one
+
 _lib = None
 
 vp, i32, f32, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -39,29 +41,23 @@ SIGNATURES = {
     "nm_raygen": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, vp]),
     "nm_raygen_batch": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]),
     "nm_sample_coarse": (i32, [vp, vp, i32, i32, vp, vp]),
-    "nm_resample": (i32, [vp, vp, vp, i32, i32, f32, i32, vp, vp]),
-    "nm_resample_ex": (i32, [vp, vp, vp, i32, i32, f32, i32, vp, vp, vp]),
-    "nm_resample_scaled": (i32, [vp, vp, vp, f32, i32, i32, f32, i32, vp, vp, vp]),
+    "nm_resample": (i32, [vp, vp, vp, f32, i32, i32, f32, i32, vp, vp, vp]),
     "nm_nerf_blob_floats": (sz, []),
     "nm_nerf_pack": (i32, [C.POINTER(NerfWeights), vp]),
     "nm_nerf_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "nm_nerf_blob_bytes_bf16x3": (sz, []),
     "nm_nerf_pack_bf16x3": (i32, [C.POINTER(NerfWeights), vp]),
     "nm_nerf_workspace_bytes_bf16x3": (sz, []),
-    "nm_nerf_fwd_bf16x3": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "nm_nerf_fwd_bf16x3_ex": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "nm_nerf_pack_fp16x3": (i32, [C.POINTER(NerfWeights), vp]),
-    "nm_nerf_fwd_fp16x3": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "nm_nerf_pack_fp16x3_scaled": (i32, [C.POINTER(NerfWeights), vp, vp]),
-    "nm_nerf_fwd_fp16x3_ex": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "nm_nerf_fwd_bf16x3": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "nm_nerf_pack_fp16x3": (i32, [C.POINTER(NerfWeights), vp, vp]),
+    "nm_nerf_fwd_fp16x3": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "nm_nerf_fwd_guarded": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "nm_nerf_blob_bytes_bwd_bf16x3": (sz, []),
     "nm_nerf_points_gate_bytes": (sz, [i32]),
     "nm_nerf_pack_bwd_bf16x3": (i32, [C.POINTER(NerfWeights), vp]),
     "nm_nerf_points_fwd_bf16x3": (i32, [vp, vp, vp, i32, vp, vp, vp]),
-    "nm_nerf_points_fwd_rays_bf16x3": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "nm_nerf_points_fwd_rays_bf16x3": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "nm_nerf_points_bwd_bf16x3": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
-    "nm_nerf_points_fwd_rays_tap_bf16x3": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "nm_nerf_points_bwd_tap_bf16x3": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "nm_nerf_blob_bytes_fp16x1": (sz, []),
     "nm_nerf_pack_fp16x1": (i32, [C.POINTER(NerfWeights), vp]),
@@ -73,26 +69,20 @@ SIGNATURES = {
     "nm_inerf_encode_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "nm_inerf_encode_bwd2": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "nm_inerf_pose_grad": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
-    "nm_inerf_composite": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp]),
-    "nm_inerf_composite_bwd": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
-    "nm_inerf_composite_ex": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
-    "nm_inerf_composite_bwd_ex": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "nm_inerf_composite": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "nm_inerf_composite_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "nm_inerf_ray_sums": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
     "nm_inerf_ray_sums_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
-    "nm_linear": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
-    "nm_linear_ex": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
-    "nm_linear_ex_bf16x3": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "nm_linear": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "nm_linear_blob_bytes_bf16x3": (sz, [i32, i32]),
     "nm_linear_qkv_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "nm_attention_presplit": (i32, [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp]),
     "nm_linear_pack_bf16x3": (i32, [vp, i32, i32, vp, vp]),
     "nm_linear_pack_t_bf16x3": (i32, [vp, i32, i32, vp, vp]),
-    "nm_linear_bf16x3": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "nm_linear_bf16x3": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "nm_layernorm": (i32, [vp, vp, vp, i32, i32, f32, vp, vp]),
     "nm_layernorm2": (i32, [vp, vp, vp, i32, f32, vp, vp, vp, vp, i32, f32, vp, i32, vp]),
-    "nm_attention": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp]),
-    "nm_attention_ld": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]),
-    "nm_attention_ex": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp]),
+    "nm_attention": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp]),
     "nm_linear_pack_perm_bf16x3": (i32, [vp, i32, i32, vp, vp]),
     "nm_encoder_tail_bf16x3": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp]),
     "nm_encoder_tail_bwd_bf16x3": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp]),
@@ -100,7 +90,6 @@ SIGNATURES = {
     "nm_attention_workspace_bytes": (sz, [i32, i32, i32]),
     "nm_attention_fp8_workspace_bytes": (sz, [i32, i32, i32]),
     "nm_attention_fp8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]),
-    "nm_attention_ws": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp]),
     "nm_add_sine_pe": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "nm_mip_encode": (i32, [vp, vp, sz, i32, i32, i32, i32, vp, vp, vp]),
     "nm_fourier_embed": (i32, [vp, sz, i32, i32, vp, vp]),
@@ -108,10 +97,9 @@ SIGNATURES = {
     "nm_cat_fourier": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "nm_cat_fourier_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "nm_match_workspace_bytes": (sz, [i32, i32, i32]),
-    "nm_dual_softmax_match": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "nm_dual_softmax_match": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "nm_match_fused_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "nm_dual_softmax_match_fused": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, f32, i32, vp, vp, vp, vp, vp, sz, vp]),
-    "nm_dual_softmax_match_ex": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "nm_fine_windows": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
     "nm_fine_windows_batch": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp]),
     "nm_assemble_matches": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp]),
@@ -125,8 +113,7 @@ SIGNATURES = {
     # training side (train.hip, attention_bwd.hip, match.hip)
     "nm_linear_wgrad_workspace_bytes": (sz, [i32, i32, i32]),
     "nm_linear_wgrad": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "nm_linear_wgrad_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "nm_linear_wgrad_bias_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "nm_linear_wgrad_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "nm_col_sum": (i32, [vp, i32, i32, i32, vp, vp]),
     "nm_gelu": (i32, [vp, sz, vp, vp]),
     "nm_gelu_bwd": (i32, [vp, vp, sz, vp, vp]),
@@ -134,9 +121,7 @@ SIGNATURES = {
     "nm_layernorm_bwd": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]),
     "nm_l2norm_bwd": (i32, [vp, vp, i32, i32, vp, vp]),
     "nm_attention_bwd_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
-    "nm_attention_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
-    "nm_attention_bwd_lse": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "nm_attention_ws_lse": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp]),
+    "nm_attention_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
     "nm_fine_windows_bwd": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
     "nm_fine_expectation_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "nm_focal_count": (i32, [vp, sz, vp, vp]),
@@ -168,6 +153,10 @@ def lib():
                 "nerfmatch_amd has no CPU / eager fallback."
             )
         h = C.CDLL(str(LIB_PATH))
+        h.nm_abi_version.restype, h.nm_abi_version.argtypes = SIGNATURES["nm_abi_version"]
+        if h.nm_abi_version() != ABI_VERSION:  # a stale build: its symbols may take other arguments than SIGNATURES lists
+            raise NerfmatchAmdError(f"{LIB_PATH} has ABI version {h.nm_abi_version()}, this package binds version {ABI_VERSION}: "
+                                    "rebuild it (python -m nerfmatch_amd.build --force)")
         missing = []
         for name, (res, args) in SIGNATURES.items():
             try:
@@ -271,7 +260,7 @@ PRECISIONS = ("fp32", "bf16x3", "fp16x3", "fp16x1", "bwd_bf16x3")
 def pack_nerf_weights(sd, prefix, precision="fp32", act_log2=None):
     """state-dict (reference key names) -> packed host blob for nm_nerf_fwd (1-D fp32 tensor) or, with
     precision="bf16x3", for nm_nerf_fwd_bf16x3 (1-D uint8 tensor).  act_log2 (fp16x3 only): the 12 input-scale exponents of
-    nm_nerf_pack_fp16x3_scaled (None = weights scaled, activations as they are)."""
+    nm_nerf_pack_fp16x3 (None = weights scaled, activations as they are)."""
     if precision not in PRECISIONS:
         raise NerfmatchAmdError(f"precision must be one of {PRECISIONS}")
     L = lib()
@@ -312,7 +301,7 @@ def pack_nerf_weights(sd, prefix, precision="fp32", act_log2=None):
     if precision == "fp16x3":  # same size and slot structure as the bf16x3 blob; int16 marks the kernel family
         blob = torch.empty(L.nm_nerf_blob_bytes_bf16x3() // 2, dtype=torch.int16)
         al = None if act_log2 is None else (C.c_int * 12)(*[int(v) for v in act_log2])
-        check(L.nm_nerf_pack_fp16x3_scaled(C.byref(w), al, C.c_void_p(blob.data_ptr())), "nm_nerf_pack_fp16x3_scaled")
+        check(L.nm_nerf_pack_fp16x3(C.byref(w), al, C.c_void_p(blob.data_ptr())), "nm_nerf_pack_fp16x3")
         return blob
     blob = torch.empty(L.nm_nerf_blob_floats(), dtype=torch.float32)
     check(L.nm_nerf_pack(C.byref(w), C.c_void_p(blob.data_ptr())), "nm_nerf_pack")

@@ -298,11 +298,11 @@ class _CoarseMatchLoss(Function):
             wss.append(ws)
             mi = None if im_m is None else im_m[b]
             mp = None if pt_m is None else pt_m[b]
-            check(L.nm_dual_softmax_match_ex(dptr(im_c[b]), dptr(pt_c[b]), M, N, Cc, scale, dptr(mi, torch.uint8), dptr(mp, torch.uint8),
-                                             float(threshold), int(bool(mutual)), flags, None if loss_only else dptr(conf[b]), dptr(imn[b]), dptr(ptn[b]),
-                                             None if loss_only else dptr(oi[b], torch.int64), None if loss_only else dptr(oj[b], torch.int64),
-                                             None if loss_only else dptr(oc[b]), C.c_void_p(cnt.data_ptr() + 4 * b), dptr(ws, torch.uint8), need, stream()),
-                  "nm_dual_softmax_match_ex")
+            check(L.nm_dual_softmax_match(dptr(im_c[b]), dptr(pt_c[b]), M, N, Cc, scale, dptr(mi, torch.uint8), dptr(mp, torch.uint8),
+                                          float(threshold), int(bool(mutual)), flags, None if loss_only else dptr(conf[b]), dptr(imn[b]), dptr(ptn[b]),
+                                          None if loss_only else dptr(oi[b], torch.int64), None if loss_only else dptr(oj[b], torch.int64),
+                                          None if loss_only else dptr(oc[b]), C.c_void_p(cnt.data_ptr() + 4 * b), dptr(ws, torch.uint8), need, stream()),
+                  "nm_dual_softmax_match")
             check(L.nm_match_focal_loss(dptr(gt[b], torch.uint8), M, N, Cc, float(alpha), float(gamma), int(bool(clamp)), dptr(ws, torch.uint8), need,
                                         dptr(acc, torch.float64), dptr(row_t[b]), dptr(col_t[b]), stream()), "nm_match_focal_loss")
         loss = (acc[0] / acc[2] + acc[1] / acc[3]).to(torch.float32)

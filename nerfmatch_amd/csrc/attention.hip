@@ -262,28 +262,6 @@ extern "C" int nm_layernorm2(const float* x0, const float* gamma0, const float* 
   return nm_launch_status();
 }
 
-extern "C" int nm_attention_ex(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S,
-                               int heads, int head_dim, float scale, int flags, float* out, nmStream_t stream) {
-  NM_CHECK_ARG(q && k && v && out && B > 0 && L > 0 && S > 0 && heads > 0);
-  const int C = heads * head_dim;
-  if (ldq < C || ldk < C || ldv < C || (ldq | ldk | ldv) % 4) return NM_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (S <= 64 && L <= 64 && (head_dim == 16 || head_dim == 32)) {
-    dim3 grid(heads, B);
-    if (head_dim == 16) attn_small_kernel<16><<<grid, 64, 0, s>>>(q, k, v, ldq, ldk, ldv, L, S, heads, scale, out);
-    else attn_small_kernel<32><<<grid, 64, 0, s>>>(q, k, v, ldq, ldk, ldv, L, S, heads, scale, out);
-    return nm_launch_status();
-  }
-  if (head_dim != 32) return NM_ERR_UNSUPPORTED;
-  if (B > 65535 || heads > 65535) return NM_ERR_UNSUPPORTED;
-  // the split-bf16 kernel streams pre-split operands from a workspace: nm_attention_ws (its first generation, which split
-  // while staging and needed none, is gone from the library: DESIGN.md section 3.4)
-  if (flags & NM_ATTN_BF16X3) return NM_ERR_WORKSPACE;
-  dim3 grid(((L + 31) / 32 + 3) / 4, heads, B);
-  attn32_kernel<<<grid, 256, 0, s>>>(q, k, v, ldq, ldk, ldv, L, S, heads, scale, out);
-  return nm_launch_status();
-}
-
 size_t nm_internal_attn_v2_workspace(int B, int S, int heads);
 int nm_internal_attn_v2(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S, int heads,
                         float scale, void* workspace, float* out, hipStream_t s, float* nlse_out);
@@ -293,39 +271,29 @@ extern "C" size_t nm_attention_workspace_bytes(int B, int S, int heads) {
   return nm_internal_attn_v2_workspace(B, S, heads);
 }
 
-extern "C" int nm_attention_ws(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S,
-                               int heads, int head_dim, float scale, int flags, void* workspace, float* out, nmStream_t stream) {
+extern "C" int nm_attention(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S,
+                            int heads, int head_dim, float scale, int flags, void* workspace, float* out, float* nlse_out,
+                            nmStream_t stream) {
   const bool small = S <= 64 && L <= 64 && (head_dim == 16 || head_dim == 32);
-  if (!(flags & NM_ATTN_BF16X3) || head_dim != 32 || small)
-    return nm_attention_ex(q, k, v, ldq, ldk, ldv, B, L, S, heads, head_dim, scale, flags & ~NM_ATTN_BF16X3, out, stream);
-  if (!workspace) return NM_ERR_WORKSPACE;
+  // the split-bf16 kernel streams pre-split operands from a workspace (its first generation, which split while staging and
+  // needed none, is gone from the library: DESIGN.md section 3.4); the flag is ignored on the other routes
+  const bool split = (flags & NM_ATTN_BF16X3) && head_dim == 32 && !small;
+  if (nlse_out && !split) return NM_ERR_UNSUPPORTED;  // only the split-bf16 kernel keeps the log-sum-exp
+  if (split && !workspace) return NM_ERR_WORKSPACE;
   NM_CHECK_ARG(q && k && v && out && B > 0 && L > 0 && S > 0 && heads > 0);
   const int C = heads * head_dim;
   if (ldq < C || ldk < C || ldv < C || (ldq | ldk | ldv) % 4) return NM_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (small) {
+    dim3 grid(heads, B);
+    if (head_dim == 16) attn_small_kernel<16><<<grid, 64, 0, s>>>(q, k, v, ldq, ldk, ldv, L, S, heads, scale, out);
+    else attn_small_kernel<32><<<grid, 64, 0, s>>>(q, k, v, ldq, ldk, ldv, L, S, heads, scale, out);
+    return nm_launch_status();
+  }
+  if (head_dim != 32) return NM_ERR_UNSUPPORTED;
   if (B > 65535 || heads > 65535) return NM_ERR_UNSUPPORTED;
-  return nm_internal_attn_v2(q, k, v, ldq, ldk, ldv, B, L, S, heads, scale, workspace, out, (hipStream_t)stream, nullptr);
-}
-
-extern "C" int nm_attention_ws_lse(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S,
-                                   int heads, int head_dim, float scale, int flags, void* workspace, float* out, float* nlse_out,
-                                   nmStream_t stream) {
-  const bool small = S <= 64 && L <= 64 && (head_dim == 16 || head_dim == 32);
-  if (!(flags & NM_ATTN_BF16X3) || head_dim != 32 || small) return NM_ERR_UNSUPPORTED;  // only the split-bf16 kernel keeps the log-sum-exp
-  if (!workspace) return NM_ERR_WORKSPACE;
-  NM_CHECK_ARG(q && k && v && out && nlse_out && B > 0 && L > 0 && S > 0 && heads > 0);
-  const int C = heads * head_dim;
-  if (ldq < C || ldk < C || ldv < C || (ldq | ldk | ldv) % 4) return NM_ERR_ARG;
-  if (B > 65535 || heads > 65535) return NM_ERR_UNSUPPORTED;
-  return nm_internal_attn_v2(q, k, v, ldq, ldk, ldv, B, L, S, heads, scale, workspace, out, (hipStream_t)stream, nlse_out);
-}
-
-extern "C" int nm_attention_ld(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S,
-                               int heads, int head_dim, float scale, float* out, nmStream_t stream) {
-  return nm_attention_ex(q, k, v, ldq, ldk, ldv, B, L, S, heads, head_dim, scale, 0, out, stream);
-}
-
-extern "C" int nm_attention(const float* q, const float* k, const float* v, int B, int L, int S, int heads, int head_dim,
-                            float scale, float* out, nmStream_t stream) {
-  const int C = heads * head_dim;
-  return nm_attention_ex(q, k, v, C, C, C, B, L, S, heads, head_dim, scale, 0, out, stream);
+  if (split) return nm_internal_attn_v2(q, k, v, ldq, ldk, ldv, B, L, S, heads, scale, workspace, out, s, nlse_out);
+  dim3 grid(((L + 31) / 32 + 3) / 4, heads, B);
+  attn32_kernel<<<grid, 256, 0, s>>>(q, k, v, ldq, ldk, ldv, L, S, heads, scale, out);
+  return nm_launch_status();
 }

@@ -330,23 +330,10 @@ extern "C" size_t nm_attention_bwd_workspace_bytes(int B, int L, int S, int head
   return (size_t)2 * B * heads * L * sizeof(float);
 }
 
-extern "C" int nm_attention_bwd_lse(const float* q, const float* k, const float* v, const float* o, const float* d_o, int ldq, int ldk,
-                                    int ldv, int ldo, int lddo, int B, int L, int S, int heads, int head_dim, float scale, float* dq,
-                                    float* dk, float* dv, int lddq, int lddk, int lddv, int flags, const float* nlse, void* workspace,
-                                    size_t workspace_bytes, nmStream_t stream);
-
 extern "C" int nm_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* d_o, int ldq, int ldk,
                                 int ldv, int ldo, int lddo, int B, int L, int S, int heads, int head_dim, float scale, float* dq,
-                                float* dk, float* dv, int lddq, int lddk, int lddv, int flags, void* workspace, size_t workspace_bytes,
-                                nmStream_t stream) {
-  return nm_attention_bwd_lse(q, k, v, o, d_o, ldq, ldk, ldv, ldo, lddo, B, L, S, heads, head_dim, scale, dq, dk, dv, lddq, lddk, lddv, flags,
-                              nullptr, workspace, workspace_bytes, stream);
-}
-
-extern "C" int nm_attention_bwd_lse(const float* q, const float* k, const float* v, const float* o, const float* d_o, int ldq, int ldk,
-                                    int ldv, int ldo, int lddo, int B, int L, int S, int heads, int head_dim, float scale, float* dq,
-                                    float* dk, float* dv, int lddq, int lddk, int lddv, int flags, const float* nlse, void* workspace,
-                                    size_t workspace_bytes, nmStream_t stream) {
+                                float* dk, float* dv, int lddq, int lddk, int lddv, int flags, const float* nlse, void* workspace,
+                                size_t workspace_bytes, nmStream_t stream) {
   NM_CHECK_ARG(q && k && v && o && d_o && dq && dk && dv && B > 0 && L > 0 && S > 0 && heads > 0);
   const int C = heads * head_dim;
   NM_CHECK_ARG(ldq >= C && ldk >= C && ldv >= C && ldo >= C && lddo >= C && lddq >= C && lddk >= C && lddv >= C);

@@ -195,7 +195,7 @@ __global__ void __launch_bounds__(256, 3) attn32_bwd_dq_v2_kernel(BwdArgs2 a) {
     }
   };
   // ---- pass 1: log-sum-exp of each query (log2 domain), lazy running maximum as in the forward kernel -- unless the forward pass
-  // kept it (HAVE_LSE, round 6: nm_attention_ws_lse), in which case the kernel is ONE pass over the keys: 3 products instead of 4
+  // kept it (HAVE_LSE, nm_attention's nlse_out), in which case the kernel is ONE pass over the keys: 3 products instead of 4
   float nlse;
   if constexpr (HAVE_LSE) {
     nlse = a.nlse[((size_t)b * a.H + h) * a.L + qc];

@@ -4,7 +4,7 @@
 #include <atomic>
 #include <mutex>
 
-extern "C" int nm_abi_version(void) { return 1; }
+extern "C" int nm_abi_version(void) { return NM_ABI_VERSION; }
 
 extern "C" const char* nm_error_string(int code) {
   switch (code) {

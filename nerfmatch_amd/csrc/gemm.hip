@@ -118,19 +118,14 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
 
 }  // namespace
 
-extern "C" int nm_linear_ex(const float* x, const float* w, const float* bias, const float* pre, const float* residual,
-                            const float* gate, int M, int N, int K, int act, float* y, nmStream_t stream) {
+extern "C" int nm_linear(const float* x, const float* w, const float* bias, const float* pre, const float* residual,
+                         const float* gate, int M, int N, int K, int act, float* y, nmStream_t stream) {
   NM_CHECK_ARG(x && w && y && M > 0 && N > 0 && K > 0);
   if (act < NM_ACT_NONE || act > NM_ACT_GELU) return NM_ERR_ARG;
   GemmArgs a{};
   a.x = x; a.w = w; a.bias = bias; a.res = residual; a.pre = pre; a.gate = gate; a.y = y;
   a.M = M; a.N = N; a.K = K; a.act = act;
   return launch_gemm<MODE_LINEAR>(a, (hipStream_t)stream);
-}
-
-extern "C" int nm_linear(const float* x, const float* w, const float* bias, const float* residual, int M, int N, int K,
-                         int act, float* y, nmStream_t stream) {
-  return nm_linear_ex(x, w, bias, nullptr, residual, nullptr, M, N, K, act, y, stream);
 }
 
 // internal (used by match.hip): sim[M,N] = mask_fill(scale * im[M,C] . pt[N,C]^T)

@@ -625,13 +625,8 @@ extern "C" int nm_linear_qkv_bf16x3(const float* x, const void* blob, int M, int
   return nm_launch_status();
 }
 
-extern "C" int nm_linear_bf16x3(const float* x, const void* blob, const float* bias, const float* residual, int M, int N, int K,
-                                int act, float* y, nmStream_t stream) {
-  return nm_linear_ex_bf16x3(x, blob, bias, nullptr, residual, nullptr, M, N, K, act, y, stream);
-}
-
-extern "C" int nm_linear_ex_bf16x3(const float* x, const void* blob, const float* bias, const float* pre, const float* residual,
-                                   const float* gate, int M, int N, int K, int act, float* y, nmStream_t stream) {
+extern "C" int nm_linear_bf16x3(const float* x, const void* blob, const float* bias, const float* pre, const float* residual,
+                                const float* gate, int M, int N, int K, int act, float* y, nmStream_t stream) {
   NM_CHECK_ARG(x && blob && y && M > 0 && N > 0 && K > 0);
   if (act < NM_ACT_NONE || act > NM_ACT_GELU) return NM_ERR_ARG;
   if (K % 8 != 0 || N % 8 != 0) return NM_ERR_UNSUPPORTED;  // 16-byte row pieces on both sides

@@ -545,16 +545,11 @@ extern "C" int nm_inerf_pose_grad(const float* Kinv_host, const float* pose_host
   return nm_launch_status();
 }
 
-extern "C" int nm_inerf_composite_ex(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays, int R, int S,
-                                     int S_act, float* rgb_map, float* weights, nmStream_t stream) {
+extern "C" int nm_inerf_composite(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays, int R, int S,
+                                  int S_act, float* rgb_map, float* weights, nmStream_t stream) {
   NM_CHECK_ARG(logit_rgb && sigma_raw && z && rays && rgb_map && R > 0 && S > 0 && S_act > 0 && S_act <= S && ld >= 3);
   inerf_composite_kernel<<<(R + 63) / 64, 64, 0, (hipStream_t)stream>>>(logit_rgb, sigma_raw, ld, z, rays, R, S, S_act, rgb_map, weights);
   return nm_launch_status();
-}
-
-extern "C" int nm_inerf_composite(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays, int R, int S,
-                                  int S_act, float* rgb_map, nmStream_t stream) {
-  return nm_inerf_composite_ex(logit_rgb, sigma_raw, ld, z, rays, R, S, S_act, rgb_map, nullptr, stream);
 }
 
 extern "C" int nm_inerf_composite4(const float* out4, const float* z, const float* rays, int R, int S, int S_act, float* rgb_map, float* weights,
@@ -572,20 +567,14 @@ extern "C" int nm_inerf_composite4_bwd(const float* out4, const float* z, const 
   return nm_launch_status();
 }
 
-extern "C" int nm_inerf_composite_bwd_ex(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays,
-                                         const float* g_rgb_map, const float* g_weights, int R, int S, int S_act, float* g_logit,
-                                         float* g_sigma, float* g_d, nmStream_t stream) {
+extern "C" int nm_inerf_composite_bwd(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays,
+                                      const float* g_rgb_map, const float* g_weights, int R, int S, int S_act, float* g_logit,
+                                      float* g_sigma, float* g_d, nmStream_t stream) {
   NM_CHECK_ARG(logit_rgb && sigma_raw && z && rays && g_rgb_map && g_logit && g_sigma && g_d && R > 0 && S > 0 && S_act > 0 && S_act <= S &&
                ld >= 3);
   inerf_composite_bwd_kernel<<<(R + 63) / 64, 64, 0, (hipStream_t)stream>>>(logit_rgb, sigma_raw, ld, z, rays, g_rgb_map, g_weights, R, S,
                                                                                S_act, g_logit, g_sigma, g_d);
   return nm_launch_status();
-}
-
-extern "C" int nm_inerf_composite_bwd(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays,
-                                      const float* g_rgb_map, int R, int S, int S_act, float* g_logit, float* g_sigma, float* g_d,
-                                      nmStream_t stream) {
-  return nm_inerf_composite_bwd_ex(logit_rgb, sigma_raw, ld, z, rays, g_rgb_map, nullptr, R, S, S_act, g_logit, g_sigma, g_d, stream);
 }
 
 extern "C" int nm_inerf_ray_sums(const float* weights, const float* feats, int C, const float* rays, const float* z, int R, int S, int S_act,

@@ -694,17 +694,9 @@ extern "C" size_t nm_match_workspace_bytes(int M, int N, int C) {
 }
 
 extern "C" int nm_dual_softmax_match(const float* im, const float* pt, int M, int N, int C, float scale, const uint8_t* im_mask,
-                                     const uint8_t* pt_mask, float threshold, int mutual, float* conf, float* im_norm,
+                                     const uint8_t* pt_mask, float threshold, int mutual, int flags, float* conf, float* im_norm,
                                      float* pt_norm, int64_t* out_i, int64_t* out_j, float* out_conf, int* count, void* workspace,
                                      size_t workspace_bytes, nmStream_t stream) {
-  return nm_dual_softmax_match_ex(im, pt, M, N, C, scale, im_mask, pt_mask, threshold, mutual, 0, conf, im_norm, pt_norm, out_i, out_j,
-                                  out_conf, count, workspace, workspace_bytes, stream);
-}
-
-extern "C" int nm_dual_softmax_match_ex(const float* im, const float* pt, int M, int N, int C, float scale, const uint8_t* im_mask,
-                                        const uint8_t* pt_mask, float threshold, int mutual, int flags, float* conf, float* im_norm,
-                                        float* pt_norm, int64_t* out_i, int64_t* out_j, float* out_conf, int* count, void* workspace,
-                                        size_t workspace_bytes, nmStream_t stream) {
   const bool stats_only = (flags & NM_MATCH_STATS_ONLY) != 0;
   NM_CHECK_ARG(im && pt && (stats_only || (out_i && out_j && out_conf && count)) && workspace && M > 0 && N > 0 && C > 0);
   if (C != 64 && C != 128 && C != 256 && C != 512) return NM_ERR_UNSUPPORTED;

@@ -22,7 +22,7 @@ constexpr int NSLOT_FULL = NSLOT_NORGB + (HS + VS);                  // + views 
 
 // small-parameter block (fp32), same layout as nerf_fwd.hip
 constexpr int OFF_BIAS = 0, OFF_BVIEWS = 2304, OFF_WALPHA = 2432, OFF_WRGB = 2688, OFF_MISC = 3072;
-// Round 4, fp16x3 only (the other modes carry ones): power-of-two operand scaling chosen at pack time (nm_nerf_pack_fp16x3_scaled).
+// Round 4, fp16x3 only (the other modes carry ones): power-of-two operand scaling chosen at pack time (nm_nerf_pack_fp16x3).
 //   OFF_SCALE   [16]  s_l, l = 0..8: the finished layer l is re-packed as fma(acc, s_l, bias'_l) -- s_l = 2^(c_{l+1} - A_l) takes the
 //                     accumulator from its scale A_l (weight scale + input scale) to the input scale c_{l+1} of the next layer,
 //                     bias'_l = bias_l * 2^c_{l+1} (stored in OFF_BIAS); exact: a power of two commutes with every rounding
@@ -63,7 +63,7 @@ struct NerfArgs {
   int Sa;    // samples per ray evaluated by the regular tiles (= S, or S/2 with NM_NERF_ZERO_TAIL)
   int left;  // 1: sample Sa of every ray is evaluated by "leftover" passes, samples > Sa have zero width (weight 0)
   int ntiles_full;       // tile count of the full evaluation (Sa = S)
-  const int* tail_viol;  // device flag raised by nm_resample_ex when the zero-width premise does NOT hold: evaluate everything
+  const int* tail_viol;  // device flag raised by nm_resample when the zero-width premise does NOT hold: evaluate everything
   float var_scale;
   int* status;  // fp16x3: device int32[16] or NULL -- [0] |= 1 when an operand reached the fp16 limit, [1 + k] = max bits of range slot k
 };

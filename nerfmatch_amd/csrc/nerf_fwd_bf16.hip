@@ -932,7 +932,7 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
   unsigned* const sm_rng = reinterpret_cast<unsigned*>(sm + LDS_RNG);  // [NRANGE][256] range telemetry (fp16x3)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = lane & 31, hi = lane >> 5;
-  // the zero-tail decision is taken HERE, from the flag nm_resample_ex left on the device (no promise by the caller)
+  // the zero-tail decision is taken HERE, from the flag nm_resample left on the device (no promise by the caller)
   const bool tail_ok = a.left && !(a.tail_viol && *a.tail_viol != 0);
   const int S = a.S, R = a.R;                // S: row length of t / weights
   const int Sa = tail_ok ? a.Sa : S;         // samples evaluated by the regular tiles
@@ -1998,7 +1998,7 @@ extern "C" size_t nm_nerf_workspace_bytes_bf16x3(void) { return (size_t)WS_WORKG
 //   weights of layer l, input group g (hidden columns | IPE columns | direction PE | appearance):  W * 2^a(l,g), chosen HERE
 //     from max|W| (-> [2^13, 2^14): constants cannot saturate);
 //   inputs of layer l:  x * 2^c_l -- c_0 (IPE, |x| <= 1) and the direction PE are static (2^12); the hidden activations' c_l come from
-//     the caller (act_log2: measured ranges, nm_nerf_fwd_fp16x3_ex status[]; NULL = 0, the unscaled activations of round 3);
+//     the caller (act_log2: measured ranges, nm_nerf_fwd_fp16x3 status[]; NULL = 0, the unscaled activations of round 3);
 //   accumulator of layer l:  2^A_l x the true pre-activation, A_l = a(l,g) + c(g) for every group g (the a's are tied by that);
 //   re-packing:  fma(acc, 2^(c_{l+1} - A_l), bias * 2^c_{l+1})  (OFF_SCALE, OFF_BIAS), density head vector * 2^-c_8, rgb head: bias
 //     * 2^A_9, vectors * 2^-A_9; tapped activations leave the kernel through OFF_DESCALE.
@@ -2170,18 +2170,9 @@ static int nerf_pack_split(const nmNerfWeights* w, void* blob_v, int fp16, const
 }
 
 extern "C" int nm_nerf_pack_bf16x3(const nmNerfWeights* w, void* blob_v) { return nerf_pack_split(w, blob_v, 0); }
-extern "C" int nm_nerf_pack_fp16x3(const nmNerfWeights* w, void* blob_v) { return nerf_pack_split(w, blob_v, 2); }
-extern "C" int nm_nerf_pack_fp16x3_scaled(const nmNerfWeights* w, const int* act_log2, void* blob_v) { return nerf_pack_split(w, blob_v, 2, act_log2); }
+extern "C" int nm_nerf_pack_fp16x3(const nmNerfWeights* w, const int* act_log2, void* blob_v) { return nerf_pack_split(w, blob_v, 2, act_log2); }
 extern "C" size_t nm_nerf_blob_bytes_fp16x1(void) { return BLOB_BYTES_FP16; }
 extern "C" int nm_nerf_pack_fp16x1(const nmNerfWeights* w, void* blob_v) { return nerf_pack_split(w, blob_v, 1); }
-
-extern "C" int nm_nerf_fwd_bf16x3(const void* blob, const float* rays, const float* t, const float* app_row, int R, int S,
-                                  int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
-                                  float* rgb, float* depth, float* acc, float* raw, float* sample_feat, void* workspace,
-                                  nmStream_t stream) {
-  return nm_nerf_fwd_bf16x3_ex(blob, rays, t, app_row, R, S, tap_layer, white_bg, var_scale, flags, weights, feat, pts, rgb, depth, acc, raw,
-                               sample_feat, workspace, nullptr, stream);
-}
 
 static int nerf_fwd_split(int mode, const void* blob, const float* rays, const float* t, const float* app_row, int R, int S, int tap_layer,
                           int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts, float* rgb, float* depth,
@@ -2217,10 +2208,10 @@ static int nerf_fwd_split(int mode, const void* blob, const float* rays, const f
   return nm_launch_status();
 }
 
-extern "C" int nm_nerf_fwd_bf16x3_ex(const void* blob, const float* rays, const float* t, const float* app_row, int R, int S,
-                                     int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
-                                     float* rgb, float* depth, float* acc, float* raw, float* sample_feat, void* workspace,
-                                     const int* zero_tail_violation, nmStream_t stream) {
+extern "C" int nm_nerf_fwd_bf16x3(const void* blob, const float* rays, const float* t, const float* app_row, int R, int S,
+                                  int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
+                                  float* rgb, float* depth, float* acc, float* raw, float* sample_feat, void* workspace,
+                                  const int* zero_tail_violation, nmStream_t stream) {
   return nerf_fwd_split(0, blob, rays, t, app_row, R, S, tap_layer, white_bg, var_scale, flags, weights, feat, pts, rgb, depth, acc, raw,
                         sample_feat, workspace, zero_tail_violation, stream);
 }
@@ -2236,15 +2227,7 @@ extern "C" int nm_nerf_fwd_fp16x1(const void* blob, const float* rays, const flo
 extern "C" int nm_nerf_fwd_fp16x3(const void* blob, const float* rays, const float* t, const float* app_row, int R, int S,
                                   int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
                                   float* rgb, float* depth, float* acc, float* raw, float* sample_feat, void* workspace,
-                                  const int* zero_tail_violation, nmStream_t stream) {
-  return nerf_fwd_split(2, blob, rays, t, app_row, R, S, tap_layer, white_bg, var_scale, flags, weights, feat, pts, rgb, depth, acc, raw,
-                        sample_feat, workspace, zero_tail_violation, stream);
-}
-
-extern "C" int nm_nerf_fwd_fp16x3_ex(const void* blob, const float* rays, const float* t, const float* app_row, int R, int S,
-                                     int tap_layer, int white_bg, float var_scale, int flags, float* weights, float* feat, float* pts,
-                                     float* rgb, float* depth, float* acc, float* raw, float* sample_feat, void* workspace,
-                                     const int* zero_tail_violation, int* status, nmStream_t stream) {
+                                  const int* zero_tail_violation, int* status, nmStream_t stream) {
   return nerf_fwd_split(2, blob, rays, t, app_row, R, S, tap_layer, white_bg, var_scale, flags, weights, feat, pts, rgb, depth, acc, raw,
                         sample_feat, workspace, zero_tail_violation, stream, status);
 }
@@ -2323,8 +2306,8 @@ extern "C" int nm_nerf_points_bwd_bf16x3_dbg(const void* blob_bwd, const float* 
   return nm_launch_status();
 }
 
-extern "C" int nm_nerf_points_fwd_rays_tap_bf16x3(const void* blob, const float* rays, const float* z, int R, int S, int S_act, const float* app_row,
-                                                  int tap_layer, float* out4, void* gates, float* feats, nmStream_t stream) {
+extern "C" int nm_nerf_points_fwd_rays_bf16x3(const void* blob, const float* rays, const float* z, int R, int S, int S_act, const float* app_row,
+                                              int tap_layer, float* out4, void* gates, float* feats, nmStream_t stream) {
   NM_CHECK_ARG(blob && rays && z && out4 && gates && R > 0 && S > 0 && S_act > 0 && S_act <= S);
   NM_CHECK_ARG(feats ? (tap_layer >= 0 && tap_layer <= 7) : tap_layer == -1);
   PointsArgs a = {};
@@ -2332,11 +2315,6 @@ extern "C" int nm_nerf_points_fwd_rays_tap_bf16x3(const void* blob, const float*
   a.n = R * S_act; a.ntiles = (a.n + TILE - 1) / TILE; a.tap = tap_layer; a.feats = feats;
   nerf_points_fwd_rays_kernel<<<points_grid(a.ntiles, stream), 256, 0, (hipStream_t)stream>>>(a);
   return nm_launch_status();
-}
-
-extern "C" int nm_nerf_points_fwd_rays_bf16x3(const void* blob, const float* rays, const float* z, int R, int S, int S_act, const float* app_row,
-                                              float* out4, void* gates, nmStream_t stream) {
-  return nm_nerf_points_fwd_rays_tap_bf16x3(blob, rays, z, R, S, S_act, app_row, -1, out4, gates, nullptr, stream);
 }
 
 extern "C" int nm_nerf_points_bwd_tap_bf16x3(const void* blob_bwd, const float* g4, const void* gates, int R, int S_act, int tap_layer,

@@ -232,7 +232,7 @@ __global__ void resample_kernel(const float* __restrict__ t_in, const float* __r
     const float base = (float)j * (float)(1.0 / (double)n);
     u = fminf((base + base) + jitter[(size_t)ray * n + j] * jscale, one_m_eps);  // (jscale 1: x * 1 is x)
     // NM_NERF_ZERO_TAIL premise: the fence posts j > S/2 all sit at u = 1 - eps (true for every jitter >= 0) and therefore
-    // coincide.  A caller-supplied jitter that breaks it raises the flag; nm_nerf_fwd_bf16x3_ex then evaluates every sample.
+    // coincide.  A caller-supplied jitter that breaks it raises the flag; nm_nerf_fwd_bf16x3 then evaluates every sample.
     if (tail_flag && j >= S / 2 + 1 && u != one_m_eps) atomicOr(tail_flag, 1);
   } else {
     // torch.linspace(0, 1-eps, n)
@@ -392,18 +392,8 @@ extern "C" int nm_sample_coarse(const float* rays, const float* t_rand, int R, i
   return nm_launch_status();
 }
 
-extern "C" int nm_resample(const float* t_in, const float* weights, const float* jitter, int R, int S, float padding,
-                           int randomized, float* t_out, nmStream_t stream) {
-  return nm_resample_ex(t_in, weights, jitter, R, S, padding, randomized, t_out, nullptr, stream);
-}
-
-extern "C" int nm_resample_ex(const float* t_in, const float* weights, const float* jitter, int R, int S, float padding,
-                              int randomized, float* t_out, int* zero_tail_violation, nmStream_t stream) {
-  return nm_resample_scaled(t_in, weights, jitter, 1.0f, R, S, padding, randomized, t_out, zero_tail_violation, stream);
-}
-
-extern "C" int nm_resample_scaled(const float* t_in, const float* weights, const float* jitter, float jitter_scale, int R, int S, float padding,
-                                  int randomized, float* t_out, int* zero_tail_violation, nmStream_t stream) {
+extern "C" int nm_resample(const float* t_in, const float* weights, const float* jitter, float jitter_scale, int R, int S, float padding,
+                           int randomized, float* t_out, int* zero_tail_violation, nmStream_t stream) {
   NM_CHECK_ARG(t_in && weights && t_out && R > 0 && S > 1 && (jitter || !randomized));
   const float jscale = jitter_scale;
   int* const tf = randomized ? zero_tail_violation : nullptr;

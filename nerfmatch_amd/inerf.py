@@ -9,11 +9,11 @@ backward:
   fine pass         nm_inerf_encode -> nm_linear(_bf16x3) x 12 -> nm_inerf_composite, and the mirrored backward
                     nm_inerf_composite_bwd -> nm_linear(_bf16x3) with transposed weights -> nm_inerf_encode_bwd
   optimiser         torch.optim.Adam on the 4x4 pose (as the reference)
-  matching term     (`use_match_loss`, :420-441) nm_inerf_composite_ex (weights) -> nm_inerf_ray_sums (pt_feat, points) ->
+  matching term     (`use_match_loss`, :420-441) nm_inerf_composite (weights) -> nm_inerf_ray_sums (pt_feat, points) ->
                     matcher.match_loss (the training kernels of the matcher under torch.autograd.Function, parameters frozen:
                     only d loss / d pt_feat and d loss / d pt3d are computed) -> nm_inerf_ray_sums_bwd -> the gradients of
                     the weights and of the tapped layer's activations join the photometric backward
-                    (nm_inerf_composite_bwd_ex, FineField.backward(g_h=...)).  Under the split arithmetic the fine pass is the
+                    (nm_inerf_composite_bwd's g_weights, FineField.backward(g_h=...)).  Under the split arithmetic the fine pass is the
                     fused kernel pair here too (round 5): the forward kernel writes the tapped activations, the backward kernel
                     forms w_n . d loss / d pt_feat[ray] itself and adds it at the tapped layer (nm_nerf_points_*_tap_bf16x3)
 Only the first S/2 + 1 fine samples of a ray are evaluated: the randomized resampler leaves the later intervals with zero
@@ -38,7 +38,7 @@ def _new(*shape, dev):
 
 class FineField:
     """nerf_fine as padded GEMM operands: forward weights and their transposes (for the backward GEMMs), cached per
-    renderer.  Layers with a concatenated input are split into two GEMMs joined through the `pre` addend of nm_linear_ex:
+    renderer.  Layers with a concatenated input are split into two GEMMs joined through the `pre` addend of nm_linear:
     layer 5 = relu(xi . W5x^T + h4 . W5h^T + b), views = relu(feature . Wvf^T + xd . Wvd^T + b); xi has 96 columns
     (90 IPE + padding), xd 48 (27 dir PE + 16 appearance + padding); the density / rgb heads are padded to 8 outputs.
     The ReLU derivatives of the backward pass are the `gate` of the same epilogue (no elementwise passes)."""
@@ -128,8 +128,8 @@ class FusedField:
         out4 = _new(n, 4, dev=dev)
         gates = torch.empty(lib().nm_nerf_points_gate_bytes(n), dtype=torch.uint8, device=dev)
         feats = _new(n, 256, dev=dev) if tap >= 0 else None
-        check(lib().nm_nerf_points_fwd_rays_tap_bf16x3(dptr(self.blob, torch.uint8), dptr(rays), dptr(z), R, S, int(S_act), dptr(app_row), int(tap),
-                                                       dptr(out4), dptr(gates, torch.uint8), dptr(feats), stream()), "nm_nerf_points_fwd_rays_tap_bf16x3")
+        check(lib().nm_nerf_points_fwd_rays_bf16x3(dptr(self.blob, torch.uint8), dptr(rays), dptr(z), R, S, int(S_act), dptr(app_row), int(tap),
+                                                   dptr(out4), dptr(gates, torch.uint8), dptr(feats), stream()), "nm_nerf_points_fwd_rays_bf16x3")
         return (out4, gates, feats) if tap >= 0 else (out4, gates)
 
     def backward(self, g4, gates, tap=None):
@@ -186,8 +186,8 @@ def _composite(logit, sig, z, rays, S_act, want_weights=False):
     R, S = z.shape[0], z.shape[1] - 1
     rgb = _new(R, 3, dev=rays.device)
     w = _new(R, S_act, dev=rays.device) if want_weights else None
-    check(lib().nm_inerf_composite_ex(dptr(logit), dptr(sig), logit.shape[1], dptr(z), dptr(rays), R, S, S_act, dptr(rgb), dptr(w), stream()),
-          "nm_inerf_composite_ex")
+    check(lib().nm_inerf_composite(dptr(logit), dptr(sig), logit.shape[1], dptr(z), dptr(rays), R, S, S_act, dptr(rgb), dptr(w), stream()),
+          "nm_inerf_composite")
     return (rgb, w) if want_weights else rgb
 
 
@@ -195,8 +195,8 @@ def _composite_bwd(logit, sig, z, rays, S_act, G, g_w=None):
     R, S = z.shape[0], z.shape[1] - 1
     g_logit, g_sig, g_d = torch.empty_like(logit), torch.empty_like(sig), _new(R, 3, dev=rays.device)
     G = G.contiguous()
-    check(lib().nm_inerf_composite_bwd_ex(dptr(logit), dptr(sig), logit.shape[1], dptr(z), dptr(rays), dptr(G), dptr(g_w), R, S,
-                                          S_act, dptr(g_logit), dptr(g_sig), dptr(g_d), stream()), "nm_inerf_composite_bwd_ex")
+    check(lib().nm_inerf_composite_bwd(dptr(logit), dptr(sig), logit.shape[1], dptr(z), dptr(rays), dptr(G), dptr(g_w), R, S,
+                                       S_act, dptr(g_logit), dptr(g_sig), dptr(g_d), stream()), "nm_inerf_composite_bwd")
     return g_logit, g_sig, g_d
 
 

@@ -74,7 +74,7 @@ class MultiHeadAttention(nn.Module):
         """project_out=False returns the attention output BEFORE proj_out (the fused encoder tail applies it).
         q/k/v projections are ONE GEMM when the inputs coincide (self attention: [q|k|v], cross attention: [k|v]); on the
         split-bf16 path that GEMM writes the keys / values directly as the attention kernel's pre-split MFMA operands
-        (ops.attention_projected), otherwise the attention kernel reads the column slices in place (nm_attention_ld)."""
+        (ops.attention_projected), otherwise the attention kernel reads the column slices in place (nm_attention's row strides)."""
         if ag.is_training():
             return self._forward_train(query, key, value, residual, project_out)
         scale = self.attend.scale() if self.att_type == "full" else self.attend.scale_value()

@@ -219,7 +219,7 @@ class NeRF(nn.Module):
         outputs (..., 4) = [sigmoid rgb, raw sigma] and, with ret_pfeat > 0, the features of layer `stop_layer` (last layer
         when negative).  The render path never comes through here (it uses the fused kernel); callers that reach into the
         network directly (the reference's iNeRF loop, nerfmatch_evaluator.py:402-406) get the same numbers from a chain of
-        the HIP GEMM kernels (nm_linear_ex; the skip and view inputs enter as `pre` addends instead of concatenations)."""
+        the HIP GEMM kernels (nm_linear; the skip and view inputs enter as `pre` addends instead of concatenations)."""
         from ...inerf import XD, XI, FineField  # GEMM-chain packing of one MLP (shared with the iNeRF refinement)
 
         lead = x.shape[:-1]

@@ -47,6 +47,16 @@ def side_stream(dev):
     return _SIDE_STREAMS[key]
 
 
+def _scratch(cache, dev, need):
+    """The (growing) uint8 scratch buffer of one kernel family, one per (device, stream): calls on one stream are serialised, calls on
+    different streams must not share it.  `cache`: that family's own dict (buffers are not shared between kernels)."""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = cache[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    return ws
+
+
 # ----------------------------------------------------------------------------- parameter fingerprints
 class ParamGuard:
     """Notices parameters whose VALUES changed behind the derived copies this package keeps of them (packed / split / transposed blobs,
@@ -171,7 +181,7 @@ def sample_coarse(rays, t_rand, S):
 
 
 def resample(t, weights, jitter, padding=0.01, randomized=True, want_tail_flag=False, jitter_scale=1.0):
-    """want_tail_flag: also return the device int32[1] flag nm_resample_ex raises when the fence posts j > S/2 do NOT
+    """want_tail_flag: also return the device int32[1] flag nm_resample raises when the fence posts j > S/2 do NOT
     coincide (the premise of nerf_fwd(zero_tail=True)); pass it on as `tail_flag`.  jitter_scale: the kernel uses jitter * jitter_scale
     (one fp32 product where it reads the value: the same bits as scaling the tensor first, one launch less)."""
     R, n = t.shape
@@ -179,13 +189,13 @@ def resample(t, weights, jitter, padding=0.01, randomized=True, want_tail_flag=F
     assert weights.shape == (R, S)
     out = torch.empty_like(t)
     flag = torch.empty(1, device=t.device, dtype=torch.int32) if want_tail_flag else None
-    check(lib().nm_resample_scaled(dptr(t), dptr(weights), dptr(jitter), float(jitter_scale), R, S, float(padding), int(bool(randomized)), dptr(out),
-                                   dptr(flag, torch.int32), stream()), "nm_resample_scaled")
+    check(lib().nm_resample(dptr(t), dptr(weights), dptr(jitter), float(jitter_scale), R, S, float(padding), int(bool(randomized)), dptr(out),
+                            dptr(flag, torch.int32), stream()), "nm_resample")
     return (out, flag) if want_tail_flag else out
 
 
 class Fp16Guard:
-    """Safety net of one fp16x3 blob (round 4): the device status block nm_nerf_fwd_fp16x3_ex writes (saturation flag + range
+    """Safety net of one fp16x3 blob (round 4): the device status block nm_nerf_fwd_fp16x3 writes (saturation flag + range
     telemetry, int32[16]) and the fp32 blob of the same parameters for the device-side fall-back nm_nerf_fwd_guarded.  NeRF.packed
     attaches one to every fp16x3 blob (`blob.nm_guard`); nerf_fwd refuses an fp16x3 blob without one.
     ONE STREAM PER STATUS BLOCK: the guarded pass consumes the flag (completion counter status[12], event count status[11]); two guarded
@@ -242,25 +252,22 @@ def nerf_fwd(blob, rays, t, app_row=None, tap_layer=-1, white_bg=False, var_scal
     common = (dptr(rays), dptr(t), dptr(app_row), R, S, int(tap_layer), int(bool(white_bg)),
               float(var_scale), flags, dptr(out["weights"]), dptr(out["feat"]), dptr(out["pts"]),
               dptr(out["rgb"]), dptr(out["depth"]), dptr(out["acc"]), dptr(out["raw"]), dptr(out["sample_feat"]))
-    if blob.dtype == torch.uint8:
-        ws = _nerf_workspace(dev) if (need_feat or want_sample_feat) else None
-        check(lib().nm_nerf_fwd_bf16x3_ex(dptr(blob, torch.uint8), *common, dptr(ws, torch.uint8), dptr(tail_flag, torch.int32), stream()),
-              "nm_nerf_fwd_bf16x3_ex")
-    elif blob.dtype == torch.int16:  # fp16 hi/lo-split blob (NeRF.packed(device, "fp16x3"))
-        g = guard if guard is not None else getattr(blob, "nm_guard", None)
-        if g is None:
-            raise _lib.NerfmatchAmdError("fp16x3 blob without an Fp16Guard: take it from NeRF.packed(device, 'fp16x3') (operands beyond "
-                                         "+-65504 would be clamped silently)")
-        ws = _nerf_workspace(dev) if (need_feat or want_sample_feat) else None
-        check(lib().nm_nerf_fwd_fp16x3_ex(dptr(blob, torch.int16), *common, dptr(ws, torch.uint8), dptr(tail_flag, torch.int32),
-                                          dptr(g.status, torch.int32), stream()), "nm_nerf_fwd_fp16x3_ex")
-        check(lib().nm_nerf_fwd_guarded(dptr(g.blob32), *common, dptr(g.status, torch.int32), stream()), "nm_nerf_fwd_guarded")
-    elif blob.dtype == torch.float16:  # single-product fp16 blob (NeRF.packed(device, "fp16x1"))
-        ws = _nerf_workspace(dev) if (need_feat or want_sample_feat) else None
-        check(lib().nm_nerf_fwd_fp16x1(dptr(blob, torch.float16), *common, dptr(ws, torch.uint8), dptr(tail_flag, torch.int32), stream()),
-              "nm_nerf_fwd_fp16x1")
-    else:
+    split = _NERF_SPLIT.get(blob.dtype)
+    if split is None:
         check(lib().nm_nerf_fwd(dptr(blob), *common, stream()), "nm_nerf_fwd")
+    else:
+        name, guarded = split
+        status = ()
+        if guarded:
+            g = guard if guard is not None else getattr(blob, "nm_guard", None)
+            if g is None:
+                raise _lib.NerfmatchAmdError("fp16x3 blob without an Fp16Guard: take it from NeRF.packed(device, 'fp16x3') (operands beyond "
+                                             "+-65504 would be clamped silently)")
+            status = (dptr(g.status, torch.int32),)
+        ws = _nerf_workspace(dev) if (need_feat or want_sample_feat) else None
+        check(getattr(lib(), name)(dptr(blob, blob.dtype), *common, dptr(ws, torch.uint8), dptr(tail_flag, torch.int32), *status, stream()), name)
+        if guarded:
+            check(lib().nm_nerf_fwd_guarded(dptr(g.blob32), *common, *status, stream()), "nm_nerf_fwd_guarded")
     if S != S_req:
         for k in ("weights", "raw", "sample_feat"):
             if out[k] is not None:
@@ -268,16 +275,16 @@ def nerf_fwd(blob, rays, t, app_row=None, tap_layer=-1, white_bg=False, var_scal
     return out
 
 
+# split-precision kernel families by blob dtype: (entry point, takes the Fp16Guard's `status` block and runs guarded)
+_NERF_SPLIT = {torch.uint8: ("nm_nerf_fwd_bf16x3", False),    # NeRF.packed(device, "bf16x3")
+               torch.int16: ("nm_nerf_fwd_fp16x3", True),     # fp16 hi/lo-split blob (NeRF.packed(device, "fp16x3"))
+               torch.float16: ("nm_nerf_fwd_fp16x1", False)}  # single-product fp16 blob (NeRF.packed(device, "fp16x1"))
 _NERF_WS = {}
 
 
 def _nerf_workspace(dev):
-    """Scratch of the persistent bf16x3 kernel, one per (device, stream): calls on one stream are serialised."""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _NERF_WS.get(key)
-    if ws is None:
-        ws = _NERF_WS[key] = torch.empty(lib().nm_nerf_workspace_bytes_bf16x3(), dtype=torch.uint8, device=dev)
-    return ws
+    """Scratch of the persistent split-precision kernels."""
+    return _scratch(_NERF_WS, dev, lib().nm_nerf_workspace_bytes_bf16x3())
 
 
 def unnormalize_points(pts, unnorm):
@@ -308,57 +315,46 @@ def _linear_evict():
     _LINEAR_BLOBS.clear()
 
 
-def _linear_blob(weight):
-    """Split / re-ordered copy of a weight matrix for nm_linear_bf16x3, cached until the tensor changes."""
+def _linear_cached(prefix, weight, make):
+    """make(w) for the detached weight, cached under prefix + (data_ptr, _version, shape, device) until the tensor changes."""
     w = weight.detach()
-    key = (w.data_ptr(), w._version, tuple(w.shape), w.device.index)
+    key = (*prefix, w.data_ptr(), w._version, tuple(w.shape), w.device.index)
     hit = _LINEAR_BLOBS.get(key)
     if hit is None:
-        N, K = w.shape
-        blob = torch.empty(lib().nm_linear_blob_bytes_bf16x3(N, K), dtype=torch.uint8, device=w.device)
-        wc = w.contiguous()
-        check(lib().nm_linear_pack_bf16x3(dptr(wc), N, K, dptr(blob, torch.uint8), stream()), "nm_linear_pack_bf16x3")
+        made = make(w)
         if len(_LINEAR_BLOBS) >= _LINEAR_LIMIT:
             _linear_evict()
-        hit = _LINEAR_BLOBS[key] = (blob, w)  # keeps the source tensor alive so that its data_ptr is not reused
+        hit = _LINEAR_BLOBS[key] = (made, w)  # keeps the source tensor alive so that its data_ptr is not reused
     _LINEAR_RECENT.append(hit)
     return hit[0]
+
+
+def _pack(name, N, K):
+    """make-callable of _linear_cached: the nm_linear_blob_bytes_bf16x3(N, K) blob that entry point `name` writes from the weight."""
+    def make(w):
+        blob = torch.empty(lib().nm_linear_blob_bytes_bf16x3(N, K), dtype=torch.uint8, device=w.device)
+        wc = w.contiguous()
+        check(getattr(lib(), name)(dptr(wc), N, K, dptr(blob, torch.uint8), stream()), name)
+        return blob
+    return make
+
+
+def _linear_blob(weight):
+    """Split / re-ordered copy of a weight matrix for nm_linear_bf16x3, cached until the tensor changes."""
+    return _linear_cached((), weight, _pack("nm_linear_pack_bf16x3", *weight.shape))
 
 
 def _linear_blob_perm(weight):
     """The same blob with the K dimension in accumulator order (nm_linear_pack_perm_bf16x3): the weights of a product whose
     input is the previous product's output still sitting in accumulator registers (nm_encoder_tail_bf16x3)."""
-    w = weight.detach()
-    key = ("perm", w.data_ptr(), w._version, tuple(w.shape), w.device.index)
-    hit = _LINEAR_BLOBS.get(key)
-    if hit is None:
-        N, K = w.shape
-        blob = torch.empty(lib().nm_linear_blob_bytes_bf16x3(N, K), dtype=torch.uint8, device=w.device)
-        wc = w.contiguous()
-        check(lib().nm_linear_pack_perm_bf16x3(dptr(wc), N, K, dptr(blob, torch.uint8), stream()), "nm_linear_pack_perm_bf16x3")
-        if len(_LINEAR_BLOBS) >= _LINEAR_LIMIT:
-            _linear_evict()
-        hit = _LINEAR_BLOBS[key] = (blob, w)
-    _LINEAR_RECENT.append(hit)
-    return hit[0]
+    return _linear_cached(("perm",), weight, _pack("nm_linear_pack_perm_bf16x3", *weight.shape))
 
 
 def _linear_blob_t(weight):
     """The packed blob of weight.T made straight from the stored (N_out, K_in) tensor (nm_linear_pack_t_bf16x3): a training step, whose
     parameter versions change every step, then needs neither the transposed copy nor a second trip through the cache for it."""
-    w = weight.detach()
-    key = ("packT", w.data_ptr(), w._version, tuple(w.shape), w.device.index)
-    hit = _LINEAR_BLOBS.get(key)
-    if hit is None:
-        K, N = w.shape  # stored (out = K of the product, in = N of the product): the packed matrix is (N, K)
-        blob = torch.empty(lib().nm_linear_blob_bytes_bf16x3(N, K), dtype=torch.uint8, device=w.device)
-        wc = w.contiguous()
-        check(lib().nm_linear_pack_t_bf16x3(dptr(wc), N, K, dptr(blob, torch.uint8), stream()), "nm_linear_pack_t_bf16x3")
-        if len(_LINEAR_BLOBS) >= _LINEAR_LIMIT:
-            _linear_evict()
-        hit = _LINEAR_BLOBS[key] = (blob, w)
-    _LINEAR_RECENT.append(hit)
-    return hit[0]
+    K, N = weight.shape  # stored (out = K of the product, in = N of the product): the packed matrix is (N, K)
+    return _linear_cached(("packT",), weight, _pack("nm_linear_pack_t_bf16x3", N, K))
 
 
 def linear_t(dy, weight):
@@ -369,8 +365,8 @@ def linear_t(dy, weight):
         d2 = dy.reshape(-1, No).contiguous()
         y = torch.empty(d2.shape[0], Ki, device=dy.device, dtype=torch.float32)
         if d2.shape[0]:
-            check(lib().nm_linear_ex_bf16x3(dptr(d2), dptr(_linear_blob_t(weight), torch.uint8), None, None, None, None, d2.shape[0], Ki, No,
-                                            _lib.NM_ACT_NONE, dptr(y), stream()), "nm_linear_ex_bf16x3")
+            check(lib().nm_linear_bf16x3(dptr(d2), dptr(_linear_blob_t(weight), torch.uint8), None, None, None, None, d2.shape[0], Ki, No,
+                                         _lib.NM_ACT_NONE, dptr(y), stream()), "nm_linear_bf16x3")
         return y.reshape(*dy.shape[:-1], Ki)
     return linear(dy, transposed(weight))
 
@@ -380,15 +376,7 @@ def transposed(weight):
     layer's backward pass, dy @ W, is nm_linear with W^T as the weight.  A fresh `.t().contiguous()` per call is a copy kernel AND a
     miss of the blob cache (a new tensor every time: one pack per layer and call); with frozen parameters -- the matching term of the
     iNeRF refinement differentiates through the matcher five times per query -- both happen once."""
-    w = weight.detach()
-    key = ("T", w.data_ptr(), w._version, tuple(w.shape), w.device.index)
-    hit = _LINEAR_BLOBS.get(key)
-    if hit is None:
-        if len(_LINEAR_BLOBS) >= _LINEAR_LIMIT:
-            _linear_evict()
-        hit = _LINEAR_BLOBS[key] = (w.t().contiguous(), w)
-    _LINEAR_RECENT.append(hit)
-    return hit[0]
+    return _linear_cached(("T",), weight, lambda w: w.t().contiguous())
 
 
 ENCODER_TAIL_FUSED = True  # False: the four separate launches (A/B runs, tests)
@@ -455,11 +443,11 @@ def linear(x, weight, bias=None, residual=None, act=_lib.NM_ACT_NONE, pre=None, 
     p2 = None if pre is None else pre.reshape(-1, N).contiguous()
     g2 = None if gate is None else gate.reshape(-1, N).contiguous()
     if LINEAR_PRECISION == "bf16x3" and K % 8 == 0 and N % 8 == 0:
-        check(lib().nm_linear_ex_bf16x3(dptr(x2), dptr(_linear_blob(weight), torch.uint8), dptr(bias), dptr(p2), dptr(r2), dptr(g2), M, N, K,
-                                        int(act), dptr(y), stream()), "nm_linear_ex_bf16x3")
+        check(lib().nm_linear_bf16x3(dptr(x2), dptr(_linear_blob(weight), torch.uint8), dptr(bias), dptr(p2), dptr(r2), dptr(g2), M, N, K,
+                                     int(act), dptr(y), stream()), "nm_linear_bf16x3")
     elif LINEAR_PRECISION in ("fp32", "bf16x3"):
-        check(lib().nm_linear_ex(dptr(x2), dptr(weight), dptr(bias), dptr(p2), dptr(r2), dptr(g2), M, N, K, int(act), dptr(y), stream()),
-              "nm_linear_ex")
+        check(lib().nm_linear(dptr(x2), dptr(weight), dptr(bias), dptr(p2), dptr(r2), dptr(g2), M, N, K, int(act), dptr(y), stream()),
+              "nm_linear")
     else:
         raise _lib.NerfmatchAmdError(f"LINEAR_PRECISION must be 'fp32' or 'bf16x3', got {LINEAR_PRECISION!r}")
     return y.reshape(*x.shape[:-1], N)
@@ -504,11 +492,7 @@ _ATTN_FP8_WS = {}
 
 
 def _attention_fp8(qp, kp, vp_, ldq, ldk, ldv, B, L, S, heads, scale, out, dev):
-    need = lib().nm_attention_fp8_workspace_bytes(int(B), int(S), int(heads))
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _ATTN_FP8_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _ATTN_FP8_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _scratch(_ATTN_FP8_WS, dev, lib().nm_attention_fp8_workspace_bytes(int(B), int(S), int(heads)))
     check(lib().nm_attention_fp8(qp, kp, vp_, ldq, ldk, ldv, int(B), int(L), int(S), int(heads), float(scale), dptr(ws, torch.uint8), dptr(out),
                                  stream()), "nm_attention_fp8")
 
@@ -528,8 +512,8 @@ def attention(q, k, v, heads, scale):
     elif B * L:
         flags = _attn_flags()
         with _probe("nm_attention_ws", 4.0 * B * L * S * Cc):
-            check(lib().nm_attention_ws(dptr(q), dptr(k), dptr(v), Cc, Cc, Cc, B, L, S, int(heads), Cc // heads, float(scale), flags,
-                                        _attn_workspace(q.device, B, S, heads, flags, L, Cc // heads), dptr(out), stream()), "nm_attention_ws")
+            check(lib().nm_attention(dptr(q), dptr(k), dptr(v), Cc, Cc, Cc, B, L, S, int(heads), Cc // heads, float(scale), flags,
+                                     _attn_workspace(q.device, B, S, heads, flags, L, Cc // heads), dptr(out), None, stream()), "nm_attention")
     return out
 
 
@@ -538,21 +522,16 @@ _ATTN_WS = {}
 
 def _attn_workspace(dev, B, S, heads, flags, L=None, head_dim=32):
     """Scratch for the pre-split K / V operands of the bf16x3 kernel, one (growing) buffer per (device, stream).  NULL for the
-    shapes nm_attention_ws does not route to that kernel (head dim != 32, or the <= 64-token windows of the fine stage: with
+    shapes nm_attention does not route to that kernel (head dim != 32, or the <= 64-token windows of the fine stage: with
     thousands of windows the request would be ~1 GB and re-grow -- a device allocation, milliseconds -- whenever a batch had
     more matches than any before)."""
     if not (flags & _lib.NM_ATTN_BF16X3) or head_dim != 32 or (L is not None and L <= 64 and S <= 64):
         return C.c_void_p(0)
-    need = lib().nm_attention_workspace_bytes(int(B), int(S), int(heads))
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _ATTN_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _ATTN_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return dptr(ws, torch.uint8)
+    return dptr(_scratch(_ATTN_WS, dev, lib().nm_attention_workspace_bytes(int(B), int(S), int(heads))), torch.uint8)
 
 
 def lse_supported(L, S, head_dim):
-    """True when the attention forward can keep the log-sum-exp for the backward pass (nm_attention_ws_lse: the split-bf16 kernel)."""
+    """True when the attention forward can keep the log-sum-exp for the backward pass (nm_attention's nlse_out: the split-bf16 kernel)."""
     return ATTENTION_PRECISION == "bf16x3" and head_dim == 32 and not (L <= 64 and S <= 64)
 
 
@@ -574,16 +553,11 @@ def attention_fused(qkv, q_cols, k_cols, v_cols, B, L, S, heads, scale, kv=None,
         _attention_fp8(qp, kp, vp_, ldq, ldkv, ldkv, B, L, S, heads, scale, out, qkv.device)
         return (out.reshape(B, L, dim), None) if want_lse else out.reshape(B, L, dim)
     flags = _attn_flags()
-    if want_lse and lse_supported(L, S, dim // heads):
-        nlse = torch.empty(B, heads, L, device=qkv.device, dtype=torch.float32)
-        check(lib().nm_attention_ws_lse(qp, kp, vp_, ldq, ldkv, ldkv, B, L, S, int(heads), dim // heads, float(scale), flags,
-                                        _attn_workspace(qkv.device, B, S, heads, flags, L, dim // heads), dptr(out), dptr(nlse), stream()),
-              "nm_attention_ws_lse")
-        return out.reshape(B, L, dim), nlse
+    nlse = torch.empty(B, heads, L, device=qkv.device, dtype=torch.float32) if want_lse and lse_supported(L, S, dim // heads) else None
     with _probe("nm_attention_ws", 4.0 * B * L * S * dim):
-        check(lib().nm_attention_ws(qp, kp, vp_, ldq, ldkv, ldkv, B, L, S, int(heads), dim // heads, float(scale), flags,
-                                    _attn_workspace(qkv.device, B, S, heads, flags, L, dim // heads), dptr(out), stream()), "nm_attention_ws")
-    return (out.reshape(B, L, dim), None) if want_lse else out.reshape(B, L, dim)
+        check(lib().nm_attention(qp, kp, vp_, ldq, ldkv, ldkv, B, L, S, int(heads), dim // heads, float(scale), flags,
+                                 _attn_workspace(qkv.device, B, S, heads, flags, L, dim // heads), dptr(out), dptr(nlse), stream()), "nm_attention")
+    return (out.reshape(B, L, dim), nlse) if want_lse else out.reshape(B, L, dim)
 
 
 def projected_attention_supported(K, heads, head_dim, L, S):
@@ -662,11 +636,7 @@ _ws_cache = {}
 def _match_workspace(dev, need):
     """Scratch of the matching kernels (similarity matrix + statistics), one growing buffer per (device, stream): calls on one
     stream are serialised, calls on different streams must not share it."""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _ws_cache[key] = torch.empty(need, device=dev, dtype=torch.uint8)
-    return ws
+    return _scratch(_ws_cache, dev, need)
 
 
 def invalidate_caches():
@@ -702,10 +672,10 @@ def dual_softmax_match(im, pt, scale, im_mask=None, pt_mask=None, threshold=0.0,
     if MATCH_PRECISION not in ("fp32", "bf16x3"):
         raise _lib.NerfmatchAmdError(f"MATCH_PRECISION must be 'fp32' or 'bf16x3', got {MATCH_PRECISION!r}")
     flags = _lib.NM_MATCH_BF16X3 if MATCH_PRECISION == "bf16x3" else 0
-    check(L.nm_dual_softmax_match_ex(dptr(im), dptr(pt), M, N, Cc, float(scale), dptr(im_m, torch.uint8), dptr(pt_m, torch.uint8),
-                                     float(threshold), int(bool(mutual)), flags, dptr(conf), dptr(imn), dptr(ptn), dptr(oi, torch.int64),
-                                     dptr(oj, torch.int64), dptr(oc), dptr(cnt, torch.int32), dptr(ws, torch.uint8), C.c_size_t(need),
-                                     stream()), "nm_dual_softmax_match_ex")
+    check(L.nm_dual_softmax_match(dptr(im), dptr(pt), M, N, Cc, float(scale), dptr(im_m, torch.uint8), dptr(pt_m, torch.uint8),
+                                  float(threshold), int(bool(mutual)), flags, dptr(conf), dptr(imn), dptr(ptn), dptr(oi, torch.int64),
+                                  dptr(oj, torch.int64), dptr(oc), dptr(cnt, torch.int32), dptr(ws, torch.uint8), C.c_size_t(need),
+                                  stream()), "nm_dual_softmax_match")
     if defer_count:  # the caller reads `count` back later (one synchronisation for a whole batch) and slices itself
         return dict(i_ids=oi, j_ids=oj, mconf=oc, conf=conf, im_norm=imn, pt_norm=ptn, count=cnt)
     k = int(cnt.item())
@@ -722,10 +692,7 @@ def _dual_softmax_match_fused(im, pt, scale, im_mask, pt_mask, threshold, mutual
     dev = im.device
     L = lib()
     need = L.nm_match_fused_workspace_bytes(B, M, N, Cc)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _fused_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _fused_ws[key] = torch.empty(need, device=dev, dtype=torch.uint8)
+    ws = _scratch(_fused_ws, dev, need)
     # (one allocation for the three lists; the compaction kernel writes every slot: matches first, zeros behind the count -- the
     # single-pair path's speculative fine stage reads the first `cap` slots as indices before the count is known)
     buf = torch.empty(B * M * 20, device=dev, dtype=torch.uint8)
@@ -776,10 +743,10 @@ def dual_softmax_match_batch(im, pt, scale, im_mask=None, pt_mask=None, threshol
     off = lambda t, b, stride: C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr() + b * stride)
     st, wsp = stream(), dptr(ws, torch.uint8)
     for b in range(B):
-        check(L.nm_dual_softmax_match_ex(off(im, b, M * Cc * 4), off(pt, b, N * Cc * 4), M, N, Cc, float(scale), off(im_m, b, M), off(pt_m, b, N),
-                                         float(threshold), int(bool(mutual)), flags, off(conf, b, M * N * 4), off(imn, b, M * Cc * 4),
-                                         off(ptn, b, N * Cc * 4), off(oi, b, M * 8), off(oj, b, M * 8), off(oc, b, M * 4), off(cnt, b, 4),
-                                         wsp, C.c_size_t(need), st), "nm_dual_softmax_match_ex")
+        check(L.nm_dual_softmax_match(off(im, b, M * Cc * 4), off(pt, b, N * Cc * 4), M, N, Cc, float(scale), off(im_m, b, M), off(pt_m, b, N),
+                                      float(threshold), int(bool(mutual)), flags, off(conf, b, M * N * 4), off(imn, b, M * Cc * 4),
+                                      off(ptn, b, N * Cc * 4), off(oi, b, M * 8), off(oj, b, M * 8), off(oc, b, M * 4), off(cnt, b, 4),
+                                      wsp, C.c_size_t(need), st), "nm_dual_softmax_match")
     return dict(i_ids=oi, j_ids=oj, mconf=oc, count=cnt, conf=conf, im_norm=imn, pt_norm=ptn)
 
 
@@ -934,14 +901,6 @@ def fine_expectation(pt_f, win_f, count, win=5):
 _WGRAD_WS = {}
 
 
-def _scratch(cache, dev, need):
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = cache.get(key)
-    if ws is None or ws.numel() < need:
-        ws = cache[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    return ws
-
-
 def _aligned16(t):
     """t, or a copy of it when its first element does not sit on a 16-byte boundary (a contiguous view at an odd offset into its storage)."""
     return t if t.data_ptr() % 16 == 0 else t.clone()
@@ -958,7 +917,7 @@ def linear_wgrad(dy, x, out=None):
     need = lib().nm_linear_wgrad_workspace_bytes(M, N, K)
     ws = _scratch(_WGRAD_WS, dy.device, need)
     if LINEAR_PRECISION == "bf16x3" and N % 2 == 0 and K % 4 == 0:  # (the arithmetic of the dX GEMMs of the same backward pass; round 6: 3 x faster than the fp32-MFMA kernel)
-        check(lib().nm_linear_wgrad_bf16x3(dptr(dy), dptr(x), M, N, K, int(out is not None), dptr(dw), dptr(ws, torch.uint8), ws.numel(), stream()),
+        check(lib().nm_linear_wgrad_bf16x3(dptr(dy), dptr(x), M, N, K, int(out is not None), dptr(dw), None, dptr(ws, torch.uint8), ws.numel(), stream()),
               "nm_linear_wgrad_bf16x3")
         return dw
     if N % 4 or K % 4:
@@ -978,8 +937,8 @@ def linear_wgrad_bias(dy, x):
     dw = torch.empty(N, K, device=dy.device, dtype=torch.float32)
     db = torch.empty(N, device=dy.device, dtype=torch.float32)
     ws = _scratch(_WGRAD_WS, dy.device, lib().nm_linear_wgrad_workspace_bytes(M, N, K))
-    check(lib().nm_linear_wgrad_bias_bf16x3(dptr(dy), dptr(x), M, N, K, 0, dptr(dw), dptr(db), dptr(ws, torch.uint8), ws.numel(), stream()),
-          "nm_linear_wgrad_bias_bf16x3")
+    check(lib().nm_linear_wgrad_bf16x3(dptr(dy), dptr(x), M, N, K, 0, dptr(dw), dptr(db), dptr(ws, torch.uint8), ws.numel(), stream()),
+          "nm_linear_wgrad_bf16x3")
     return dw, db
 
 
@@ -1062,10 +1021,10 @@ def attention_bwd_fused(q_src, q_col, kv_src, k_col, v_col, o, d_o, B, L, S, hea
     off = lambda t, c: C.c_void_p(t.data_ptr() + 4 * c)
     if nlse is not None and not (flags & _lib.NM_ATTN_BF16X3):
         nlse = None  # (the precision switch moved between forward and backward: the fp32 kernels rebuild the log-sum-exp themselves)
-    check(lib().nm_attention_bwd_lse(off(q_src, q_col), off(kv_src, k_col), off(kv_src, v_col), dptr(o2), dptr(d2), ldq, ldkv, ldkv, dim, dim,
-                                     B, L, S, int(heads), dim // heads, float(scale), off(dq_src, q_col), off(dkv_src, k_col),
-                                     off(dkv_src, v_col), ldq, ldkv, ldkv, flags, dptr(nlse), dptr(ws, torch.uint8), ws.numel(), stream()),
-          "nm_attention_bwd_lse")
+    check(lib().nm_attention_bwd(off(q_src, q_col), off(kv_src, k_col), off(kv_src, v_col), dptr(o2), dptr(d2), ldq, ldkv, ldkv, dim, dim,
+                                 B, L, S, int(heads), dim // heads, float(scale), off(dq_src, q_col), off(dkv_src, k_col),
+                                 off(dkv_src, v_col), ldq, ldkv, ldkv, flags, dptr(nlse), dptr(ws, torch.uint8), ws.numel(), stream()),
+          "nm_attention_bwd")
     return dq_src, dkv_src
 
 
@@ -1081,7 +1040,7 @@ def attention_bwd(q, k, v, o, d_o, heads, scale):
     need = lib().nm_attention_bwd_workspace_bytes(B, L, S, int(heads), flags)
     ws = _scratch(_ATTN_BWD_WS, q.device, need)
     check(lib().nm_attention_bwd(dptr(q), dptr(k), dptr(v), dptr(o), dptr(d_o), Cc, Cc, Cc, Cc, Cc, B, L, S, int(heads), Cc // heads,
-                                 float(scale), dptr(dq), dptr(dk), dptr(dv), Cc, Cc, Cc, flags, dptr(ws, torch.uint8), ws.numel(), stream()),
+                                 float(scale), dptr(dq), dptr(dk), dptr(dv), Cc, Cc, Cc, flags, None, dptr(ws, torch.uint8), ws.numel(), stream()),
           "nm_attention_bwd")
     return dq, dk, dv
 

@@ -1,4 +1,4 @@
-"""Per-shape time of nm_linear_ex_bf16x3 at the matcher's sizes against its two rooflines (HBM bytes, issued bf16 MFMA work)."""
+"""Per-shape time of nm_linear_bf16x3 at the matcher's sizes against its two rooflines (HBM bytes, issued bf16 MFMA work)."""
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))

@@ -1,4 +1,4 @@
-"""Workload for scripts/pmc_collect.sh (PMC_SCRIPT=pmc_gemm.py): one nm_linear_ex_bf16x3 shape, 8 launches.
+"""Workload for scripts/pmc_collect.sh (PMC_SCRIPT=pmc_gemm.py): one nm_linear_bf16x3 shape, 8 launches.
 GEMM_SHAPE="M,K,N,res" (default 153600,256,256,1)."""
 import os, sys
 from pathlib import Path

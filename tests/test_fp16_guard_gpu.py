@@ -1,5 +1,5 @@
 """Round 4: the fp16x3 kernel's safety net (VERDICT r3 item 1b / ADVICE r3 renderer.py:84).  An operand that reaches +-65504 is
-clamped by the kernel (v_med3) -- and REPORTED: status[0] of nm_nerf_fwd_fp16x3_ex goes up, the guarded fp32 launch behind it
+clamped by the kernel (v_med3) -- and REPORTED: status[0] of nm_nerf_fwd_fp16x3 goes up, the guarded fp32 launch behind it
 (nm_nerf_fwd_guarded, decision on the device) rewrites every output, and the managed path (NeRF.fused) re-calibrates the operand
 scales.  Never a silently clamped result."""
 import warnings

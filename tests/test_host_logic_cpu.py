@@ -53,11 +53,11 @@ def test_timing_proxy_times_launching_entry_points_only():
             return lambda *a: 0
 
     proxy = latency.TimedLib(Fake())
-    raw = proxy.nm_nerf_pack_fp16x3_scaled          # host-side packing: never wrapped
+    raw = proxy.nm_nerf_pack_fp16x3                 # host-side packing: never wrapped
     assert raw.__name__ == "<lambda>" and raw() == 0
     assert proxy.nm_abi_version.__name__ == "<lambda>"  # no stream argument
     assert proxy.nm_match_workspace_bytes.__name__ == "<lambda>"  # size query
-    assert proxy.nm_layernorm.__name__ == "timed" and proxy.nm_nerf_fwd_fp16x3_ex.__name__ == "timed"
+    assert proxy.nm_layernorm.__name__ == "timed" and proxy.nm_nerf_fwd_fp16x3.__name__ == "timed"
     assert set(_lib.SIGNATURES) >= {"nm_mip_encode", "nm_fourier_embed"}
 
 

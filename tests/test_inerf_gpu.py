@@ -106,7 +106,7 @@ def _match_setup(gpu):
 
 
 def test_ray_sums_and_weight_gradient_kernels(gpu, built_lib):
-    """nm_inerf_composite_ex / _bwd_ex (weights and their extra gradient) and nm_inerf_ray_sums / _bwd against torch autograd
+    """nm_inerf_composite / _bwd (with weights and their extra gradient) and nm_inerf_ray_sums / _bwd against torch autograd
     over the oracle's compositing and frustum means."""
     from oracle import nerf_oracle as no
 
@@ -273,7 +273,7 @@ def _points_case(gpu, app, R, Sa, seed):
 
 @pytest.mark.parametrize("app,R,Sa,tap", [(False, 61, 65, 3), (True, 37, 65, 7), (False, 19, 128, 0), (False, 300, 65, 5)])
 def test_tapped_points_kernels_vs_gemm_chain(gpu, built_lib, app, R, Sa, tap):
-    """nm_nerf_points_fwd_rays_tap_bf16x3 / nm_nerf_points_bwd_tap_bf16x3 (round 5: the matching term on the fused pair) against the fp32
+    """nm_nerf_points_fwd_rays_bf16x3 with a tap / nm_nerf_points_bwd_tap_bf16x3 (round 5: the matching term on the fused pair) against the fp32
     GEMM chain (FineField, which the oracle / reference tests above pin): tapped activations, outputs, and d loss / d (xi, xd) with a
     gradient entering at the tapped layer as w_n . g_pt_feat[ray] -- including a ragged last tile (R Sa is no multiple of 128)."""
     ren, rays, z, app_row, g = _points_case(gpu, app, R, Sa, seed=21 + tap)
@@ -434,7 +434,7 @@ def test_encode_backward_vs_fp64_sums(gpu, built_lib, R, S, Sa, two):
 @pytest.mark.parametrize("R,S,Sa,with_gw", [(50, 64, 33, False), (37, 128, 65, True), (9, 256, 129, True), (4801, 128, 128, False)])
 def test_wavefront_compositing_vs_per_ray_loops(gpu, built_lib, R, S, Sa, with_gw):
     """nm_inerf_composite4 / _bwd (round 6: one wavefront per ray, prefix product and suffix sum over lanes, the fused field's (n, 4) rows as they
-    lie) against the sequential one-thread-per-ray kernels (nm_inerf_composite_ex / _bwd_ex, themselves pinned by the step-gradient tests against
+    lie) against the sequential one-thread-per-ray kernels (nm_inerf_composite / _bwd, themselves pinned by the step-gradient tests against
     the oracle's autograd): same expression, different association of the products and sums."""
     g = torch.Generator().manual_seed(R + Sa)
     n = R * Sa

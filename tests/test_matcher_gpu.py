@@ -573,7 +573,7 @@ def test_multi_pair_vs_reference(gpu, built_lib, precision):
 # ----------------------------------------------------------------------------- bf16x3 attention
 @pytest.fixture
 def attn_bf16x3():
-    """Both matcher contractions on the split-bf16 path: attention (nm_attention_ex) and nn.Linear (nm_linear_bf16x3)."""
+    """Both matcher contractions on the split-bf16 path: attention (nm_attention with NM_ATTN_BF16X3) and nn.Linear (nm_linear_bf16x3)."""
     ops.ATTENTION_PRECISION = "bf16x3"
     ops.LINEAR_PRECISION = "bf16x3"
     ops.MATCH_PRECISION = "bf16x3"

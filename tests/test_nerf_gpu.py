@@ -55,7 +55,7 @@ def make_renderer(fx, gpu, S=None):
 
 
 def test_library_loaded(gpu, built_lib):
-    assert _lib.lib().nm_abi_version() == 1
+    assert _lib.lib().nm_abi_version() == _lib.ABI_VERSION
 
 
 def test_mfma_probe_runs(gpu, built_lib):
@@ -583,7 +583,7 @@ def test_per_pixel_raygen_equals_the_per_ray_form(gpu, built_lib, H, W, ds):
 
 @pytest.mark.parametrize("S", [64, 128, 20])
 def test_resampler_scales_the_jitter_like_an_elementwise_product(gpu, built_lib, S):
-    """nm_resample_scaled (round 5): jitter * scale inside the kernel = the tensor scaled by torch first, bit for bit (the renderer's own
+    """nm_resample's jitter_scale (round 5): jitter * scale inside the kernel = the tensor scaled by torch first, bit for bit (the renderer's own
     draw goes in unscaled: one launch less in front of the coarse pass)."""
     g = torch.Generator().manual_seed(S)
     R = 333

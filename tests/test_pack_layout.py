@@ -34,7 +34,7 @@ def test_packed_chain_matches_oracle(built_lib, case, net):
 @pytest.mark.parametrize("act", [None, [12, 8, 7, 7, 7, 6, 6, 6, 5, 7, 12, 3], [10, -3, 0, 2, 9, -6, 1, 4, 0, 11, 14, -2]])
 @pytest.mark.parametrize("case,net,style", [("r128_s64_app", "nerf_fine", None), ("surf_w1_p21", "nerf_coarse", "surface")])
 def test_fp16x3_scaled_pack_bookkeeping(built_lib, case, net, style, act):
-    """Round 4: nm_nerf_pack_fp16x3_scaled's power-of-two scales cancel exactly.  The fp16x3 blob (weights x 2^a per input group,
+    """Round 4: nm_nerf_pack_fp16x3's power-of-two scales cancel exactly.  The fp16x3 blob (weights x 2^a per input group,
     biases / head vectors / re-packing multipliers / tap descale in the small block) is read back and the kernel's scaled layer chain is
     replayed in float64: density, tapped features and colours must equal the oracle MLP for ANY activation exponents -- including
     ones no calibration would choose -- up to the 22-bit representation of the weights."""
