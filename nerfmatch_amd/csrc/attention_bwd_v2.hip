@@ -10,28 +10,15 @@
 // row (i&3) + 16 ks + 8 (i>>2) + 4 half, cf. attention_v2.hip).  The soft-max shift and the D term enter as the C operand
 // of the first MFMA (-lse, -D), so the scores come out ready for exp2 and dP - D needs no subtraction.
 // The dq kernel first rebuilds the log-sum-exp of its queries (scores only, lazy running maximum) and publishes -lse, -D.
-#include "common.h"
+#include "bf16x3.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 constexpr int KSLOT_BYTES = 12288, KSLOT_FLOATS = KSLOT_BYTES / 4;  // 12 operand pieces of 1 KiB
 constexpr int QSLOT_BYTES = 17408, QSLOT_FLOATS = QSLOT_BYTES / 4;  // 16 operand pieces + 1 KiB of per-query scalars
 constexpr int RING = 3;
 constexpr float LOG2E = 1.44269504088896340736f;
 constexpr float RAISE = 8.0f;
-
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)v[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(v[i] - (float)h);
-  }
-}
 
 // grid (tiles, H, B), block 256.  Piece p of a slot (64 lanes x 16 bytes): group g = p / 4 in {x rows, y rows, x^T, y^T},
 // k-step ks = (p / 2) & 1, hi / lo = p & 1.  groups: 3 (key tiles: x = K, y = V) or 4 (query tiles: x = Q, y = dO, plus the

@@ -18,7 +18,6 @@
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int F8_SLOT_BYTES = 4096;
 constexpr int F8_SLOT_FLOATS = F8_SLOT_BYTES / 4;
 constexpr int F8_RING = 4;

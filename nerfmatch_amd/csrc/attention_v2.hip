@@ -11,27 +11,14 @@
 //   * "lazy" running maximum: the scores come out of the MFMA already shifted (C operand = -m), m is only raised when a
 //     score exceeds it by more than 2^8 (wave-uniform branch), so the common tile costs max + exp2 + sum + split only.
 // Arithmetic and accuracy are those of the first generation (w_hi*x_hi + w_hi*x_lo + w_lo*x_hi, fp32 accumulate).
-#include "common.h"
+#include "bf16x3.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-constexpr int AT_SLOT_BYTES = 8192;
+constexpr int AT_SLOT_BYTES = NM_SLOT8K_BYTES;
 constexpr int AT_SLOT_FLOATS = AT_SLOT_BYTES / 4;
 constexpr int AT_RING = 4;
 constexpr float AT_RAISE = 8.0f;  // log2 units: probabilities stay below 2^8 between two raises of the running maximum
-
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)v[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(v[i] - (float)h);
-  }
-}
 
 // grid (tiles, H, B), block 256: thread = (which in {K, V}, k-step, lane) -> one hi and one lo operand of 16 bytes
 __global__ void __launch_bounds__(256) kv_presplit_kernel(const float* __restrict__ k, const float* __restrict__ v, int ldk, int ldv,
@@ -67,16 +54,6 @@ __global__ void __launch_bounds__(256) kv_presplit_kernel(const float* __restric
   slot[(op + 1) * 64 + lane] = __builtin_bit_cast(u32x4, lo8);
 }
 
-// two 1 KiB pieces per wavefront: one address / one M0, told apart by the immediate offset
-__device__ __forceinline__ void dma_tile(const char* slots, int t, float* ring, int wave, int lane) {
-  const unsigned voff = (unsigned)(wave * 2048 + lane * 16);
-  const char* base = slots + (size_t)t * AT_SLOT_BYTES;
-  const auto* src = (const __attribute__((address_space(1))) void*)(base + voff);
-  auto* dst = (__attribute__((address_space(3))) void*)(ring + (t & (AT_RING - 1)) * AT_SLOT_FLOATS + wave * 512);
-  __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
-  __builtin_amdgcn_global_load_lds(src, dst, 16, 1024, 0);
-}
-
 // 1-D grid of ceil(B*H / 8) * 8 * ceil(L/128) workgroups, block 256 = 4 wavefronts x 32 queries.
 // XCD-aware work mapping: consecutive workgroup ids go round robin to the 8 XCDs (each with its own 4 MiB L2), so
 // id -> (xcd = id % 8, query block = (id / 8) % nqb, (batch, head) = 8 * (id / (8 nqb)) + xcd): all query blocks of one
@@ -109,9 +86,9 @@ __global__ void __launch_bounds__(256, 4) attn32_v3_kernel(const float* __restri
   const int qc = qrow < L ? qrow : L - 1;
   const int nt = (S + 31) / 32;
   const char* slots = blob + ((size_t)b * H + h) * nt * AT_SLOT_BYTES;
-  dma_tile(slots, 0, ring, wave, lane);
-  if (nt > 1) dma_tile(slots, 1, ring, wave, lane);
-  if (nt > 2) dma_tile(slots, 2, ring, wave, lane);
+  dma_slot_8k<AT_RING>(slots, 0, ring, wave, lane);
+  if (nt > 1) dma_slot_8k<AT_RING>(slots, 1, ring, wave, lane);
+  if (nt > 2) dma_slot_8k<AT_RING>(slots, 2, ring, wave, lane);
   bf16x8 qh[2], ql[2];
   {
     const float qs = scale * 1.44269504088896340736f;
@@ -151,7 +128,7 @@ __global__ void __launch_bounds__(256, 4) attn32_v3_kernel(const float* __restri
     if (t + 2 < nt) NM_WAIT_VMCNT(2);
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // everybody's pieces of tile t+1 landed; nobody reads tile t-1 any more
-    if (t + 3 < nt) dma_tile(slots, t + 3, ring, wave, lane);
+    if (t + 3 < nt) dma_slot_8k<AT_RING>(slots, t + 3, ring, wave, lane);
     if (t == nt - 1 && (S & 31)) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)

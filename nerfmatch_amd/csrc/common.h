@@ -39,6 +39,7 @@ extern "C" int nm_stream_cus(nmStream_t stream);
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // The build uses -ffp-contract=off: every fused multiply-add below is written explicitly so that the
 // plain mul/add sequences of the reference's elementwise torch ops are reproduced op for op.
@@ -89,6 +90,13 @@ __device__ __forceinline__ void nm_sincosf(float x, float& sn, float& cs) {
 __device__ __forceinline__ float nm_cosf(float x) { return nm_sincos_sel(x, 1); }
 
 __device__ __forceinline__ float nm_shfl_xor32(float v) { return __shfl_xor(v, 32, 64); }
+
+// sum over the 64 lanes of a wavefront (xor butterfly: every lane ends up with the total)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // Exchange between the two 32-lane halves of a wavefront without the LDS round trip of ds_bpermute (gfx950:
 // v_permlane32_swap_b32 swaps the upper half of its first operand with the lower half of its second).  After the call

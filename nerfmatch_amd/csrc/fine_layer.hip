@@ -11,21 +11,16 @@
 //   * arithmetic = the split-bf16 products of gemm_bf16.hip (w_hi x_hi + w_hi x_lo + w_lo x_hi, fp32 accumulate); a product's 128 outputs
 //     sit in 4 accumulator blocks (lane = row, register r of block ob <-> feature 32 ob + (r & 3) + 8 (r >> 2) + 4 half) and 8 consecutive
 //     registers are one K-step operand of the NEXT product when its weights are packed in that K order (nm_linear_pack_perm_bf16x3, as in
-//     encoder_tail.hip): LayerNorm, GELU, bias, residual and the hi / lo re-packing are lane local (two xor-32 reductions per LayerNorm);
+//     encoder_tail.hip; repack, bf16x3.h): LayerNorm, GELU, bias, residual and the hi / lo re-packing are lane local (two xor-32 reductions per LayerNorm);
 //     the window is gathered straight into that layout, so all six weight matrices use the permuted pack;
 //   * a product's 64 KiB of pre-split weights are copied to LDS once per workgroup (four matches read them from there);
 //   * attention: per head a lane (token t, half) owns 8 of the 16 dims.  Round 6: scores and weighted sums are two small products on the
 //     matrix cores (S^T = K . Q^T straight from the registers, O^T = V^T . P^T with V^T read from a 4 KiB LDS scratch), soft-max lane local
 //     plus one xor-32 exchange, the result again in the accumulator layout (round 5 did both on the VALU with keys / values as broadcast LDS
 //     reads: scripts/variants/fine_layer_attention_valu_r6.patch).
-#include "common.h"
+#include "bf16x3.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 constexpr int FL_T = 25, FL_D = 128, FL_NKS = 8, FL_SLOT_FLOATS = 2048, FL_BLOB_FLOATS = FL_NKS * FL_SLOT_FLOATS;  // 64 KiB per matrix
 
@@ -44,9 +39,6 @@ struct FLArgs {
   const float *pw0t, *pb0, *pw1t, *pb1;                   // transposed weights [pt_c0][128], [128][128]; biases may be NULL
 };
 
-__host__ __device__ __forceinline__ constexpr int nrow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) { return __builtin_bit_cast(unsigned, bf16x2{(__bf16)a, (__bf16)b}); }
-
 // x = h + m + l with three bf16 terms (24 bits: exact for fp32 inputs up to the last term's rounding)
 __device__ __forceinline__ void split3(const float (&x)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
 #pragma unroll
@@ -58,38 +50,6 @@ __device__ __forceinline__ void split3(const float (&x)[8], bf16x8& h, bf16x8& m
     m[i] = b;
     l[i] = (__bf16)(r1 - (float)b);
   }
-}
-
-// x = h + m with two bf16 terms (16 bits: the split of every 128-wide product of this kernel)
-__device__ __forceinline__ void split2(const float (&x)[8], bf16x8& h, bf16x8& m) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 a = (__bf16)x[i];
-    h[i] = a;
-    m[i] = (__bf16)(x[i] - (float)a);
-  }
-}
-
-struct Unit {
-  u32x4 h, l;
-};
-// values v[ob][r] (accumulator layout) -> the 8 K-step operands of the next product: unit 2 ob + m = registers 8 m .. 8 m + 7 of block ob
-__device__ __forceinline__ void repack(const f32x16 (&v)[4], Unit (&u)[8]) {
-#pragma unroll
-  for (int ob = 0; ob < 4; ++ob)
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      unsigned h4[4], l4[4];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const float x0 = v[ob][8 * m + 2 * p], x1 = v[ob][8 * m + 2 * p + 1];
-        const unsigned hp = pack_bf16(x0, x1);
-        h4[p] = hp;
-        l4[p] = pack_bf16(x0 - __uint_as_float(hp << 16), x1 - __uint_as_float(hp & 0xffff0000u));
-      }
-      u[2 * ob + m].h = u32x4{h4[0], h4[1], h4[2], h4[3]};
-      u[2 * ob + m].l = u32x4{l4[0], l4[1], l4[2], l4[3]};
-    }
 }
 
 // one matrix: global -> LDS, 256 threads x 16 pieces of 16 bytes
@@ -156,19 +116,6 @@ __device__ __forceinline__ void layernorm_rows(f32x16 (&v)[4], const float* g, c
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[ob][4 * q + e] = (v[ob][4 * q + e] * rstd) * g4[e] + b4[e];
     }
-}
-
-// exact-erf GELU with erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, as in encoder_tail.hip: one v_rcp + one v_exp + 7 FMA-class
-// instructions instead of the ~50 of erff -- 64 activations per lane sit between two products with nothing to overlap them)
-__device__ __forceinline__ float gelu_erf(float v) {
-  const float x = fabsf(v) * 0.70710678118654752440f;
-  const float t = __builtin_amdgcn_rcpf(NM_FMA(0.3275911f, x, 1.0f));
-  float p = NM_FMA(1.061405429f, t, -1.453152027f);
-  p = NM_FMA(p, t, 1.421413741f);
-  p = NM_FMA(p, t, -0.284496736f);
-  p = NM_FMA(p, t, 0.254829592f);
-  const float e = 1.0f - (p * t) * __builtin_amdgcn_exp2f(-(x * x) * 1.44269504088896340736f);
-  return 0.5f * v * (1.0f + copysignf(e, v));
 }
 
 __global__ void __launch_bounds__(256, 1) fine_layer_kernel(FLArgs a) {
@@ -366,8 +313,8 @@ __global__ void __launch_bounds__(256, 1) fine_layer_kernel(FLArgs a) {
             pp[t] = p[8 * s2 + t];
           }
           bf16x8 vh, vm, ph, pm;
-          split2(vt, vh, vm);
-          split2(pp, ph, pm);
+          split8(vt, vh, vm);
+          split8(pp, ph, pm);
           ot = MFMA_BF16(vm, ph, ot);
           ot = MFMA_BF16(vh, pm, ot);
           ot = MFMA_BF16(vh, ph, ot);

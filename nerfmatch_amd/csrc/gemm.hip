@@ -29,7 +29,7 @@ struct GemmArgs {
   const uint8_t* col_mask;
 };
 
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
+__device__ __forceinline__ float gelu_erff(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 template <int NB, int MODE>
 __global__ void __launch_bounds__(256) gemm_kernel(GemmArgs a) {
@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(256) gemm_kernel(GemmArgs a) {
         if (MODE == MODE_LINEAR) {
           if (a.pre) v += a.pre[(size_t)row * a.N + col];
           if (a.act == NM_ACT_RELU) v = fmaxf(v, 0.f);
-          else if (a.act == NM_ACT_GELU) v = gelu_erf(v);
+          else if (a.act == NM_ACT_GELU) v = gelu_erff(v);
           if (a.res) v += a.res[(size_t)row * a.N + col];
           if (a.gate && !(a.gate[(size_t)row * a.N + col] > 0.f)) v = 0.f;
         } else {

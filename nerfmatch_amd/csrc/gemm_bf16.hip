@@ -17,18 +17,14 @@
 //     with coalesced writes).  The epilogue therefore transposes the tile through the (by then idle) LDS ring, half a
 //     tile at a time, and writes 256-byte row segments; `pre` / residual / `gate` are read in the same coalesced layout,
 //     the bias is the accumulators' starting value.
-#include "common.h"
+#include "bf16x3.h"
 #include <utility>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
 constexpr int GB_ROWS = 128;         // rows per workgroup
 constexpr int GB_COLS = 128;         // output features per workgroup (4 blocks of 32)
-constexpr int GB_SLOT_BYTES = 8192;  // 4 blocks x (hi, lo) x 64 lanes x 16 bytes
+constexpr int GB_SLOT_BYTES = NM_SLOT8K_BYTES;  // 4 blocks x (hi, lo) x 64 lanes x 16 bytes
 constexpr int GB_SLOT_FLOATS = GB_SLOT_BYTES / 4;
 constexpr int GB_RING = 4;
 
@@ -55,16 +51,6 @@ struct GemmBArgs {
 };
 
 __device__ __forceinline__ float gelu_erf_b(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-
-// two 1 KiB pieces per wavefront: one address / one M0, told apart by the immediate offset
-__device__ __forceinline__ void dma_slot(const char* slots, int g, float* ring, int wave, int lane) {
-  const unsigned voff = (unsigned)(wave * 2048 + lane * 16);
-  const char* base = slots + (size_t)g * GB_SLOT_BYTES;
-  const auto* src = (const __attribute__((address_space(1))) void*)(base + voff);
-  auto* dst = (__attribute__((address_space(3))) void*)(ring + (g & (GB_RING - 1)) * GB_SLOT_FLOATS + wave * 512);
-  __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
-  __builtin_amdgcn_global_load_lds(src, dst, 16, 1024, 0);
-}
 
 // epilogue: register 4q+e of block ob <-> feature 32 ob + 8 q + 4 half + e of row m (n_base = first column of the chunk + 4 half)
 __device__ __forceinline__ void epilogue(const GemmBArgs& a, const f32x16 (&acc)[4], int m, int n_base) {
@@ -300,11 +286,11 @@ __global__ void __launch_bounds__(256, 4) gemm_bf16x3_kernel(GemmBArgs a) {
   bias_init(a, acc, chunk * GB_COLS + 4 * hi);
 
   // prologue: slots / x pieces of K-steps 0 and 1 (same issue order as the loop: DMA, then x)
-  dma_slot(slots, 0, ring, wave, lane);
+  dma_slot_8k<GB_RING>(slots, 0, ring, wave, lane);
   XRow x0 = xload(0);
   XRow x1 = x0;
   if (nks > 1) {
-    dma_slot(slots, 1, ring, wave, lane);
+    dma_slot_8k<GB_RING>(slots, 1, ring, wave, lane);
     x1 = xload(1);
   }
   for (int ks = 0; ks < nks; ++ks) {
@@ -314,7 +300,7 @@ __global__ void __launch_bounds__(256, 4) gemm_bf16x3_kernel(GemmBArgs a) {
     __builtin_amdgcn_s_barrier();  // everybody's pieces of slot ks landed; nobody reads slot ks-2 any more
     XRow x2 = x1;
     if (ks + 2 < nks) {
-      dma_slot(slots, ks + 2, ring, wave, lane);
+      dma_slot_8k<GB_RING>(slots, ks + 2, ring, wave, lane);
       x2 = xload(ks + 2);
     }
     bf16x8 xh, xl;

@@ -83,11 +83,6 @@ __global__ void inerf_encode_kernel(const float* __restrict__ rays, const float*
 // through LDS atomics on one address each (128-way serialised): 380 us per step for 540 MB, 9 % of an iNeRF step.  Now a thread takes
 // (sample, frequency, axis) ITEMS in the order the gradient rows lie in memory (45 consecutive floats per half row), the view-direction rows
 // are read as whole 16-byte pieces, and the sums are lane reductions + one LDS round.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 constexpr int ENC_MAX_S = 1024;  // samples per ray this kernel holds Gaussians for (nm_inerf_encode_bwd* refuse more)
 template <bool TWO>
 __global__ void __launch_bounds__(256) inerf_encode_bwd_kernel(const float* __restrict__ rays, const float* __restrict__ z, int R, int S,

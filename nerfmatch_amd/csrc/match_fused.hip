@@ -19,17 +19,13 @@
 //   compact    ordered compaction per pair
 // Every conf value comes out of the same inlined expression on bit-identical accumulators (the tile code is one function), so
 // the equality tests compare equal bits exactly like the reference's `conf == conf.max()`.
-#include "common.h"
+#include "bf16x3.h"
 #include <limits.h>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
 constexpr int FT = 128;               // tile edge (rows and columns)
-constexpr int F_SLOT_BYTES = 8192;    // 4 blocks x (hi, lo) x 64 lanes x 16 bytes: one 16-wide K-step of 128 point rows
+constexpr int F_SLOT_BYTES = NM_SLOT8K_BYTES;  // 4 blocks x (hi, lo) x 64 lanes x 16 bytes: one 16-wide K-step of 128 point rows
 constexpr int F_SLOT_FLOATS = F_SLOT_BYTES / 4;
 constexpr int F_RING = 4;
 constexpr float LOG2E = 1.44269504088896340736f;
@@ -56,15 +52,6 @@ struct FArgs {
   float* sel_v;          // [P][M] row maximum of conf
   int* tie;              // [P][M] 1: resolve in the tie pass
 };
-
-__device__ __forceinline__ void dma_slot(const char* slots, int g, float* ring, int wave, int lane) {
-  const unsigned voff = (unsigned)(wave * 2048 + lane * 16);
-  const char* base = slots + (size_t)g * F_SLOT_BYTES;
-  const auto* src = (const __attribute__((address_space(1))) void*)(base + voff);
-  auto* dst = (__attribute__((address_space(3))) void*)(ring + (g & (F_RING - 1)) * F_SLOT_FLOATS + wave * 512);
-  __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
-  __builtin_amdgcn_global_load_lds(src, dst, 16, 1024, 0);
-}
 
 // acc[ob][reg] = dot(imn[row], ptn[col]) for row = 128 row_tile + 32 wave + (lane & 31), col = 128 chunk + 32 ob + (reg & 3) +
 // 8 (reg >> 2) + 4 (lane >> 5).  The K-loop of gemm_bf16x3_kernel (gemm_bf16.hip) with both sides pre-split: point slots by LDS
@@ -99,7 +86,7 @@ __device__ __forceinline__ void sim_tile(const FArgs& a, int p, int row_tile, in
 #pragma unroll
   for (int g = 0; g < 3; ++g)
     if (g < nks) {
-      dma_slot(slots, g, ring, wave, lane);
+      dma_slot_8k<F_RING>(slots, g, ring, wave, lane);
       xq[g] = xload(g);
     }
   for (int ks0 = 0; ks0 < nks; ks0 += 4)  // (nks is a multiple of 4: C in {64, 128, 256, 512}; j is the compile-time index of xq)
@@ -112,7 +99,7 @@ __device__ __forceinline__ void sim_tile(const FArgs& a, int p, int row_tile, in
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (ks + 3 < nks) {
-      dma_slot(slots, ks + 3, ring, wave, lane);
+      dma_slot_8k<F_RING>(slots, ks + 3, ring, wave, lane);
       xq[(j + 3) & 3] = xload(ks + 3);
     }
     const bf16x8 xh = __builtin_bit_cast(bf16x8, xq[j].h), xl = __builtin_bit_cast(bf16x8, xq[j].l);

@@ -1,13 +1,11 @@
 // Shared between the two generations of the split-bf16 fused NeRF kernel (nerf_fwd_bf16.hip: one wavefront per SIMD;
-// nerf_fwd_bf16_2w.hip: two wavefronts per SIMD): blob / LDS constants, the kernel argument block, small device helpers.
+// nerf_fwd_bf16_2w.hip: two wavefronts per SIMD): blob / LDS constants, the kernel argument block, small device helpers (the split-bf16
+// vocabulary itself -- vector types, split8, pack_bf16, nrow, MFMA_BF16 -- is bf16x3.h).
 #pragma once
-#include "common.h"
+#include "bf16x3.h"
 #include <string.h>
 
 namespace nmbf {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TILE = 128;
 constexpr int SLOT_BYTES = 16384;
@@ -68,13 +66,10 @@ struct NerfArgs {
   int* status;  // fp16x3: device int32[16] or NULL -- [0] |= 1 when an operand reached the fp16 limit, [1 + k] = max bits of range slot k
 };
 
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 // -DNM_TRACE: profiling build only -- the `raw` output becomes a [grid][32] table of s_memtime stamps of wavefront 0
 #ifndef NM_TRACE
 #define NM_TRACE 0
 #endif
-
-__host__ __device__ __forceinline__ constexpr int nrow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 __device__ __forceinline__ int launder(int v) {
   asm volatile("" : "+v"(v));
@@ -95,16 +90,6 @@ __device__ __forceinline__ int launder_s(int v) {
 #define TRACE(i) do { } while (0)
 #endif
 
-// x = hi + lo with hi, lo bf16 (round to nearest even): 16 bits of mantissa survive.
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)v[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(v[i] - (float)h);
-  }
-}
-
 // Element of a finished accumulator: one 32-bit cross-class copy (v_accvgpr_read_b32) at the point of use.  Without the
 // opaque asm the compiler copies whole 16-register tuples around (and through scratch when it runs out of registers).
 __device__ __forceinline__ float acc_read(float av) {
@@ -112,10 +97,6 @@ __device__ __forceinline__ float acc_read(float av) {
   return av;
 }
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {  // v_cvt_pk_bf16_f32 (round to nearest even)
-  return __builtin_bit_cast(unsigned, bf16x2{(__bf16)a, (__bf16)b});
-}
 // Opaque identity: keeps a value (and the instructions that made it) in the basic block and at the position it was
 // written -- without it LLVM sinks the re-packing arithmetic out of the MFMA stream into the block of its first use.
 template <class T>

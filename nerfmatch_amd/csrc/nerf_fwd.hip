@@ -68,7 +68,6 @@ struct NerfArgs {
 #define NM_XPIPE 0   // 1: produce the B operands of group g+1 while group g's MFMAs issue
 #endif
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 using wsrc_t = __amdgpu_buffer_rsrc_t;
 
 // 16-byte weight fetch: wave-uniform descriptor + scalar byte offset + constant per-lane offset (lane*16).

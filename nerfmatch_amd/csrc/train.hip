@@ -15,11 +15,6 @@ namespace {
 
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------- weight gradient
 // One workgroup = one 64x64 tile of dW over one slice of the M rows; its 4 wavefronts own the four 32x32 blocks.
