@@ -33,8 +33,10 @@ def _digest():
 
 
 SAFE_LIB = LIBDIR / "libnerfmatch_amd_safewait.so"  # checker build: every counted s_waitcnt vmcnt(n) is vmcnt(0) (csrc/common.h)
-# sources whose kernels use counted waits: only these differ in the checker build, the rest is linked from the product objects
-SAFE_SOURCES = ("attention_v2", "attention_bwd_v2", "attention_fp8", "encoder_tail", "encoder_tail_bwd", "gemm_bf16", "match_fused", "nerf_fwd_bf16")
+# sources whose kernels use counted waits (NM_WAIT_VMCNT, directly or through a header: tests/test_host_logic_cpu.py checks the list):
+# only these differ in the checker build, the rest is linked from the product objects
+SAFE_SOURCES = ("attention_v2", "attention_bwd_v2", "attention_fp8", "encoder_tail", "encoder_tail_bwd", "gemm_bf16", "match_fused", "nerf_fwd_bf16",
+                "nerf_points_bf16")
 
 
 SAFE_STAMP = LIBDIR / "build_safewait.stamp"
@@ -52,6 +54,10 @@ def build(force=False, verbose=False, safe=False):
         return LIB
     do_lib, do_safe = force or not have_lib, safe and (force or not have_safe)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    stems = {src.stem for src in sources()}
+    for obj in LIBDIR.glob("*.o"):  # objects of sources that no longer exist (scripts/build_variants.sh links every object it finds)
+        if obj.name.split(".")[0] not in stems:
+            obj.unlink()
     objs, safe_objs = [], []
     procs = []
     for src in sources():

@@ -128,7 +128,7 @@ __device__ __forceinline__ void wait_vm(int allow) {
   }
 }
 
-// K-step g of the 48-step stream, software pipelined over its two chunks ("consume first", as in nerf_fwd_bf16.hip):
+// K-step g of the 48-step stream, software pipelined over its two chunks ("consume first", as in nerf_split_chain.h):
 //   chunk 0 MFMAs (operands c0, fetched during the previous step)  |  behind them: the 8 operand reads of chunk 1 of THIS step
 //   wait: step g + 1 landed; barrier (=> for everybody; and everybody is past step g - 1)
 //   chunk 1 MFMAs  |  behind them: the 4 DMA pieces of step g + 3 (ring position of step g - 1), the 8 operand reads of chunk 0

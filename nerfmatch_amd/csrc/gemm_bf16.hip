@@ -1,6 +1,6 @@
 // y[M,N] = act(x[M,K] . w[N,K]^T + bias) + residual  on the bf16 matrix cores with fp32-accurate operand splitting.
 //
-// Same contract as nm_linear (gemm.hip); the arithmetic is that of nerf_fwd_bf16.hip: every fp32 operand is split into
+// Same contract as nm_linear (gemm.hip); the arithmetic is that of nerf_split_chain.h: every fp32 operand is split into
 // two bf16 values (x = hi + lo) and each product is w_hi*x_hi + w_hi*x_lo + w_lo*x_hi on v_mfma_f32_32x32x16_bf16 with
 // fp32 accumulation (error ~1e-6 relative; 3/16 of the fp32-MFMA time).
 //
@@ -10,7 +10,7 @@
 //     4-slot LDS ring with global_load_lds two K-steps ahead (one counted s_waitcnt + one s_barrier per K-step), the
 //     rows of x go global -> registers two K-steps ahead and are split on the fly;
 //   * 64 accumulator registers per wavefront: 3 waves/SIMD, so neighbouring workgroups hide each other's LDS and
-//     memory latency -- no hand scheduling here (contrast nerf_fwd_bf16.hip, which runs one wave per SIMD);
+//     memory latency -- no hand scheduling here (contrast nerf_split_chain.h, whose kernels run one wave per SIMD);
 //   * result layout lane = row, register = feature.  Stored like that (every lane 16-byte pieces of its own row, 32 bytes
 //     per row and instruction) the kernel ran at 2-3 TB/s: that store pattern, harmless on its own, halves the throughput
 //     as soon as it is MIXED with loads (scripts/ubench/access_pattern.hip: 3.7 TB/s for read + lane=row write against 6.6

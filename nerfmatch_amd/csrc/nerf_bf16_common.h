@@ -1,6 +1,6 @@
-// Shared between the two generations of the split-bf16 fused NeRF kernel (nerf_fwd_bf16.hip: one wavefront per SIMD;
-// nerf_fwd_bf16_2w.hip: two wavefronts per SIMD): blob / LDS constants, the kernel argument block, small device helpers (the split-bf16
-// vocabulary itself -- vector types, split8, pack_bf16, nrow, MFMA_BF16 -- is bf16x3.h).
+// Shared by the files of the operand-splitting NeRF MLP kernels (nerf_split_chain.h and the render / pointwise kernels built on it,
+// nerf_pack_bf16.hip): blob / LDS constants, the kernel argument block, small device helpers (the split-bf16 vocabulary itself -- vector
+// types, split8, pack_bf16, nrow, MFMA_BF16 -- is bf16x3.h).
 #pragma once
 #include "bf16x3.h"
 #include <string.h>
@@ -29,8 +29,14 @@ constexpr int OFF_BIAS = 0, OFF_BVIEWS = 2304, OFF_WALPHA = 2432, OFF_WRGB = 268
 constexpr int OFF_SCALE = 3088, OFF_DESCALE = 3104, OFF_INSCALE = 3112, SMALL = 3120;
 constexpr int NRANGE = 10;  // range telemetry slots: re-packed output of layers 0..8, views-layer extra inputs
 constexpr int SMALL_PAD = 4096;  // floats reserved in the blob / LDS (16 KiB)
-constexpr int NSLOT_PAD = 4;  // zero slots behind the last one: the two-wavefront kernel's weight stream runs that far past the end
+// zero slots behind the last one, for the run-ahead of the weight stream: a slot is requested ring_ahead (4) K-steps before its use and
+// the stream simply runs on past a tile's last slot (the 2w experiment, which read the same blob, is in scripts/variants/)
+constexpr int NSLOT_PAD = 4;
 constexpr size_t BLOB_BYTES = (size_t)SMALL_PAD * 4 + (size_t)(NSLOT_FULL + NSLOT_PAD) * SLOT_BYTES;
+constexpr int NSLOT_FULL_PAIRED = NSLOT_NORGB + HS / 2 + 2;  // 134: split modes -- eight paired hidden slots of the views layer, extras 0 | 1, extra 2
+constexpr size_t BLOB_BYTES_FP16 = (size_t)SMALL_PAD * 4 + (size_t)(NSLOT_FULL + 8) * (SLOT_BYTES / 2);  // fp16x1: 8 >= ring_ahead<1>() + 1 slots of padding
+constexpr int NSLOT_BWD = 8 + 8 + 16 * 9;  // 160: the transposed products of the pointwise backward (nerf_points_bf16.hip)
+constexpr size_t BLOB_BYTES_BWD = (size_t)SMALL_PAD * 4 + (size_t)(NSLOT_BWD + NSLOT_PAD) * SLOT_BYTES;
 
 // LDS map (floats)
 constexpr int LDS_SMALL = 0;

@@ -1,0 +1,713 @@
+// The K-loop machinery of the operand-splitting NeRF MLP kernels ("bf16x3" / "fp16x3" / "fp16x1"): everything the bodies of both
+// kernel files call -- nerf_fwd_bf16.hip (the fused per-ray render, whose header comment describes the structure) and
+// nerf_points_bf16.hip (the pointwise forward / backward pair of the iNeRF refinement).  Mode traits, the LDS ring of weight slots and
+// its barrier protocol, the loop-carried state (Ctx), the re-packing of a finished layer in the shadow of its consumer's MFMAs
+// (UnitWork), the K-steps (slot_step8 / 4 / 4x2) and the layer walk built from them (ipe_steps, layer_pass, views_*).
+// Everything here is __forceinline__: the two files compile to the device code they had as one translation unit.
+#pragma once
+#include "nerf_bf16_common.h"
+
+namespace nmbf {
+
+// Arithmetic mode P of the layer products (template parameter of everything below):
+//   P = 0  "bf16x3": operands split into bf16 hi / lo parts, three MFMAs per product block (16 KiB weight slots: hi and lo)
+//   P = 2  "fp16x3": the same with fp16 hi / lo parts (22 instead of 16 mantissa bits; saturating at the fp16 range)
+//   P = 1  "fp16x1": operands rounded once to fp16, ONE MFMA per product block (8 KiB slots) -- opt-in throughput mode of
+//                    the lean render's coarse pass: DESIGN.md section 3.1d
+//   P = 4  bf16x3 + the ReLU gates of every layer recorded as bits (the pointwise forward of the iNeRF refinement, nerf_points_bf16.hip)
+// Operands are carried as 16-byte vectors typed bf16x8 in all modes; P = 1, 2 reinterpret them as 8 x fp16.
+template <int P> constexpr bool is_bf16() { return P == 0 || P == 4; }
+template <int P> constexpr bool has_gates() { return P == 4; }
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+template <int P>
+__device__ __forceinline__ f32x16 mfma_p(const bf16x8& a, const bf16x8& b, const f32x16& c) {
+  if constexpr (is_bf16<P>()) return MFMA_BF16(a, b, c);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+template <int P> constexpr bool is_split() { return P != 1; }  // hi / lo operand pairs, three products
+template <int P> constexpr int slot_bytes() { return is_split<P>() ? SLOT_BYTES : SLOT_BYTES / 2; }
+template <int P> constexpr int slot_floats() { return slot_bytes<P>() / 4; }
+// ring geometry: the same 64 KiB hold 4 slots of 16 KiB or 8 of 8 KiB; a slot is requested `ring_ahead` K-steps before its use
+// (fp16x1: a K-step is 8 MFMAs, ~300 cycles -- two steps ahead would be less than the L2 -> LDS latency)
+template <int P> constexpr int ring_slots() { return is_split<P>() ? NRING : 2 * NRING; }
+template <int P> constexpr int ring_ahead() { return is_split<P>() ? 4 : 6; }
+constexpr float F16_MAX = 65504.0f;
+// x = hi + lo with hi, lo fp16 (round to nearest even), x clamped to the fp16 range first
+__device__ __forceinline__ void split8_f16(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
+  f16x8 h8, l8;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float c = __builtin_amdgcn_fmed3f(v[i], -F16_MAX, F16_MAX);
+    const _Float16 h = (_Float16)c;
+    h8[i] = h;
+    l8[i] = (_Float16)(c - (float)h);
+  }
+  hi = __builtin_bit_cast(bf16x8, h8);
+  lo = __builtin_bit_cast(bf16x8, l8);
+}
+template <int P>
+__device__ __forceinline__ void split8_p(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
+  if constexpr (is_bf16<P>()) split8(v, hi, lo);
+  else split8_f16(v, hi, lo);
+}
+template <int P>
+__device__ __forceinline__ float* ring_slot(float* ring, int g) { return ring + (g & (ring_slots<P>() - 1)) * slot_floats<P>(); }
+__device__ __forceinline__ unsigned pack_f16(float a, float b) {  // v_cvt_pk_f16_f32 (round to nearest even, two values)
+  const f16x2 h = {(_Float16)a, (_Float16)b};
+  return __builtin_bit_cast(unsigned, h);
+}
+__device__ __forceinline__ bf16x8 pack8_f16(const float (&v)[8]) {
+  const u32x4 r = {pack_f16(v[0], v[1]), pack_f16(v[2], v[3]), pack_f16(v[4], v[5]), pack_f16(v[6], v[7])};
+  return __builtin_bit_cast(bf16x8, r);
+}
+
+// The 4 pieces share ONE global address and ONE M0 (LDS base) and differ only in the instruction's immediate offset,
+// which the hardware adds on both sides -- measured 31 instead of 58 cycles of issue per piece beside the MFMAs.
+// Address = uniform slot base (SGPR pair) + one 32-bit per-lane offset: no 64-bit VGPR arithmetic per slot.
+template <int P>
+__device__ __forceinline__ void dma_slot(const char* blob_slots, int g, float* ring, int wave, int lane) {
+  const unsigned voff = (unsigned)(wave * (slot_bytes<P>() / 4) + lane * 16);
+  const char* base = blob_slots + (size_t)g * slot_bytes<P>();  // uniform
+  const auto* src = (const __attribute__((address_space(1))) void*)(base + voff);
+  auto* dst = (__attribute__((address_space(3))) void*)(ring_slot<P>(ring, g) + wave * (slot_floats<P>() / 4));
+  __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
+  __builtin_amdgcn_global_load_lds(src, dst, 16, 1024, 0);
+  if constexpr (is_split<P>()) {
+    __builtin_amdgcn_global_load_lds(src, dst, 16, 2048, 0);
+    __builtin_amdgcn_global_load_lds(src, dst, 16, 3072, 0);
+  }
+}
+
+// Ring protocol for slot g (identical sequence in all 4 wavefronts):
+//   wait until this wavefront's DMA pieces of slot g have landed (at most the 4 instructions of slot g+1 may remain
+//   in flight), barrier (=> every wavefront's pieces landed AND everybody finished reading slot g-1... g-2), then
+//   start the DMA of slot g+2 into the ring position that slot g-2 occupied.
+template <int P>
+__device__ __forceinline__ void ring_acquire(const char* blob_slots, int g, int nslots, float* ring, int wave, int lane) {
+  if constexpr (is_split<P>()) {
+    NM_WAIT_VMCNT(4);  // (slot g+1 is always in flight: the stream runs on into the blob's padding)
+  } else {
+    // Branch free: the stream simply runs on past the tile's last slot (the blob is padded by ring_ahead slots), so slots
+    // g+1 .. g+5 are ALWAYS in flight here, 2 DMA instructions per wavefront each.  (A first version that counted the
+    // remaining slots cost ten scalar branches per K-step -- as much as the 8 MFMAs.)
+    NM_WAIT_VMCNT(10);
+  }
+  __builtin_amdgcn_s_barrier();
+  if constexpr (is_split<P>()) dma_slot<P>(blob_slots, g + ring_ahead<P>(), ring, wave, lane);
+  // (fp16x1: this form only opens a tile -- slot 0 landed, slots 1..5 in flight, nothing new requested; inside the stream
+  //  ring_acquire_pair does the work for two K-steps at once)
+}
+
+// Split modes, NM_RING_PAIRS: ONE barrier per two K-steps.  The s_memtime trace with the barrier compiled out
+// (scripts/trace_nerf.py on the -DNM_ABL=2 build of scripts/variants/nerf_study_switches_r6.patch) put the per-K-step barrier at 196 of a K-step's 1150 cycles -- more than the weight DMA
+// (81), the operand reads (160) or the re-packing (143): four wavefronts on four SIMDs re-synchronised every 24 MFMAs pay the
+// slowest one's stalls every time.  Called in the middle of every ODD K-step g (8-block layers; at the start of it in the views
+// layer): slots g+1 and g+2 -- requested two K-steps ago, right behind the previous barrier -- must have landed (this wavefront's
+// pieces: vmcnt(0); everybody's: the barrier); then slots g+3 and g+4 are requested into the ring positions of slots g-1 and g,
+// whose last reads (the second-half operands of slot g, fetched in the first half of K-step g) every wavefront issued before it
+// arrived here.  The 4-slot ring suffices: two slots in use, two in flight.
+template <int P>
+__device__ __forceinline__ void ring_acquire_two(const char* blob_slots, int g, float* ring, int wave, int lane) {
+  // lgkmcnt(0): this wavefront's own reads of slot g (issued 8 MFMAs ago) have RETURNED before it signals the barrier -- the DMA
+  // another wavefront issues right behind the barrier overwrites that ring position
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  dma_slot<P>(blob_slots, g + 3, ring, wave, lane);
+  dma_slot<P>(blob_slots, g + 4, ring, wave, lane);
+}
+
+// fp16x1, called in every EVEN K-step g: slots g+1 and g+2 have landed when at most the 6 DMA instructions of slots g+3..g+5
+// remain in flight; one barrier for both; then slots g+6 and g+7 are requested into the ring positions of slots g-2 and g-1
+// (every wavefront is past their MFMAs).  Halves the barriers / counted waits per MFMA of a stream whose K-step is 8 MFMAs.
+__device__ __forceinline__ void ring_acquire_pair(const char* blob_slots, int g, float* ring, int wave, int lane) {
+  NM_WAIT_VMCNT(6);
+  __builtin_amdgcn_s_barrier();
+  dma_slot<1>(blob_slots, g + 6, ring, wave, lane);
+  dma_slot<1>(blob_slots, g + 7, ring, wave, lane);
+}
+
+// A operands of half a slot: 4 output blocks x (hi, lo) = 8 x 16 bytes per lane.
+struct OpHalf {
+  bf16x8 h[4], l[4];
+};
+
+template <int P>
+__device__ __forceinline__ void load_half(OpHalf& d, const float* slot, int lane, int p) {
+  const u32x4* s4 = reinterpret_cast<const u32x4*>(slot) + lane;
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    if constexpr (is_split<P>()) {
+      d.h[o] = __builtin_bit_cast(bf16x8, s4[((4 * p + o) * 2 + 0) * 64]);
+      d.l[o] = __builtin_bit_cast(bf16x8, s4[((4 * p + o) * 2 + 1) * 64]);
+    } else {
+      d.h[o] = __builtin_bit_cast(bf16x8, s4[(4 * p + o) * 64]);
+    }
+  }
+}
+
+// Loop-carried state of the layer pipeline (all per wavefront; Unit = the B operands of one K-step: bf16x3.h)
+struct Ctx {
+  const char* blob_slots;
+  float* ring;
+  const float* sm_small;
+  f32x4* tapw;      // this lane's column of the workspace
+  // NM_TAP_PREFETCH: read-back of the tile's tapped activations (32 rows of 1 KiB per wavefront; the workspace of the 32 CUs of an XCD
+  // is as large as their L2, so the rows come back over the fabric: 6.6 k cycles when the reduction asks for them itself)
+  bool tap_pref;    // this tile reads its tap back (a feature output is wanted, regular tile)
+  bool rgb;         // the pass has colour heads (the views K-loop is the tile's last; else layer 7's)
+  float* tap_ring;  // landing zones of this wavefront, both free once the tile's last K-loop is over: ring slot `wave` (rows 0..15)
+  float* tap_ipe;   //   and its IPE operand region (rows 16..27); rows 28..31 are loaded by the reduction itself, behind its first 14 units
+  int nslots, wave, lane, hi;
+  int tap;          // layer whose activations are tapped (-1: none)
+  int g;            // next weight slot
+  OpHalf opA;       // A operands of the next half slot, fetched one half slot ahead
+  OpHalf opB;       // fp16x1: blocks 4-7 of the next slot (the whole slot is fetched one K-step ahead there)
+  Unit xn;          // B operands of the next hidden K-step
+  float sig_part;   // this lane's partial dot product of the density head
+  float sc;         // fp16x3: s_l of the finished layer in cx.hv (OFF_SCALE), wavefront-uniform -> lives in an SGPR: the re-packing fma
+                    // has two VGPR sources like the add it replaces
+  float vmax;       // fp16x3: running max |re-packed value| of the layer being consumed (range telemetry / saturation flag)
+  unsigned* rng;    // this thread's column of the [NRANGE][256] LDS table
+  u32x4* gptr;       // P = 4: this thread's cell of the gate table of the tile in flight, [layer][256 threads] x 16 bytes
+  unsigned gbits[4]; // P = 4: ReLU gates of the layer being re-packed, 8 bits per unit (bit k < 4: element 2k, bit 4 + k: element 2k + 1)
+  float hv[128];    // finished layer (raw accumulators, before bias/relu), lane local: hv[16 block + register]
+};
+
+// 8 gate bits of one unit from its four packed hi words (two bf16 halves each): bit k = low half of word k non-zero, bit 4 + k = high half
+__device__ __forceinline__ unsigned gate_byte(const u32x4& h) {
+  // v_pk_min_u16 against (1, 1): 0 / 1 per half.  (Inline asm on scalars: the vector-typed __builtin_elementwise_min on a bit-cast
+  // element of the ext-vector came out reading word 0 four times -- scripts/ubench/gate_byte.hip.)
+  const unsigned w0 = h[0], w1 = h[1], w2 = h[2], w3 = h[3];
+  unsigned m0, m1, m2, m3;
+  const unsigned one = 0x00010001u;
+  asm("v_pk_min_u16 %0, %1, %2" : "=v"(m0) : "v"(w0), "v"(one));
+  asm("v_pk_min_u16 %0, %1, %2" : "=v"(m1) : "v"(w1), "v"(one));
+  asm("v_pk_min_u16 %0, %1, %2" : "=v"(m2) : "v"(w2), "v"(one));
+  asm("v_pk_min_u16 %0, %1, %2" : "=v"(m3) : "v"(w3), "v"(one));
+  const unsigned t = m0 | (m1 << 1) | (m2 << 2) | (m3 << 3);
+  return (t & 0xfu) | ((t >> 12) & 0xf0u);
+}
+
+// Unit u of the finished layer lo held in cx.hv: registers 8m .. 8m+7 (m = u & 1) of output block u >> 1, i.e. neurons
+// 32 (u>>1) + 16 m + 4 half + {0..3, 8..11}  ->  + bias, relu, hi/lo split.
+// Cut into pieces of <= 6 VALU instructions; slot_step8/4 issue one piece behind each MFMA of a half slot, pinned with
+// sched_barriers, so the re-packing runs in the shadow of the matrix pipe.  Branch free on purpose: the pieces must stay
+// inside the MFMAs' basic block.
+template <int P>
+struct UnitWork {
+  Ctx& cx;
+  Unit& out;
+  int u, lo;
+  float floor_v;
+  f32x4 b0, b1;
+  float sc;  // fp16x3: s_lo (OFF_SCALE)
+  float v8[8];
+  float f0, f1;
+  unsigned hpk;  // fp16x3: the packed hi pair of the current pair of values
+  // bias loads; issued ahead of the MFMAs that shadow the pieces (and ahead of the next A-operand fetch, so that the
+  // counted LDS wait in front of piece 0 covers these two reads only)
+  __device__ __forceinline__ void prefetch() {
+    const int ob = u >> 1, m = u & 1;
+    const float* bl = cx.sm_small + OFF_BIAS + lo * 256 + ob * 32 + 16 * m + 4 * cx.hi;
+    b0 = *reinterpret_cast<const f32x4*>(bl); b1 = *reinterpret_cast<const f32x4*>(bl + 8);
+  }
+  __device__ __forceinline__ void operator()(int j) {
+    const int ob = u >> 1, m = u & 1;
+    if (j < 4) {               // elements j and 4 + j: bias, relu
+      if constexpr (is_bf16<P>()) {
+        v8[j] = __builtin_fmaxf(cx.hv[ob * 16 + 8 * m + j] + b0[j], floor_v);
+        v8[4 + j] = __builtin_fmaxf(cx.hv[ob * 16 + 8 * m + 4 + j] + b1[j], floor_v);
+      } else if constexpr (P == 1) {  // fp16 operands: the same instruction count with v_med3_f32 -- an activation beyond the fp16
+                                      // range saturates instead of turning into infinity (and the pass into NaNs)
+        v8[j] = __builtin_amdgcn_fmed3f(cx.hv[ob * 16 + 8 * m + j] + b0[j], floor_v, F16_MAX);
+        v8[4 + j] = __builtin_amdgcn_fmed3f(cx.hv[ob * 16 + 8 * m + 4 + j] + b1[j], floor_v, F16_MAX);
+      } else {  // fp16x3: the accumulator goes to the next layer's input scale inside the bias add (one v_fma instead of one v_add;
+                // exact), and the running maximum of what is about to become fp16 is kept: a value AT the limit raises the
+                // saturation flag at the end of the kernel (status[0]) -- never a silent clamp
+        v8[j] = __builtin_amdgcn_fmed3f(__builtin_fmaf(cx.hv[ob * 16 + 8 * m + j], sc, b0[j]), floor_v, F16_MAX);
+        v8[4 + j] = __builtin_amdgcn_fmed3f(__builtin_fmaf(cx.hv[ob * 16 + 8 * m + 4 + j], sc, b1[j]), floor_v, F16_MAX);
+        asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(cx.vmax) : "v"(v8[j]), "v"(v8[4 + j]));
+      }
+      pin(v8[j]); pin(v8[4 + j]);
+    } else if constexpr (P == 1) {  // pieces 4..7: pair p = j - 4 rounded to fp16 and packed (pieces 8..11: nothing)
+      if (j < 8) {
+        unsigned hp = pack_f16(v8[2 * (j - 4)], v8[2 * (j - 4) + 1]);
+        pin(hp);
+        out.h[j - 4] = hp;
+      }
+    } else if (!(j & 1)) {     // pair p = (2p, 2p+1): hi halves and their fp32 values
+      const int p = (j - 4) >> 1;
+      unsigned hp;
+      if constexpr (is_bf16<P>()) {
+        hp = pack_bf16(v8[2 * p], v8[2 * p + 1]);
+        f0 = __uint_as_float(hp << 16);
+        f1 = __uint_as_float(hp & 0xffff0000u);
+      } else {
+        // fp16 parts: hi = the value truncated to 11 significant bits by v_cvt_pkrtz_f16_f32 (round toward zero, two values per
+        // instruction); lo = v - hi comes straight from the PACKED hi register with v_fma_mix_f32 (an fp16 half as a source of
+        // an fp32 FMA: hi * -1 + v, exact) in piece j+1 -- no fp32 copy of hi is made -- and needs 12 bits at most, rounded to
+        // nearest by v_cvt_pk_f16_f32: 22 significant bits like the round-to-nearest split (below 2^-14, where fp16 is
+        // subnormal, the absolute quantum 2^-24 bounds the error).
+        hp = pack_f16(v8[2 * p], v8[2 * p + 1]);  // (round to nearest: |lo| <= 2^-12 |v|; the remainder below is exact for either rounding)
+        hpk = hp;
+      }
+      pin(hp);
+      if constexpr (is_bf16<P>()) { pin(f0); pin(f1); }
+      out.h[p] = hp;
+    } else {                   // lo halves = rounded remainders
+      const int p = (j - 5) >> 1;
+      float r0, r1;
+      if constexpr (is_bf16<P>()) {
+        r0 = v8[2 * p] - f0; r1 = v8[2 * p + 1] - f1;
+      } else {
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hpk), "v"(v8[2 * p]));
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hpk), "v"(v8[2 * p + 1]));
+      }
+      pin(r0); pin(r1);
+      unsigned lp = is_bf16<P>() ? pack_bf16(r0, r1) : pack_f16(r0, r1);
+      pin(lp);
+      out.l[p] = lp;
+      if constexpr (has_gates<P>()) {
+        if (j == 11) {  // all four hi words of the unit exist: value > 0 <=> its bf16 hi half is non-zero (after the ReLU nothing is negative)
+          const unsigned t = gate_byte(out.h);
+          cx.gbits[u >> 2] |= t << (8 * (u & 3));
+        }
+      }
+    }
+  }
+};
+// fp16x3: the consumer of layer `slot`'s output has made all its units -- fold the running maximum into this thread's LDS cell
+// (ds_max_u32 without return: fire and forget; the values are >= 0, so the bit patterns order like the floats)
+template <int P>
+__device__ __forceinline__ void fold_range(Ctx& cx, int slot) {
+  if constexpr (P == 2) {
+    // (inline asm: for a ds_ instruction it can see, the compiler first waits vmcnt(0) -- the weight stream's LDS-DMA "may write LDS" --
+    //  i.e. for the two slots requested half a K-step ago, at the end of EVERY layer's K-loop.  An LDS atomic without return needs no wait;
+    //  LDS operations complete in order, so one more in flight only makes the compiler's own lgkmcnt waits conservative.)
+    const unsigned addr = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned*)(cx.rng + slot * 256);
+    asm volatile("ds_max_u32 %0, %1" :: "v"(addr), "v"(__float_as_uint(cx.vmax)) : "memory");
+    cx.vmax = 0.f;
+  }
+}
+struct NoWork {
+  __device__ __forceinline__ void prefetch() {}
+  __device__ __forceinline__ void operator()(int) {}
+};
+// The work of a layer's LAST K-step (which re-packs nothing: all 16 units of the previous layer exist, cx.hv is dead): blocks 0..3 of the
+// layer being finished are final once that K-step's first half is through, so their 64 accumulator reads (v_accvgpr_read, finish_layer's
+// first half) go behind the MFMAs of its second half instead of in front of the next layer.
+template <int P>
+struct AccTake {
+  const f32x16 (&acc)[8];
+  Ctx& cx;
+  __device__ __forceinline__ void prefetch() {}
+  __device__ __forceinline__ void operator()(int j) {
+    constexpr int per = is_split<P>() ? 6 : 8;  // 12 pieces of 6 (split modes) / 8 pieces of 8 (fp16x1)
+#pragma unroll
+    for (int k = 0; k < per; ++k) {
+      const int i = per * j + k;
+      if (i < 64) cx.hv[i] = acc_read(acc[i >> 4][i & 15]);
+    }
+  }
+};
+template <int P>
+__device__ __forceinline__ UnitWork<P> unit_work(int u, int lo, Ctx& cx, Unit& out) {
+  return UnitWork<P>{cx, out, u, lo, lo < 8 ? 0.f : (!is_bf16<P>() ? -F16_MAX : -__builtin_inff()), {}, {}, cx.sc, {}, 0.f, 0.f, 0u};
+}
+
+// End of layer l: move the accumulators out of the AGPRs (the next layer starts from C = 0 in the same registers) and
+// make unit 0.  The only part of the re-packing that is not hidden behind MFMAs (128 + ~40 VALU instructions).
+template <int P>
+__device__ __forceinline__ void finish_layer(const f32x16 (&acc)[8], int l, Ctx& cx) {
+#pragma unroll
+  for (int ob = 4; ob < 8; ++ob)  // (blocks 0..3: AccTake, in the shadow of the layer's last K-step)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) cx.hv[ob * 16 + r] = acc_read(acc[ob][r]);
+  if constexpr (P == 2)
+    cx.sc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, cx.sm_small[OFF_SCALE + l])));
+  UnitWork<P> w = unit_work<P>(0, l, cx, cx.xn);
+  w.prefetch();
+#pragma unroll
+  for (int j = 0; j < 12; ++j) w(j);
+}
+
+// Density head on the finished layer 7: sigma partial = relu(h7) . w_alpha over this lane's 128 neurons.  Once per tile,
+// not hidden behind MFMAs (~2k cycles).
+// (fp16x3: bias and density vector are stored pre-scaled -- relu(fma(acc, s_7, b'_7)) = 2^c_8 relu(h_7), w'_alpha = 2^-c_8 w_alpha)
+__device__ __forceinline__ void alpha_head(Ctx& cx) {
+  const float* bl = cx.sm_small + OFF_BIAS + 7 * 256 + 4 * cx.hi;
+  const float* wa = cx.sm_small + OFF_WALPHA + 4 * cx.hi;
+  const float s7 = cx.sm_small[OFF_SCALE + 7];  // (1 in the other modes: fma(x, 1, b) == x + b)
+  float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+#pragma unroll
+  for (int ob = 0; ob < 8; ++ob)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4 b = *reinterpret_cast<const f32x4*>(bl + ob * 32 + 8 * q);
+      const f32x4 w4v = *reinterpret_cast<const f32x4*>(wa + ob * 32 + 8 * q);
+      p0 = NM_FMA(__builtin_fmaxf(__builtin_fmaf(cx.hv[ob * 16 + 4 * q + 0], s7, b[0]), 0.f), w4v[0], p0);
+      p1 = NM_FMA(__builtin_fmaxf(__builtin_fmaf(cx.hv[ob * 16 + 4 * q + 1], s7, b[1]), 0.f), w4v[1], p1);
+      p2 = NM_FMA(__builtin_fmaxf(__builtin_fmaf(cx.hv[ob * 16 + 4 * q + 2], s7, b[2]), 0.f), w4v[2], p2);
+      p3 = NM_FMA(__builtin_fmaxf(__builtin_fmaf(cx.hv[ob * 16 + 4 * q + 3], s7, b[3]), 0.f), w4v[3], p3);
+    }
+  cx.sig_part = (p0 + p1) + (p2 + p3);
+}
+
+// Tapped activations (fp32, after bias and relu) of the finished layer lo -> L2-resident workspace, 1 KiB per store.
+// Once per tile and not hidden behind MFMAs (~2k cycles).
+__device__ __forceinline__ void dump_tap(int lo, Ctx& cx) {
+  const float* bl = cx.sm_small + OFF_BIAS + lo * 256 + 4 * cx.hi;
+  const float sl = cx.sm_small[OFF_SCALE + lo];  // (fp16x3: the workspace holds 2^c_{lo+1} x the activations; OFF_DESCALE undoes it per ray)
+  auto* tp = (__attribute__((address_space(1))) f32x4*)cx.tapw;  // (global_store, not flat_store: a pending FLAT access makes every later ds_read wait for vmcnt)
+#pragma unroll
+  for (int ob = 0; ob < 8; ++ob) {
+    f32x4 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4 b = *reinterpret_cast<const f32x4*>(bl + ob * 32 + 8 * q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[q][e] = __builtin_fmaxf(__builtin_fmaf(cx.hv[ob * 16 + 4 * q + e], sl, b[e]), 0.f);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tp[q * 64] = v[q];  // immediate offsets 0, 1, 2, 3 KiB
+    tp += 256;
+    pin(tp);  // one running pointer instead of 32 precomputed addresses
+  }
+}
+
+// acc[4p .. 4p+3] (+)= W_half . (xh + xl)  as  w_hi*x_hi + w_hi*x_lo + w_lo*x_hi; FIRST starts from C = 0
+template <int P, bool FIRST, int NOB>
+__device__ __forceinline__ void mfma_head(f32x16 (&acc)[NOB], int p, const OpHalf& a, const bf16x8& xh) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int o = 0; o < 4; ++o) acc[4 * p + o] = mfma_p<P>(a.h[o], xh, FIRST ? zero : acc[4 * p + o]);
+}
+template <int P, int NOB>
+__device__ __forceinline__ void mfma_tail(f32x16 (&acc)[NOB], int p, const OpHalf& a, const bf16x8& xh, const bf16x8& xl) {
+#pragma unroll
+  for (int o = 0; o < 4; ++o) acc[4 * p + o] = mfma_p<P>(a.h[o], xl, acc[4 * p + o]);
+#pragma unroll
+  for (int o = 0; o < 4; ++o) acc[4 * p + o] = mfma_p<P>(a.l[o], xh, acc[4 * p + o]);
+}
+
+// fp16x1 form of the K-step: 8 MFMAs whose A operands (all 8 blocks of slot g) were fetched during the PREVIOUS K-step, so
+// no MFMA waits for LDS, and everything else a K-step has to issue -- the ring barrier of slot g+1 with the DMA of a later
+// slot, the 8 operand reads of slot g+1, the bias reads and the 8 pieces of re-packing work -- sits BETWEEN the MFMAs, a
+// few instructions behind each (with 8 MFMAs per K-step instead of 24 there is no second half to hide them behind; a first
+// version that issued barrier and reads up front ran at 640 cycles per K-step against 256 of MFMA time).
+// (past the last slot the fetched operands are stale ring contents nobody uses)
+__device__ __forceinline__ bf16x8 load_op1(const float* slot, int lane, int blk) {
+  return __builtin_bit_cast(bf16x8, (reinterpret_cast<const u32x4*>(slot) + lane)[blk * 64]);
+}
+#define NM_SB __builtin_amdgcn_sched_barrier(0)
+template <bool FIRST, bool ACQ, class Work>
+__device__ __forceinline__ void slot_step8_one(f32x16 (&acc)[8], Ctx& cx, const bf16x8& x, Work work) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int g = cx.g;
+  const OpHalf A = cx.opA, B = cx.opB;
+  const float* nxt = ring_slot<1>(cx.ring, g + 1);
+  acc[0] = mfma_p<1>(A.h[0], x, FIRST ? zero : acc[0]); NM_SB;
+  if constexpr (ACQ) ring_acquire_pair(cx.blob_slots, g, cx.ring, cx.wave, cx.lane);
+  NM_SB;
+  acc[1] = mfma_p<1>(A.h[1], x, FIRST ? zero : acc[1]); NM_SB;
+  cx.opA.h[0] = load_op1(nxt, cx.lane, 0); cx.opA.h[1] = load_op1(nxt, cx.lane, 1); work.prefetch(); NM_SB;
+  acc[2] = mfma_p<1>(A.h[2], x, FIRST ? zero : acc[2]); NM_SB;
+  cx.opA.h[2] = load_op1(nxt, cx.lane, 2); cx.opA.h[3] = load_op1(nxt, cx.lane, 3); NM_SB;
+  acc[3] = mfma_p<1>(A.h[3], x, FIRST ? zero : acc[3]); NM_SB;
+  cx.opB.h[0] = load_op1(nxt, cx.lane, 4); cx.opB.h[1] = load_op1(nxt, cx.lane, 5); NM_SB;
+  acc[4] = mfma_p<1>(B.h[0], x, FIRST ? zero : acc[4]); NM_SB;
+  cx.opB.h[2] = load_op1(nxt, cx.lane, 6); cx.opB.h[3] = load_op1(nxt, cx.lane, 7); NM_SB;
+  acc[5] = mfma_p<1>(B.h[1], x, FIRST ? zero : acc[5]); NM_SB;
+  work(0); work(1); NM_SB;  // (first use of the bias reads: the LDS wait in front of it has two more MFMAs of cover)
+  acc[6] = mfma_p<1>(B.h[2], x, FIRST ? zero : acc[6]); NM_SB;
+  work(2); work(3); work(4); NM_SB;
+  acc[7] = mfma_p<1>(B.h[3], x, FIRST ? zero : acc[7]); NM_SB;
+  work(5); work(6); work(7); NM_SB;
+  cx.g = g + 1;
+}
+
+// One K-step (slot cx.g) of an 8-block layer, software pipelined over half slots with a "consume first" order: every
+// batch of LDS reads is issued right AFTER four MFMAs that use the previously fetched operands:
+//   head(blocks 0-3, A) | fetch B = blocks 4-7 of slot g | tail(blocks 0-3, A)
+//   ring barrier of slot g+1 (+ DMA of slot g+3)
+//   head(blocks 4-7, B) | fetch A = blocks 0-3 of slot g+1 | tail(blocks 4-7, B)
+// work(j), j = 0..11, is VALU work independent of this slot's second half (re-packing of a later K-step's B operands);
+// piece j is issued right behind the j-th MFMA of the second half.
+// (EVEN: the K-step's position in the weight stream is even -- every layer holds an even number of K-steps, so the callers know)
+template <int P, bool FIRST, bool EVEN, class Work>
+__device__ __forceinline__ void slot_step8(f32x16 (&acc)[8], Ctx& cx, const bf16x8& xh, const bf16x8& xl, Work work) {
+  if constexpr (P == 1) {
+    slot_step8_one<FIRST, EVEN>(acc, cx, xh, work);
+    return;
+  }
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int g = cx.g;
+  OpHalf B;
+  mfma_head<P, FIRST, 8>(acc, 0, cx.opA, xh);
+  __builtin_amdgcn_sched_barrier(0);
+  load_half<P>(B, cx.ring + (g & (NRING - 1)) * SLOT_FLOATS, cx.lane, 1);
+  work.prefetch();
+  __builtin_amdgcn_sched_barrier(0);
+  mfma_tail<P, 8>(acc, 0, cx.opA, xh, xl);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (!EVEN) ring_acquire_two<P>(cx.blob_slots, g, cx.ring, cx.wave, cx.lane);
+  // from here to the end of the K-step: ONE basic block (the work pieces must not be separated from their MFMAs)
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    acc[4 + o] = mfma_p<P>(B.h[o], xh, FIRST ? zero : acc[4 + o]);
+    __builtin_amdgcn_sched_barrier(0);
+    work(o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // the next slot's first operands, behind four MFMAs ("consume first"); unconditional: past the last slot they are
+  // stale ring contents nobody uses
+  load_half<P>(cx.opA, cx.ring + ((g + 1) & (NRING - 1)) * SLOT_FLOATS, cx.lane, 0);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    acc[4 + o] = mfma_p<P>(B.h[o], xl, acc[4 + o]);
+    __builtin_amdgcn_sched_barrier(0);
+    work(4 + o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    acc[4 + o] = mfma_p<P>(B.l[o], xh, acc[4 + o]);
+    __builtin_amdgcn_sched_barrier(0);
+    work(8 + o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  cx.g = g + 1;
+}
+
+// Same for the 4-block views layer (a slot is a single half).
+template <bool FIRST, bool ACQ, class Work>
+__device__ __forceinline__ void slot_step4_one(f32x16 (&acc)[4], Ctx& cx, const bf16x8& x, Work work) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int g = cx.g;
+  const OpHalf C = cx.opA;
+  const float* nxt = ring_slot<1>(cx.ring, g + 1);
+  acc[0] = mfma_p<1>(C.h[0], x, FIRST ? zero : acc[0]); NM_SB;
+  if constexpr (ACQ) ring_acquire_pair(cx.blob_slots, g, cx.ring, cx.wave, cx.lane);
+  NM_SB;
+  acc[1] = mfma_p<1>(C.h[1], x, FIRST ? zero : acc[1]); NM_SB;
+#pragma unroll
+  for (int o = 0; o < 4; ++o) cx.opA.h[o] = load_op1(nxt, cx.lane, o);
+  work.prefetch(); NM_SB;
+  acc[2] = mfma_p<1>(C.h[2], x, FIRST ? zero : acc[2]); NM_SB;
+  work(0); work(1); work(2); work(3); NM_SB;
+  acc[3] = mfma_p<1>(C.h[3], x, FIRST ? zero : acc[3]); NM_SB;
+  work(4); work(5); work(6); work(7); NM_SB;
+  cx.g = g + 1;
+}
+
+template <int P, bool FIRST, bool EVEN, class Work>
+__device__ __forceinline__ void slot_step4(f32x16 (&acc)[4], Ctx& cx, const bf16x8& xh, const bf16x8& xl, Work work) {
+  if constexpr (P == 1) {
+    slot_step4_one<FIRST, EVEN>(acc, cx, xh, work);
+    return;
+  }
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int g = cx.g;
+  const OpHalf C = cx.opA;
+  work.prefetch();
+  if constexpr (!EVEN) ring_acquire_two<P>(cx.blob_slots, g, cx.ring, cx.wave, cx.lane);
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    acc[o] = mfma_p<P>(C.h[o], xh, FIRST ? zero : acc[o]);
+    __builtin_amdgcn_sched_barrier(0);
+    work(o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  load_half<P>(cx.opA, cx.ring + ((g + 1) & (NRING - 1)) * SLOT_FLOATS, cx.lane, 0);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    acc[o] = mfma_p<P>(C.h[o], xl, acc[o]);
+    __builtin_amdgcn_sched_barrier(0);
+    work(4 + o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    acc[o] = mfma_p<P>(C.l[o], xh, acc[o]);
+    __builtin_amdgcn_sched_barrier(0);
+    work(8 + o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  cx.g = g + 1;
+}
+
+// Split modes, NM_VIEWS_PAIRS: TWO K-steps of the 4-block views layer per weight slot (half 0: the four output blocks of K-step 2s, half 1:
+// those of K-step 2s + 1) -- the shape of slot_step8 with both halves accumulating into the same four blocks: one ring barrier, one DMA of a
+// FULL slot and one counted wait per 24 MFMAs instead of per 12 (a single 4-block K-step runs at 67 cycles per MFMA against the 8-block
+// layers' 46: its fixed cost does not hide behind 12 MFMAs).  w0 makes the unit the SECOND half consumes (u1, ready behind this slot's
+// 12th MFMA), w1 the first unit of the next slot (cx.xn).
+template <int P, bool FIRST, bool EVEN, class W0, class W1>
+__device__ __forceinline__ void slot_step4x2(f32x16 (&av)[4], Ctx& cx, const bf16x8& x0h, const bf16x8& x0l, Unit& u1, W0 w0, W1 w1) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int g = cx.g;
+  const OpHalf A = cx.opA;
+  OpHalf B;
+  w0.prefetch();
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    av[o] = mfma_p<P>(A.h[o], x0h, FIRST ? zero : av[o]);
+    __builtin_amdgcn_sched_barrier(0);
+    w0(o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  load_half<P>(B, cx.ring + (g & (NRING - 1)) * SLOT_FLOATS, cx.lane, 1);  // the second K-step's operands, behind four MFMAs
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    av[o] = mfma_p<P>(A.h[o], x0l, av[o]);
+    __builtin_amdgcn_sched_barrier(0);
+    w0(4 + o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    av[o] = mfma_p<P>(A.l[o], x0h, av[o]);
+    __builtin_amdgcn_sched_barrier(0);
+    w0(8 + o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // (all reads of this slot are issued: the barrier below may hand its ring position to slot g + 4)
+  if constexpr (!EVEN) ring_acquire_two<P>(cx.blob_slots, g, cx.ring, cx.wave, cx.lane);
+  const bf16x8 x1h = __builtin_bit_cast(bf16x8, u1.h), x1l = __builtin_bit_cast(bf16x8, u1.l);
+  w1.prefetch();
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    av[o] = mfma_p<P>(B.h[o], x1h, av[o]);
+    __builtin_amdgcn_sched_barrier(0);
+    w1(o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  load_half<P>(cx.opA, cx.ring + ((g + 1) & (NRING - 1)) * SLOT_FLOATS, cx.lane, 0);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    av[o] = mfma_p<P>(B.h[o], x1l, av[o]);
+    __builtin_amdgcn_sched_barrier(0);
+    w1(4 + o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    av[o] = mfma_p<P>(B.l[o], x1h, av[o]);
+    __builtin_amdgcn_sched_barrier(0);
+    w1(8 + o);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  cx.g = g + 1;
+}
+
+// The hidden part of the views layer: layer 7's sixteen units (unit 0 in cx.xn) against the folded 128 x 256 matrix
+template <int P>
+__device__ __forceinline__ void views_hidden(f32x16 (&av)[4], Ctx& cx) {
+  if constexpr (is_split<P>()) {
+#pragma unroll
+    for (int sl = 0; sl < HS / 2; ++sl) {
+      const Unit x0 = cx.xn;
+      Unit u1;
+      const bf16x8 x0h = __builtin_bit_cast(bf16x8, x0.h), x0l = __builtin_bit_cast(bf16x8, x0.l);
+      // (NSLOT_NORGB is even: slot sl of the views layer sits at an even stream position iff sl is even)
+      if (sl == 0) slot_step4x2<P, true, true>(av, cx, x0h, x0l, u1, unit_work<P>(1, 7, cx, u1), unit_work<P>(2, 7, cx, cx.xn));
+      else if (sl + 1 == HS / 2) slot_step4x2<P, false, false>(av, cx, x0h, x0l, u1, unit_work<P>(2 * sl + 1, 7, cx, u1), NoWork{});
+      else if (sl & 1) slot_step4x2<P, false, false>(av, cx, x0h, x0l, u1, unit_work<P>(2 * sl + 1, 7, cx, u1), unit_work<P>(2 * sl + 2, 7, cx, cx.xn));
+      else slot_step4x2<P, false, true>(av, cx, x0h, x0l, u1, unit_work<P>(2 * sl + 1, 7, cx, u1), unit_work<P>(2 * sl + 2, 7, cx, cx.xn));
+    }
+  } else {
+#pragma unroll
+    for (int ks = 0; ks < HS; ks += 2) {
+      {
+        const Unit xc = cx.xn;
+        if (ks == 0) slot_step4<P, true, true>(av, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 1, 7, cx, cx.xn));
+        else slot_step4<P, false, true>(av, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 1, 7, cx, cx.xn));
+      }
+      {
+        const Unit xc = cx.xn;
+        if (ks + 2 < HS) slot_step4<P, false, false>(av, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 2, 7, cx, cx.xn));
+        else slot_step4<P, false, false>(av, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), NoWork{});
+      }
+    }
+  }
+}
+// The three extra K-steps (direction encoding, appearance row, padding): split modes with NM_VIEWS_PAIRS -- the first two share a slot
+template <int P>
+__device__ __forceinline__ void views_extras(f32x16 (&av)[4], Ctx& cx, const bf16x8 (&eh)[VS], const bf16x8 (&el)[VS]) {
+  if constexpr (is_split<P>()) {
+    Unit u1;
+    u1.h = __builtin_bit_cast(u32x4, eh[1]); u1.l = __builtin_bit_cast(u32x4, el[1]);
+    slot_step4x2<P, false, true>(av, cx, eh[0], el[0], u1, NoWork{}, NoWork{});   // stream position NSLOT_NORGB + 8: even
+    slot_step4<P, false, false>(av, cx, eh[2], el[2], NoWork{});                  // a single half slot at an odd position
+  } else {
+#pragma unroll
+    for (int e = 0; e < VS; ++e) {
+      if (e & 1) slot_step4<P, false, false>(av, cx, eh[e], el[e], NoWork{});  // (the views layer's extra K-steps sit at positions 16, 17, 18)
+      else slot_step4<P, false, true>(av, cx, eh[e], el[e], NoWork{});
+    }
+  }
+}
+
+// IPE K-steps of layers 0 (FIRST: they open the layer) and 5 (skip connection, after the hidden K-steps)
+template <int P, bool FIRST>
+__device__ __forceinline__ void ipe_steps(f32x16 (&acc)[8], Ctx& cx, const float* ipe_src) {
+  auto operand = [&](int m, bf16x8& ph, bf16x8& pl) {
+    // (fp16x1: one operand per K-step, at [m][64 lanes][4 floats] of the same LDS region)
+    ph = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ipe_src + (is_split<P>() ? (m * 2 + 0) : m) * 256));
+    pl = ph;
+    if constexpr (is_split<P>()) pl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ipe_src + (m * 2 + 1) * 256));
+  };
+#pragma unroll
+  for (int m = 0; m < XS; m += 2) {  // (XS is even; pairs so that the position parity is a template argument)
+    bf16x8 ph, pl;
+    operand(m, ph, pl);
+    if (m == 0) slot_step8<P, FIRST, true>(acc, cx, ph, pl, NoWork{});
+    else slot_step8<P, false, true>(acc, cx, ph, pl, NoWork{});
+    operand(m + 1, ph, pl);
+    if (m + 2 == XS) slot_step8<P, false, false>(acc, cx, ph, pl, AccTake<P>{acc, cx});  // (the IPE steps close layers 0 and 5)
+    else slot_step8<P, false, false>(acc, cx, ph, pl, NoWork{});
+  }
+}
+
+// One pts layer (l = 1..7): unit ks+1 of the finished layer l-1 (in cx.hv) is made in the shadow of K-step ks.
+// (feature_linear is no layer of this kernel: it has no activation, so nerf_pack_split multiplies it into the views layer.)
+template <int P>
+__device__ __forceinline__ void layer_pass(f32x16 (&acc)[8], int l, Ctx& cx, const float* ipe_src) {
+  if (l - 1 == cx.tap) dump_tap(l - 1, cx);
+#pragma unroll
+  for (int ks = 0; ks < HS; ks += 2) {  // (pairs: the parity of a K-step's position in the stream is a template argument)
+    {
+      const Unit xc = cx.xn;
+      if (ks == 0) slot_step8<P, true, true>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 1, l - 1, cx, cx.xn));
+      else slot_step8<P, false, true>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 1, l - 1, cx, cx.xn));
+    }
+    {
+      const Unit xc = cx.xn;
+      if (ks + 2 < HS) slot_step8<P, false, false>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 2, l - 1, cx, cx.xn));
+      // (every layer, no branch in the MFMA stream: in layer 5 the skip connection's IPE steps still follow, what is taken here is
+      //  overwritten by their own AccTake)
+      else slot_step8<P, false, false>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), AccTake<P>{acc, cx});
+    }
+  }
+  fold_range<P>(cx, l - 1);  // (all 16 units of layer l-1's output exist now)
+  if constexpr (has_gates<P>()) {
+    cx.gptr[(l - 1) * 256] = u32x4{cx.gbits[0], cx.gbits[1], cx.gbits[2], cx.gbits[3]};
+    cx.gbits[0] = cx.gbits[1] = cx.gbits[2] = cx.gbits[3] = 0u;
+  }
+  if (l == 5) ipe_steps<P, false>(acc, cx, ipe_src);
+  finish_layer<P>(acc, l, cx);
+  if (l == 7) {  // the last pts layer: tap / density head read it from cx.hv (inside the layer loop's body: after the loop, next to the
+                 // views K-loop, the register allocator spilled ~150 registers per tile)
+    // (a pass without colour heads has no K-loop behind this point: it does the same after the layer loop, behind tap_prefetch)
+    if (cx.rgb) {
+      if (cx.tap == 7) dump_tap(7, cx);
+      alpha_head(cx);
+    }
+  }
+}
+
+}  // namespace nmbf

@@ -102,7 +102,7 @@ class FineField:
 
 
 class FusedField:
-    """nerf_fine's pointwise forward / backward as TWO fused kernels (round 4; csrc/nerf_fwd_bf16.hip, nm_nerf_points_fwd_bf16x3 /
+    """nerf_fine's pointwise forward / backward as TWO fused kernels (round 4; csrc/nerf_points_bf16.hip, nm_nerf_points_fwd_bf16x3 /
     nm_nerf_points_bwd_bf16x3) instead of 12 + 14 GEMM launches: the K-loop machinery of the render kernel, activations in
     registers, and between the passes only one BIT per ReLU activation (9 x 16 bytes per sample lane).  dX only -- the pose is the
     only parameter of the refinement.  With the matching term (round 5) the forward kernel also writes the tapped layer's activations

@@ -1,4 +1,5 @@
-"""Interleaved A/B timing of nerf_fwd variants (one process per variant because the library is loaded once)."""
+"""Interleaved A/B timing of nerf_fwd variants (one process per variant because the library is loaded once).
+For the NM_ABL / NM_TELEMETRY / NM_IPE_EXACT variants apply scripts/variants/nerf_study_switches_r6.patch first."""
 import os, subprocess, sys, json
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]

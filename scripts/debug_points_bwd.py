@@ -1,5 +1,8 @@
+"""Stage-by-stage check of the pointwise backward chain against a GEMM chain.  Needs a library built with -DNM_POINTS_DEBUG=1
+(nm_nerf_points_bwd_bf16x3_dbg): apply scripts/variants/nerf_study_switches_r6.patch first."""
 import sys, torch
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from nerfmatch_amd import inerf, ops, synth
 from nerfmatch_amd.nerf.renderer import NerfRenderer
 torch.set_grad_enabled(False)

@@ -1,3 +1,4 @@
+# the nowscale / ipex variants (-DNM_NO_WSCALE on nerf_pack_bf16, -DNM_IPE_EXACT on nerf_fwd_bf16): apply scripts/variants/nerf_study_switches_r6.patch first
 cd $GRAFT_REPO_ROOT
 V=nerfmatch_amd/lib/variants
 {

@@ -2,7 +2,8 @@
 |HIP - reference fp32|, |HIP - reference fp64| and |reference fp32 - fp64| over all rays of all fixtures, per output.
 One process per library variant (NERFMATCH_AMD_LIB), e.g.
     python scripts/surface_seed_stats.py fp32 fp16x3 fp16x3:neutral
-`:neutral` skips the activation-scale calibration (weights still scaled unless the library was built with -DNM_NO_WSCALE)."""
+`:neutral` skips the activation-scale calibration (weights still scaled unless the library was built with -DNM_NO_WSCALE;
+for that and the other study variants apply scripts/variants/nerf_study_switches_r6.patch first)."""
 import sys
 from pathlib import Path
 

@@ -1,4 +1,4 @@
-// micro test of gate_byte (nerf_fwd_bf16.hip): 4 packed words -> 8 gate bits
+// micro test of gate_byte (nerf_split_chain.h): 4 packed words -> 8 gate bits
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

@@ -119,7 +119,7 @@ def run_wave(blob, ipe90, dirpe27, app16, tap, need_rgb=True):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# fp16x3 blob of nerf_fwd_bf16.hip (round 4: power-of-two operand scaling).  CPU model of the SCALE BOOK-KEEPING only: the
+# fp16x3 blob of nerf_pack_bf16.hip (round 4: power-of-two operand scaling).  CPU model of the SCALE BOOK-KEEPING only: the
 # weight slots are read back into plain matrices (hi + lo, still carrying their pack-time factor), and the layer chain is
 # replayed with the kernel's re-packing rule  v = relu(fma(acc, s_l, bias'_l))  and head / tap descaling, in float64.
 F16 = dict(OFF_BIAS=0, OFF_BVIEWS=2304, OFF_WALPHA=2432, OFF_WRGB=2688, OFF_MISC=3072, OFF_SCALE=3088, OFF_DESCALE=3104, OFF_INSCALE=3112,

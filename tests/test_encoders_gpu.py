@@ -67,7 +67,7 @@ def test_modules_vs_reference_values(gpu, built_lib, name):
 
 @pytest.mark.parametrize("name", WITH_IPE)
 def test_split_kernel_arithmetic_vs_reference_values(gpu, built_lib, name):
-    """arith = 1 evaluates x_ret with the device functions nerf_fwd_bf16.hip inlines (exp2-based exponential, fp32 Cody-Waite sine)."""
+    """arith = 1 evaluates x_ret with the device functions nerf_fwd_bf16.hip inlines (sin32: nerf_bf16_common.h) (exp2-based exponential, fp32 Cody-Waite sine)."""
     fx = load_golden(name)
     n = fx["ipe_coarse"].shape[0]
     mean, var = fx["mean_coarse"].reshape(-1, 3)[:n].to(gpu), fx["var_coarse"].reshape(-1, 3)[:n].to(gpu)

@@ -249,3 +249,25 @@ def test_gt_ids_follow_the_current_mask():
     m._gt_ids(c)
     c[0, 0, 0] = True  # an in-place change of the same tensor is seen too
     assert all(torch.equal(a, b) for a, b in zip(m._gt_ids(c), torch.where(c)))
+
+
+def test_safe_sources_are_the_files_with_counted_waits():
+    """The checker library recompiles exactly build.SAFE_SOURCES with every counted wait turned into a full one: the list must be the
+    csrc/*.hip files that mention NM_WAIT_VMCNT -- or the NM_SAFE_WAIT switch itself, as encoder_tail_chain.h's wait_vm_n does --
+    themselves or through a project header they include (common.h only defines the macro)."""
+    import re
+
+    from nerfmatch_amd import build
+
+    text = {p.name: p.read_text() for p in list(build.CSRC.glob("*.hip")) + list(build.CSRC.glob("*.h"))}
+
+    def waits(name, seen):
+        if name == "common.h" or name not in text or name in seen:
+            return False
+        seen.add(name)
+        return bool(re.search("NM_WAIT_VMCNT|NM_SAFE_WAIT", text[name])) or any(waits(inc, seen) for inc in re.findall(r'#include\s+"([^"]+)"', text[name]))
+
+    want = {name[:-4] for name in text if name.endswith(".hip") and waits(name, set())}
+    assert len(want) >= 8
+    assert set(build.SAFE_SOURCES) == want
+    assert len(build.SAFE_SOURCES) == len(want)
