@@ -338,7 +338,7 @@ int nm_linear_pack_bf16x3(const float* w, int N, int K, void* blob, nmStream_t s
  * without a transposed copy of the weight in between.  nm_linear_blob_bytes_bf16x3(N, K) bytes. */
 int nm_linear_pack_t_bf16x3(const float* w, int N, int K, void* blob, nmStream_t stream);
 
-/* Row-wise LayerNorm over `dim` (<= 1024, multiple of 64), eps as nn.LayerNorm (1e-5).
+/* Row-wise LayerNorm over `dim` in {64,128,256,512} (NM_ERR_UNSUPPORTED otherwise), eps as nn.LayerNorm (1e-5).
  * (nerfmatch/modules/attention.py:196-207, :229-230, :238). */
 int nm_layernorm(const float* x, const float* gamma, const float* beta, int rows, int dim, float eps, float* y,
                  nmStream_t stream);

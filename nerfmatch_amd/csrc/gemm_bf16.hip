@@ -42,7 +42,7 @@ struct GemmBArgs {
   float scale;
   const uint8_t* row_mask;
   const uint8_t* col_mask;
-  int fast_epi;  // 1: transposed (coalesced) epilogue; 0: register-layout epilogue (pre / gate present)
+  int fast_epi;  // 1: transposed (coalesced) epilogue, whatever addends are set; 0: register-layout epilogue (NM_GEMM_COALESCED=0 only)
   // fused q|k|v (or k|v) projection for attn32_v2_kernel (nm_linear_qkv_bf16x3): columns [0, n_q) go to y (row stride n_q),
   // columns [n_q, n_q + 32 H) are the keys and [n_q + 32 H, n_q + 64 H) the values, written split and laid out as that
   // kernel's MFMA operands (attention_v2.hip: 8 KiB slot per (batch, head, 32-key tile)) instead of as fp32 rows

@@ -359,7 +359,8 @@ def _linear_blob_t(weight):
 
 def linear_t(dy, weight):
     """dy (..., N_out) @ weight (N_out, K_in) -> (..., K_in): a linear layer's input gradient.  Split-bf16 arithmetic: nm_linear_bf16x3 on the
-    transposed-pack blob; otherwise nm_linear on the cached transposed copy (ops.transposed)."""
+    transposed-pack blob; otherwise nm_linear on the cached transposed copy (ops.transposed).  N_out is the K of that product and the kernels
+    slice K into 8-wide pieces: an N_out that is no multiple of 8 (a 3-wide output head) is zero-padded to the next one, on both operands."""
     No, Ki = weight.shape
     if LINEAR_PRECISION == "bf16x3" and No % 8 == 0 and Ki % 8 == 0:
         d2 = dy.reshape(-1, No).contiguous()
@@ -368,6 +369,10 @@ def linear_t(dy, weight):
             check(lib().nm_linear_bf16x3(dptr(d2), dptr(_linear_blob_t(weight), torch.uint8), None, None, None, None, d2.shape[0], Ki, No,
                                          _lib.NM_ACT_NONE, dptr(y), stream()), "nm_linear_bf16x3")
         return y.reshape(*dy.shape[:-1], Ki)
+    if No % 8:
+        pad = -No % 8  # (the zero columns add exact zeros to every sum)
+        wt = _linear_cached(("Tpad",), weight, lambda w: torch.nn.functional.pad(w.t(), (0, pad)).contiguous())
+        return linear(torch.nn.functional.pad(dy, (0, pad)), wt)
     return linear(dy, transposed(weight))
 
 
