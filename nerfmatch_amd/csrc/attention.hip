@@ -1,4 +1,5 @@
-// LayerNorm and softmax multi-head attention.
+// Softmax multi-head attention: the fp32 kernels and the nm_attention entry point, which also routes to the
+// split-bf16 kernel of attention_v2.hip.
 //
 // attn32_kernel: flash-style attention for head dim 32 on the fp32 matrix cores; the (L,S,H) score tensor the
 // reference materialises (415 MB at 3600^2 x 8 heads) never exists.  One wavefront owns 32 queries of one head.
@@ -9,58 +10,10 @@
 // K / V tiles are staged once per workgroup in LDS (see attn32_kernel) and shared by its 4 query tiles.
 // attn_small_kernel: sequences <= 64 tokens (the 5x5 fine windows: 25 tokens, head dim 16): one thread per query,
 // K/V of the (batch, head) in LDS, plain fp32 FMAs.
-#include "common.h"
+#include "attention_tile.h"
+#include "internal.h"
 
 namespace {
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-
-// one wavefront per row; dim = 64 * PER
-template <int PER>
-__device__ __forceinline__ void layernorm_row(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b, int rows, float eps,
-                                              float* __restrict__ y, int row) {
-  const int lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const int dim = 64 * PER;
-  const float* xr = x + (size_t)row * dim;
-  float v[PER];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    v[i] = xr[lane + 64 * i];
-    s += v[i];
-  }
-  const float mean = wave_sum(s) / (float)dim;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const float d = v[i] - mean;
-    q = NM_FMA(d, d, q);
-  }
-  const float var = wave_sum(q) / (float)dim;
-  const float rstd = 1.0f / sqrtf(var + eps);
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const int c = lane + 64 * i;
-    y[(size_t)row * dim + c] = (v[i] - mean) * rstd * g[c] + b[c];
-  }
-}
-template <int PER>
-__global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                        const float* __restrict__ b, int rows, float eps, float* __restrict__ y) {
-  layernorm_row<PER>(x, g, b, rows, eps, y, blockIdx.x * 4 + (threadIdx.x >> 6));
-}
-// two tensors with their own affine parameters in one launch (round 5: the two pre-norms of a cross-attention layer): workgroups [0, g0) take
-// the first, the rest the second; a row's arithmetic is layernorm_kernel's
-template <int PER>
-__global__ void __launch_bounds__(256) layernorm2_kernel(const float* __restrict__ x0, const float* __restrict__ g0, const float* __restrict__ b0, int rows0,
-                                                         float eps0, float* __restrict__ y0, int wg0, const float* __restrict__ x1,
-                                                         const float* __restrict__ g1, const float* __restrict__ b1, int rows1, float eps1,
-                                                         float* __restrict__ y1) {
-  if ((int)blockIdx.x < wg0) layernorm_row<PER>(x0, g0, b0, rows0, eps0, y0, blockIdx.x * 4 + (threadIdx.x >> 6));
-  else layernorm_row<PER>(x1, g1, b1, rows1, eps1, y1, (blockIdx.x - wg0) * 4 + (threadIdx.x >> 6));
-}
 
 // Workgroup = 4 wavefronts = 128 queries of one (batch, head); every 32-key K/V tile is fetched ONCE per workgroup
 // with coalesced 16-byte loads (thread t: key t/8, 16 bytes at column 4*(t%8)) and staged in a 3-slot LDS ring (rows
@@ -83,7 +36,7 @@ __global__ void __launch_bounds__(256) attn32_kernel(const float* __restrict__ q
   const int qrow = qt * 32 + j;
   const int qc = qrow < L ? qrow : L - 1;
   float qreg[16];
-  {
+  {  // (load16, the tail mask and store16 of attention_tile.h are written out in this kernel: as calls they changed its register allocation)
     const float qs = scale * 1.44269504088896340736f;  // scores are kept in the log2 domain
     const float* qp = q + ((size_t)b * L + qc) * ldq + h * 32 + 4 * hi;
 #pragma unroll
@@ -165,7 +118,7 @@ __global__ void __launch_bounds__(256) attn32_kernel(const float* __restrict__ q
     for (int i = 0; i < 16; ++i) o[i] *= alpha;
     const float* vs = sm + cur * KV_SLOT + va_off;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o = MFMA32(vs[((r & 3) + 8 * (r >> 2)) * KV_LD], sc[r], o);
+    for (int r = 0; r < 16; ++r) o = MFMA32(vs[nrow(r, 0) * KV_LD], sc[r], o);
     if (t + 2 < nt) sstore(sm + nx2 * KV_SLOT, kst, vst);
     __syncthreads();
     cur = nxt;
@@ -227,40 +180,6 @@ __global__ void __launch_bounds__(64) attn_small_kernel(const float* __restrict_
 
 }  // namespace
 
-extern "C" int nm_layernorm(const float* x, const float* gamma, const float* beta, int rows, int dim, float eps, float* y,
-                            nmStream_t stream) {
-  NM_CHECK_ARG(x && gamma && beta && y && rows > 0 && dim > 0);
-  hipStream_t s = (hipStream_t)stream;
-  const int grid = (rows + 3) / 4;
-  switch (dim) {
-    case 64: layernorm_kernel<1><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y); break;
-    case 128: layernorm_kernel<2><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y); break;
-    case 256: layernorm_kernel<4><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y); break;
-    case 512: layernorm_kernel<8><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y); break;
-    default: return NM_ERR_UNSUPPORTED;
-  }
-  return nm_launch_status();
-}
-
-extern "C" int nm_layernorm2(const float* x0, const float* gamma0, const float* beta0, int rows0, float eps0, float* y0, const float* x1,
-                             const float* gamma1, const float* beta1, int rows1, float eps1, float* y1, int dim, nmStream_t stream) {
-  NM_CHECK_ARG(x0 && gamma0 && beta0 && y0 && x1 && gamma1 && beta1 && y1 && rows0 > 0 && rows1 > 0 && dim > 0);
-  hipStream_t s = (hipStream_t)stream;
-  const int wg0 = (rows0 + 3) / 4, grid = wg0 + (rows1 + 3) / 4;
-  switch (dim) {
-    case 64: layernorm2_kernel<1><<<grid, 256, 0, s>>>(x0, gamma0, beta0, rows0, eps0, y0, wg0, x1, gamma1, beta1, rows1, eps1, y1); break;
-    case 128: layernorm2_kernel<2><<<grid, 256, 0, s>>>(x0, gamma0, beta0, rows0, eps0, y0, wg0, x1, gamma1, beta1, rows1, eps1, y1); break;
-    case 256: layernorm2_kernel<4><<<grid, 256, 0, s>>>(x0, gamma0, beta0, rows0, eps0, y0, wg0, x1, gamma1, beta1, rows1, eps1, y1); break;
-    case 512: layernorm2_kernel<8><<<grid, 256, 0, s>>>(x0, gamma0, beta0, rows0, eps0, y0, wg0, x1, gamma1, beta1, rows1, eps1, y1); break;
-    default: return NM_ERR_UNSUPPORTED;
-  }
-  return nm_launch_status();
-}
-
-size_t nm_internal_attn_v2_workspace(int B, int S, int heads);
-int nm_internal_attn_v2(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S, int heads,
-                        float scale, void* workspace, float* out, hipStream_t s, float* nlse_out);
-
 extern "C" size_t nm_attention_workspace_bytes(int B, int S, int heads) {
   if (B <= 0 || S <= 0 || heads <= 0) return 0;
   return nm_internal_attn_v2_workspace(B, S, heads);
@@ -270,8 +189,7 @@ extern "C" int nm_attention(const float* q, const float* k, const float* v, int 
                             int heads, int head_dim, float scale, int flags, void* workspace, float* out, float* nlse_out,
                             nmStream_t stream) {
   const bool small = S <= 64 && L <= 64 && (head_dim == 16 || head_dim == 32);
-  // the split-bf16 kernel streams pre-split operands from a workspace (its first generation, which split while staging and
-  // needed none, is gone from the library: DESIGN.md section 3.4); the flag is ignored on the other routes
+  // the split-bf16 kernel streams pre-split operands from a workspace; the flag is ignored on the other routes
   const bool split = (flags & NM_ATTN_BF16X3) && head_dim == 32 && !small;
   if (nlse_out && !split) return NM_ERR_UNSUPPORTED;  // only the split-bf16 kernel keeps the log-sum-exp
   if (split && !workspace) return NM_ERR_WORKSPACE;

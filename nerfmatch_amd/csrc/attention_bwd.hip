@@ -10,18 +10,15 @@
 //   attn32_bwd_dkv_kernel  one wavefront = 32 keys; loops over the query tiles, accumulates dK and dV.  No atomics.
 // Seven 32x32x32 contractions per tile pair instead of the minimal five (S and dP are computed by both kernels) buy
 // deterministic, atomic-free gradients.
-#include "common.h"
+#include "attention_tile.h"
+#include "internal.h"
 
 namespace {
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 constexpr int LD = 36;                 // floats per LDS row (32 + 4 pad: conflict-free 16-byte row reads)
 constexpr int TILE = 32 * LD;          // one 32 x 32 tile
 constexpr int SLOT = 2 * TILE + 64;    // two tiles + 2 x 32 per-row scalars
 constexpr float LOG2E = 1.44269504088896340736f;
-
-__device__ __forceinline__ int nrow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // rows[32 x 32] . regs: out[row i][col j] = sum_d tile[i][d] * breg(j)[d]   (A = LDS rows, B = registers of lane j)
 __device__ __forceinline__ f32x16 rows_times_regs(const float* tile, int j, int hi, const float (&breg)[16]) {
@@ -43,21 +40,7 @@ __device__ __forceinline__ f32x16 rows_times_regs(const float* tile, int j, int 
 __device__ __forceinline__ void cols_times_regs(const float* tile, int j, int hi, const f32x16& p, f32x16& acc) {
   const float* a = tile + 4 * hi * LD + j;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc = MFMA32(a[((r & 3) + 8 * (r >> 2)) * LD], p[r], acc);
-}
-
-__device__ __forceinline__ void load16(const float* p, float s, float (&reg)[16]) {  // dims 8c + 4hi + t (p already offset by 4hi)
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const f32x4 t4 = *reinterpret_cast<const f32x4*>(p + 8 * c);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) reg[4 * c + t] = t4[t] * s;
-  }
-}
-
-__device__ __forceinline__ void store16(float* p, const f32x16& a, float s) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4*>(p + 8 * g) = f32x4{a[4 * g] * s, a[4 * g + 1] * s, a[4 * g + 2] * s, a[4 * g + 3] * s};
+  for (int r = 0; r < 16; ++r) acc = MFMA32(a[nrow(r, 0) * LD], p[r], acc);
 }
 
 struct BwdArgs {
@@ -101,7 +84,7 @@ __global__ void __launch_bounds__(256) attn32_bwd_dq_kernel(BwdArgs a) {
     *reinterpret_cast<f32x4*>(slot + st_off) = kk;
     *reinterpret_cast<f32x4*>(slot + TILE + st_off) = vv;
   };
-  auto mask_tail = [&](int t, f32x16& sc) {
+  auto mask_last = [&](int t, f32x16& sc) {
     if (t == nt - 1 && (a.S & 31)) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
@@ -118,7 +101,7 @@ __global__ void __launch_bounds__(256) attn32_bwd_dq_kernel(BwdArgs a) {
     const float* slot = sm + (t & 1) * SLOT;
     if (t + 1 < nt) gload(t + 1, kst, vst);
     f32x16 sc = rows_times_regs(slot, j, hi, qreg);
-    mask_tail(t, sc);
+    mask_last(t, sc);
     float mx = sc[0];
 #pragma unroll
     for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[r]);
@@ -149,7 +132,7 @@ __global__ void __launch_bounds__(256) attn32_bwd_dq_kernel(BwdArgs a) {
     const float* slot = sm + (t & 1) * SLOT;
     if (t + 1 < nt) gload(t + 1, kst, vst);
     f32x16 sc = rows_times_regs(slot, j, hi, qreg);
-    mask_tail(t, sc);
+    mask_last(t, sc);
     const f32x16 dp = rows_times_regs(slot + TILE, j, hi, doreg);
 #pragma unroll
     for (int r = 0; r < 16; ++r) sc[r] = __builtin_amdgcn_exp2f(sc[r] - lse) * (dp[r] - dsum);  // dS
@@ -317,12 +300,6 @@ __global__ void __launch_bounds__(64) attn_small_bwd_kernel(BwdArgs a) {
 }
 
 }  // namespace
-
-// attention_bwd_v2.hip
-size_t nm_internal_attn_bwd_v2_workspace(int B, int L, int S, int heads);
-int nm_internal_attn_bwd_v2(const float* q, const float* k, const float* v, const float* o, const float* d_o, int ldq, int ldk, int ldv,
-                            int ldo, int lddo, int B, int L, int S, int heads, float scale, float* dq, float* dk, float* dv, int lddq,
-                            int lddk, int lddv, void* workspace, hipStream_t s, const float* nlse_fwd);
 
 extern "C" size_t nm_attention_bwd_workspace_bytes(int B, int L, int S, int heads, int flags) {
   if (B <= 0 || L <= 0 || S <= 0 || heads <= 0) return 0;

@@ -7,10 +7,11 @@
 //   query-tile slot (17 KiB) : Q rows, dO rows, Q^T, dO^T (query-permuted), -lse/-D  -> attn32_bwd_dkv_v2_kernel (lane = key)
 // "rows" = A operand of a (rows x dims) . (dims x lanes) product; "^T permuted" = A operand of a (dims x rows) . (rows x
 // lanes) product whose B operand is what the first product left in the accumulator registers (k-slot i of step ks <->
-// row (i&3) + 16 ks + 8 (i>>2) + 4 half, cf. attention_v2.hip).  The soft-max shift and the D term enter as the C operand
+// row (i&3) + 16 ks + 8 (i>>2) + 4 half = nrow(8 ks + i, half), cf. kv_presplit_kernel in attention_v2.hip).  The soft-max shift and the D term enter as the C operand
 // of the first MFMA (-lse, -D), so the scores come out ready for exp2 and dP - D needs no subtraction.
 // The dq kernel first rebuilds the log-sum-exp of its queries (scores only, lazy running maximum) and publishes -lse, -D.
-#include "bf16x3.h"
+#include "attention_tile.h"
+#include "internal.h"
 
 namespace {
 
@@ -28,13 +29,13 @@ __global__ void __launch_bounds__(256) bwd_presplit_kernel(const float* __restri
                                                             const float* __restrict__ nd, char* __restrict__ blob) {
   const int t = blockIdx.x, h = blockIdx.y, b = blockIdx.z, nt = gridDim.x;
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, half = lane >> 5;
-  char* slot = blob + (((size_t)b * H + h) * nt + t) * slot_bytes;
+  char* slot = blob + tile_slot(b, H, h, nt, t) * slot_bytes;
   for (int job = tid >> 6; job < 2 * groups; job += 4) {  // job = (group, k-step)
     const int g = job >> 1, ks = job & 1;
     const float* src = (g & 1) ? y : x;
     const int ld = (g & 1) ? ldy : ldx;
     float v8[8];
-    if (g < 2) {  // rows: row = r, k-slots = dims 16 ks + 8 half + i
+    if (g < 2) {  // "rows" gather of kv_presplit_kernel (attention_v2.hip)
       const int row = t * 32 + r;
       if (row < n) {
         const float* p = src + ((size_t)b * n + row) * ld + h * 32 + 16 * ks + 8 * half;
@@ -44,7 +45,7 @@ __global__ void __launch_bounds__(256) bwd_presplit_kernel(const float* __restri
 #pragma unroll
         for (int i = 0; i < 8; ++i) v8[i] = 0.f;
       }
-    } else {  // transposed: row = dim r, k-slot i of step ks <-> tile row (i&3) + 16 ks + 8 (i>>2) + 4 half
+    } else {  // its "transposed, accumulator-permuted" gather
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int row = t * 32 + (i & 3) + 16 * ks + 8 * (i >> 2) + 4 * half;
@@ -106,48 +107,17 @@ __device__ __forceinline__ f32x16 mma_rows(const u32x4* s4, int p0, const bf16x8
   return acc;
 }
 
-__device__ __forceinline__ void load_split(const float* p, float s, bf16x8 (&h)[2], bf16x8 (&l)[2]) {  // dims 16 m + 8 half + i
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const f32x4 a4 = *reinterpret_cast<const f32x4*>(p + 16 * m), b4 = *reinterpret_cast<const f32x4*>(p + 16 * m + 4);
-    const float v8[8] = {a4[0] * s, a4[1] * s, a4[2] * s, a4[3] * s, b4[0] * s, b4[1] * s, b4[2] * s, b4[3] * s};
-    split8(v8, h[m], l[m]);
-  }
-}
-
-__device__ __forceinline__ void split16(const f32x16& v, bf16x8 (&h)[2], bf16x8 (&l)[2]) {
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const float v8[8] = {v[8 * m], v[8 * m + 1], v[8 * m + 2], v[8 * m + 3], v[8 * m + 4], v[8 * m + 5], v[8 * m + 6], v[8 * m + 7]};
-    split8(v8, h[m], l[m]);
-  }
-}
-
-__device__ __forceinline__ void store16(float* p, const f32x16& a, float s) {  // register 4g+e <-> dim 8g + 4hi + e (p offset by 4hi)
-#pragma unroll
-  for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4*>(p + 8 * g) = f32x4{a[4 * g] * s, a[4 * g + 1] * s, a[4 * g + 2] * s, a[4 * g + 3] * s};
-}
-
-// XCD-aware 1-D grid as in attention_v2.hip: id -> (xcd = id % 8, row block = (id / 8) % nblk, (batch, head) = 8 (id / (8 nblk)) + xcd)
-__device__ __forceinline__ bool map_work(int nblk, int BH, int& bh, int& blk) {
-  const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-  bh = 8 * (jj / nblk) + xcd;
-  blk = jj % nblk;
-  return bh < BH;
-}
-
 template <bool HAVE_LSE>
 __global__ void __launch_bounds__(256, 3) attn32_bwd_dq_v2_kernel(BwdArgs2 a) {
   __shared__ __attribute__((aligned(16))) float ring[RING * KSLOT_FLOATS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hi = lane >> 5;
-  const int nqb = ((a.L + 31) / 32 + 3) / 4;
   int bh, blk;
-  if (!map_work(nqb, a.B * a.H, bh, blk)) return;
+  if (!map_work(row_blocks(a.L), a.B * a.H, bh, blk)) return;
   const int h = bh % a.H, b = bh / a.H;
   const int qrow = (blk * 4 + wave) * 32 + j;
   const int qc = qrow < a.L ? qrow : a.L - 1;
   const int nt = (a.S + 31) / 32;
-  const char* slots = a.blob + ((size_t)b * a.H + h) * nt * KSLOT_BYTES;
+  const char* slots = a.blob + tile_slot(b, a.H, h, nt, 0) * KSLOT_BYTES;
   dma_tile<3, KSLOT_BYTES>(slots, 0, ring, wave, lane);
   if (nt > 1) dma_tile<3, KSLOT_BYTES>(slots, 1, ring, wave, lane);
   bf16x8 qh[2], ql[2], doh[2], dol[2];
@@ -174,11 +144,11 @@ __global__ void __launch_bounds__(256, 3) attn32_bwd_dq_v2_kernel(BwdArgs2 a) {
     __builtin_amdgcn_s_barrier();  // everybody's pieces of tile t landed; nobody reads tile t-1 any more
     if (t + 2 < ntiles) dma_tile<3, KSLOT_BYTES>(slots, t + 2, ring, wave, lane);
   };
-  auto mask_tail = [&](int t, f32x16& sc) {
+  auto mask_last = [&](int t, f32x16& sc) {
     if (t == nt - 1 && (a.S & 31)) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= a.S) sc[r] = -__builtin_inff();
+        if (t * 32 + nrow(r, hi) >= a.S) sc[r] = -__builtin_inff();
     }
   };
   // ---- pass 1: log-sum-exp of each query (log2 domain), lazy running maximum as in the forward kernel -- unless the forward pass
@@ -197,7 +167,7 @@ __global__ void __launch_bounds__(256, 3) attn32_bwd_dq_v2_kernel(BwdArgs2 a) {
     acquire(t, nt);
     const u32x4* s4 = reinterpret_cast<const u32x4*>(ring + (t % RING) * KSLOT_FLOATS) + lane;
     f32x16 sc = mma_rows(s4, 0, qh, ql, negm);
-    mask_tail(t, sc);
+    mask_last(t, sc);
     float mx = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
 #pragma unroll
     for (int r = 4; r < 16; r += 4) mx = fmaxf(mx, fmaxf(fmaxf(sc[r], sc[r + 1]), fmaxf(sc[r + 2], sc[r + 3])));
@@ -240,7 +210,7 @@ __global__ void __launch_bounds__(256, 3) attn32_bwd_dq_v2_kernel(BwdArgs2 a) {
     acquire(t, nt);
     const u32x4* s4 = reinterpret_cast<const u32x4*>(ring + (t % RING) * KSLOT_FLOATS) + lane;
     f32x16 sc = mma_rows(s4, 0, qh, ql, c_lse);          // log2 P
-    mask_tail(t, sc);
+    mask_last(t, sc);
     const f32x16 dp = mma_rows(s4, 4, doh, dol, c_d);    // dP - D
 #pragma unroll
     for (int i = 0; i < 16; ++i) sc[i] = __builtin_amdgcn_exp2f(sc[i]) * dp[i];  // dS
@@ -254,14 +224,13 @@ __global__ void __launch_bounds__(256, 3) attn32_bwd_dq_v2_kernel(BwdArgs2 a) {
 __global__ void __launch_bounds__(256, 3) attn32_bwd_dkv_v2_kernel(BwdArgs2 a) {
   __shared__ __attribute__((aligned(16))) float ring[RING * QSLOT_FLOATS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hi = lane >> 5;
-  const int nkb = ((a.S + 31) / 32 + 3) / 4;
   int bh, blk;
-  if (!map_work(nkb, a.B * a.H, bh, blk)) return;
+  if (!map_work(row_blocks(a.S), a.B * a.H, bh, blk)) return;
   const int h = bh % a.H, b = bh / a.H;
   const int krow = (blk * 4 + wave) * 32 + j;
   const int kc = krow < a.S ? krow : a.S - 1;
   const int nt = (a.L + 31) / 32;
-  const char* slots = a.blob + ((size_t)b * a.H + h) * nt * QSLOT_BYTES;
+  const char* slots = a.blob + tile_slot(b, a.H, h, nt, 0) * QSLOT_BYTES;
   auto dma = [&](int t) {
     dma_tile<4, QSLOT_BYTES>(slots, t, ring, wave, lane);
     if (wave == 0) {  // the scalar piece (only 256 bytes are meaningful; one more 1 KiB instruction of this wavefront)
@@ -339,15 +308,15 @@ int nm_internal_attn_bwd_v2(const float* q, const float* k, const float* v, cons
   char* qblob = kblob + (size_t)B * heads * ntk * KSLOT_BYTES;
   float* nlse = (float*)(((uintptr_t)(qblob + (size_t)B * heads * ntq * QSLOT_BYTES) + 255) & ~(uintptr_t)255);
   float* nd = nlse + (size_t)B * heads * L;
-  const long long gq = (long long)((B * heads + 7) / 8) * 8 * ((ntq + 3) / 4), gk = (long long)((B * heads + 7) / 8) * 8 * ((ntk + 3) / 4);
-  if (gq > 0x7fffffffLL || gk > 0x7fffffffLL) return NM_ERR_UNSUPPORTED;
+  unsigned gq, gk;
+  if (!map_work_grid(B * heads, row_blocks(L), gq) || !map_work_grid(B * heads, row_blocks(S), gk)) return NM_ERR_UNSUPPORTED;
   if (nlse_fwd) nlse = const_cast<float*>(nlse_fwd);  // (read only on this path: the dq kernel loads it, the query-tile pre-split copies it)
   BwdArgs2 a{q, o, d_o, ldq, ldo, lddo, k, v, ldk, ldv, dq, dk, dv, lddq, lddk, lddv, L, S, heads, B, scale, kblob, nlse, nd};
   bwd_presplit_kernel<<<dim3(ntk, heads, B), 256, 0, s>>>(k, v, ldk, ldv, S, heads, 3, KSLOT_BYTES, nullptr, nullptr, kblob);
-  if (nlse_fwd) attn32_bwd_dq_v2_kernel<true><<<(unsigned)gq, 256, 0, s>>>(a);
-  else attn32_bwd_dq_v2_kernel<false><<<(unsigned)gq, 256, 0, s>>>(a);
+  if (nlse_fwd) attn32_bwd_dq_v2_kernel<true><<<gq, 256, 0, s>>>(a);
+  else attn32_bwd_dq_v2_kernel<false><<<gq, 256, 0, s>>>(a);
   bwd_presplit_kernel<<<dim3(ntq, heads, B), 256, 0, s>>>(q, d_o, ldq, lddo, L, heads, 4, QSLOT_BYTES, nlse, nd, qblob);
   a.blob = qblob;
-  attn32_bwd_dkv_v2_kernel<<<(unsigned)gk, 256, 0, s>>>(a);
+  attn32_bwd_dkv_v2_kernel<<<gk, 256, 0, s>>>(a);
   return nm_launch_status();
 }

@@ -14,7 +14,7 @@
 //   * K / V^T operands are packed once per call into 4 KiB slots of 64 keys = {K, V^T} x {sub-tile of 32 keys} x {k-step} x
 //     64 lanes x 8 bytes, streamed by LDS DMA (one 1 KiB instruction per wavefront and slot) into a 4-slot ring three slots
 //     ahead; the row sum of the probabilities is taken in fp32 before quantisation.
-#include "common.h"
+#include "attention_tile.h"
 
 namespace {
 
@@ -66,12 +66,11 @@ __global__ void __launch_bounds__(256) kv_prepack_fp8_kernel(const float* __rest
   const int tid = threadIdx.x, op = tid >> 6, lane = tid & 63, r = lane & 31, half = lane >> 5;
   const int which = op >> 1, sub = op & 1;
   const float sc = pow2_scale(__uint_as_float(amax[((size_t)b * H + h) * 2 + which]));
-  long* slot = reinterpret_cast<long*>(slots + (((size_t)b * H + h) * nt + t) * F8_SLOT_BYTES);
+  long* slot = reinterpret_cast<long*>(slots + tile_slot(b, H, h, nt, t) * F8_SLOT_BYTES);
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     float v8[8];
-    if (which == 0) {
-      // K sub-tile as A operand of S^T = K . Q^T: row = key r, k-slots = dims 16 ks + 8 half + i
+    if (which == 0) {  // "rows" gather of kv_presplit_kernel (attention_v2.hip), per 32-key sub-tile
       const int key = t * 64 + sub * 32 + r;
       if (key < S) {
         const float* p = k + ((size_t)b * S + key) * ldk + h * 32 + 16 * ks + 8 * half;
@@ -81,9 +80,7 @@ __global__ void __launch_bounds__(256) kv_prepack_fp8_kernel(const float* __rest
 #pragma unroll
         for (int i = 0; i < 8; ++i) v8[i] = 0.f;
       }
-    } else {
-      // V^T sub-tile as A operand of O^T += V^T . P^T: row = dim r, k-slot i of step ks <-> key (i&3) + 16 ks + 8 (i>>2) + 4 half
-      // (= the key held by accumulator register 8 ks + i of a lane in half `half` after the first MFMA)
+    } else {  // its "transposed, accumulator-permuted" gather
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int key = t * 64 + sub * 32 + (i & 3) + 16 * ks + 8 * (i >> 2) + 4 * half;
@@ -104,23 +101,24 @@ __device__ __forceinline__ void dma_slot(const char* slots, int t, float* ring, 
   __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
 }
 
-// Grid / work mapping as attn32_v3_kernel (XCD-aware: all query blocks of one (batch, head) on one XCD).
+// Grid / work mapping: map_work (XCD-aware: all query blocks of one (batch, head) on one XCD).
 __global__ void __launch_bounds__(256, 4) attn32_fp8_kernel(const float* __restrict__ q, int ldq, const unsigned* __restrict__ amax,
                                                           const char* __restrict__ blob, int L, int S, int H, int B, float scale,
                                                           float* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) float ring[F8_RING * F8_SLOT_FLOATS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hi = lane >> 5;
-  const int nqb = ((L + 31) / 32 + 3) / 4;
+  // map_work (attention_tile.h), written out like the row epilogue below: as calls they reorder this kernel's prologue and epilogue
+  const int nqb = row_blocks(L);
   const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
   const int bh = 8 * (jj / nqb) + xcd;
-  if (bh >= B * H) return;
+  if (bh >= B * H) return;  // (whole workgroup: B*H is padded to a multiple of 8)
   const int h = bh % H, b = bh / H;
   const int qt = (jj % nqb) * 4 + wave;
   const int C = H * 32;
   const int qrow = qt * 32 + j;
   const int qc = qrow < L ? qrow : L - 1;
   const int nt = (S + 63) / 64;
-  const char* slots = blob + ((size_t)b * H + h) * nt * F8_SLOT_BYTES;
+  const char* slots = blob + tile_slot(b, H, h, nt, 0) * F8_SLOT_BYTES;
   dma_slot(slots, 0, ring, wave, lane);
   if (nt > 1) dma_slot(slots, 1, ring, wave, lane);
   if (nt > 2) dma_slot(slots, 2, ring, wave, lane);
@@ -129,20 +127,13 @@ __global__ void __launch_bounds__(256, 4) attn32_fp8_kernel(const float* __restr
   long qf[2];
   float dsc;
   {
-    const float qs = scale * 1.44269504088896340736f;
-    const float* qp = q + ((size_t)b * L + qc) * ldq + h * 32 + 8 * hi;
     float v8[2][8];
+    load_row(q + ((size_t)b * L + qc) * ldq + h * 32 + 8 * hi, scale * 1.44269504088896340736f, v8);
     float am = 0.f;
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const f32x4 a4 = *reinterpret_cast<const f32x4*>(qp + 16 * m), b4 = *reinterpret_cast<const f32x4*>(qp + 16 * m + 4);
-      const float w8[8] = {a4[0] * qs, a4[1] * qs, a4[2] * qs, a4[3] * qs, b4[0] * qs, b4[1] * qs, b4[2] * qs, b4[3] * qs};
+    for (int m = 0; m < 2; ++m)
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        v8[m][i] = w8[i];
-        am = fmaxf(am, fabsf(w8[i]));
-      }
-    }
+      for (int i = 0; i < 8; ++i) am = fmaxf(am, fabsf(v8[m][i]));
     am = fmaxf(am, nm_shfl_xor32(am));  // the query's other 16 dims live in the other wavefront half
     const float sq = pow2_scale(am);
 #pragma unroll
@@ -254,9 +245,8 @@ extern "C" int nm_attention_fp8(const float* q, const float* k, const float* v, 
   const int nt = (S + 63) / 64;
   absmax_kernel<<<dim3(nt, B), 32 * heads, 0, s>>>(k, v, ldk, ldv, S, heads, amax);
   kv_prepack_fp8_kernel<<<dim3(nt, heads, B), 256, 0, s>>>(k, v, ldk, ldv, S, heads, amax, slots);
-  const int nqb = ((L + 31) / 32 + 3) / 4;
-  const long long grid = (long long)((B * heads + 7) / 8) * 8 * nqb;
-  if (grid > 0x7fffffffLL) return NM_ERR_UNSUPPORTED;
-  attn32_fp8_kernel<<<(unsigned)grid, 256, 0, s>>>(q, ldq, amax, slots, L, S, heads, B, scale, out);
+  unsigned grid;
+  if (!map_work_grid(B * heads, row_blocks(L), grid)) return NM_ERR_UNSUPPORTED;
+  attn32_fp8_kernel<<<grid, 256, 0, s>>>(q, ldq, amax, slots, L, S, heads, B, scale, out);
   return nm_launch_status();
 }

@@ -1,17 +1,11 @@
-// Flash-style softmax attention for head_dim 32 on the bf16 matrix cores (hi/lo operand splitting), second generation.
-//
-// attn32_bf16x3_kernel (attention.hip) re-splits every K/V tile in every workgroup (38 times for 4800 queries) and
-// spends more VALU cycles on staging and on the online-softmax bookkeeping than the matrix cores need for the two
-// contractions.  Here
-//   * K and V are split ONCE per call (kv_presplit_kernel) into ready-made MFMA A operands: per (batch, head, 32-key tile)
-//     one 8 KiB slot = {K, V^T} x {dims/keys 0-15, 16-31} x {hi, lo} x 64 lanes x 8 bf16, V^T key-permuted so that a
-//     lane's 8 consecutive bf16 are exactly the 8 K-slots the probabilities occupy after the first MFMA;
-//   * the slots are streamed into a 4-slot LDS ring with global_load_lds two tiles ahead (no VGPRs, no VALU), one
-//     counted s_waitcnt + one s_barrier per tile;
-//   * "lazy" running maximum: the scores come out of the MFMA already shifted (C operand = -m), m is only raised when a
-//     score exceeds it by more than 2^8 (wave-uniform branch), so the common tile costs max + exp2 + sum + split only.
-// Arithmetic and accuracy are those of the first generation (w_hi*x_hi + w_hi*x_lo + w_lo*x_hi, fp32 accumulate).
-#include "bf16x3.h"
+// Flash-style softmax attention for head_dim 32 on the bf16 matrix cores with hi/lo operand splitting (w_hi*x_hi + w_hi*x_lo +
+// w_lo*x_hi, fp32 accumulate).
+//   * kv_presplit_kernel splits K and V ONCE per call into ready-made MFMA A operands, one 8 KiB slot per (batch, head, 32-key
+//     tile) in the layout attention_tile.h names (nm_linear_qkv_bf16x3 writes the same slots straight from its projection);
+//   * attn32_v3_kernel streams the slots into a 4-slot LDS ring with global_load_lds (no VGPRs, no VALU), one counted s_waitcnt +
+//     one s_barrier per tile, and keeps a "lazy" running maximum: the scores come out of the MFMA already shifted (C operand = -m).
+#include "attention_tile.h"
+#include "internal.h"
 
 namespace {
 
@@ -26,8 +20,9 @@ __global__ void __launch_bounds__(256) kv_presplit_kernel(const float* __restric
   const int t = blockIdx.x, h = blockIdx.y, b = blockIdx.z, nt = gridDim.x;
   const int tid = threadIdx.x, which = tid >> 7, ks = (tid >> 6) & 1, lane = tid & 63, r = lane & 31, half = lane >> 5;
   float v8[8];
-  if (which == 0) {
-    // K tile as A operand of S^T = K . Q^T: row = key r, k-slots = dims 16 ks + 8 half + i
+  // (the two gathers are written out in each of kv_presplit_kernel, kv_prepack_fp8_kernel and bwd_presplit_kernel: as shared functions they changed the kernels' code and register counts)
+  if (which == AT_K) {
+    // "rows": K tile as A operand of S^T = K . Q^T: row = key r, k-slots = dims 16 ks + 8 half + i
     const int key = t * 32 + r;
     if (key < S) {
       const float* p = k + ((size_t)b * S + key) * ldk + h * 32 + 16 * ks + 8 * half;
@@ -38,8 +33,8 @@ __global__ void __launch_bounds__(256) kv_presplit_kernel(const float* __restric
       for (int i = 0; i < 8; ++i) v8[i] = 0.f;
     }
   } else {
-    // V^T tile as A operand of O^T += V^T . P^T: row = dim r, k-slot i of step ks <-> key (i&3) + 16 ks + 8 (i>>2) + 4 half
-    // (= the key held by accumulator register 8 ks + i of a lane in half `half` after the first MFMA)
+    // "transposed, accumulator-permuted": V^T tile as A operand of O^T += V^T . P^T: row = dim r, k-slot i of step ks <-> key
+    // nrow(8 ks + i, half) = (i&3) + 16 ks + 8 (i>>2) + 4 half, the key held by accumulator register 8 ks + i after the first MFMA
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int key = t * 32 + (i & 3) + 16 * ks + 8 * (i >> 2) + 4 * half;
@@ -48,26 +43,23 @@ __global__ void __launch_bounds__(256) kv_presplit_kernel(const float* __restric
   }
   bf16x8 hi8, lo8;
   split8(v8, hi8, lo8);
-  u32x4* slot = reinterpret_cast<u32x4*>(blob + (((size_t)b * H + h) * nt + t) * AT_SLOT_BYTES);
-  const int op = which * 4 + ks * 2;
-  slot[(op + 0) * 64 + lane] = __builtin_bit_cast(u32x4, hi8);
-  slot[(op + 1) * 64 + lane] = __builtin_bit_cast(u32x4, lo8);
+  u32x4* slot = reinterpret_cast<u32x4*>(blob + tile_slot(b, H, h, nt, t) * AT_SLOT_BYTES);
+  slot[at_piece(which, ks, AT_HI) * 64 + lane] = __builtin_bit_cast(u32x4, hi8);
+  slot[at_piece(which, ks, AT_LO) * 64 + lane] = __builtin_bit_cast(u32x4, lo8);
 }
 
-// 1-D grid of ceil(B*H / 8) * 8 * ceil(L/128) workgroups, block 256 = 4 wavefronts x 32 queries.
-// XCD-aware work mapping: consecutive workgroup ids go round robin to the 8 XCDs (each with its own 4 MiB L2), so
-// id -> (xcd = id % 8, query block = (id / 8) % nqb, (batch, head) = 8 * (id / (8 nqb)) + xcd): all query blocks of one
+// 1-D grid and work mapping of map_work (attention_tile.h), block 256 = 4 wavefronts x 32 queries: all query blocks of one
 // (batch, head) run on ONE XCD, whose L2 then holds the 1.2 MB of K/V slots they all stream (with the natural
 // blockIdx.{x,y,z} order ~20 different (batch, head) pairs were live per XCD and the slots came back from the fabric
 // nine times over: 358 MB of FETCH_SIZE per 4-query launch).
-// Third generation: the same arithmetic, software-pipelined INSIDE the wavefront.  In the second generation a tile was a strict
+// Software-pipelined INSIDE the wavefront.  Before, a tile was a strict
 // chain -- 6 dependent QK^T MFMAs -> ~95 VALU instructions of softmax -> 6 dependent PV MFMAs -- so the matrix pipe only
 // worked while some OTHER wavefront of the SIMD happened to be in its VALU phase (measured: one tile per 754 cycles and SIMD
 // against 384 MFMA and ~430 VALU cycles).  Here iteration t issues the QK^T MFMAs of tile t+1 before the softmax of tile t,
 // so they run underneath that VALU work, and the running maximum is not tracked per tile any more: the scores come out of the
 // MFMA shifted by the current maximum as before, but it is only raised when a tile's probabilities get near the fp32 range
 // (detected on the row sum the loop needs anyway; the first tile always sets it) -- the per-tile max / swap / compare /
-// branch of the second generation is gone from the common path.  Ring: tile t+3 is requested while tile t+1's keys and
+// branch of that form is gone from the common path.  Ring: tile t+3 is requested while tile t+1's keys and
 // tile t's values are read (4 slots).
 constexpr float AT_BIG = 1.2676506e30f;  // 2^100: a tile whose per-lane probability sum reaches this raises the maximum
 
@@ -75,7 +67,8 @@ __global__ void __launch_bounds__(256, 4) attn32_v3_kernel(const float* __restri
                                                          int S, int H, int B, float scale, float* __restrict__ out, float* __restrict__ nlse_out) {
   __shared__ __attribute__((aligned(16))) float ring[AT_RING * AT_SLOT_FLOATS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hi = lane >> 5;
-  const int nqb = ((L + 31) / 32 + 3) / 4;
+  // map_work (attention_tile.h), written out like the row epilogue below: as calls they reorder this kernel's prologue and epilogue
+  const int nqb = row_blocks(L);
   const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
   const int bh = 8 * (jj / nqb) + xcd;
   if (bh >= B * H) return;  // (whole workgroup: B*H is padded to a multiple of 8)
@@ -85,7 +78,7 @@ __global__ void __launch_bounds__(256, 4) attn32_v3_kernel(const float* __restri
   const int qrow = qt * 32 + j;
   const int qc = qrow < L ? qrow : L - 1;
   const int nt = (S + 31) / 32;
-  const char* slots = blob + ((size_t)b * H + h) * nt * AT_SLOT_BYTES;
+  const char* slots = blob + tile_slot(b, H, h, nt, 0) * AT_SLOT_BYTES;
   dma_slot_8k<AT_RING>(slots, 0, ring, wave, lane);
   if (nt > 1) dma_slot_8k<AT_RING>(slots, 1, ring, wave, lane);
   if (nt > 2) dma_slot_8k<AT_RING>(slots, 2, ring, wave, lane);
@@ -109,8 +102,8 @@ __global__ void __launch_bounds__(256, 4) attn32_v3_kernel(const float* __restri
     f32x16 r = c;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
-      const bf16x8 kh = __builtin_bit_cast(bf16x8, s4[(2 * m + 0) * 64]);
-      const bf16x8 kl = __builtin_bit_cast(bf16x8, s4[(2 * m + 1) * 64]);
+      const bf16x8 kh = __builtin_bit_cast(bf16x8, s4[at_piece(AT_K, m, AT_HI) * 64]);
+      const bf16x8 kl = __builtin_bit_cast(bf16x8, s4[at_piece(AT_K, m, AT_LO) * 64]);
       r = MFMA_BF16(kh, qh[m], r);
       r = MFMA_BF16(kh, ql[m], r);
       r = MFMA_BF16(kl, qh[m], r);
@@ -129,10 +122,11 @@ __global__ void __launch_bounds__(256, 4) attn32_v3_kernel(const float* __restri
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // everybody's pieces of tile t+1 landed; nobody reads tile t-1 any more
     if (t + 3 < nt) dma_slot_8k<AT_RING>(slots, t + 3, ring, wave, lane);
+    // (load_split and split16 of attention_tile.h stay written out above and below: as calls they changed this loop's schedule)
     if (t == nt - 1 && (S & 31)) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= S) sc[r] = -__builtin_inff();
+        if (t * 32 + nrow(r, hi) >= S) sc[r] = -__builtin_inff();
     }
     // ONE basic block: the 6 (dependent) QK^T MFMAs of the next tile, each followed by a share of this tile's exp2 / row-sum
     // VALU work -- the in-order front end reaches the next MFMA just as the previous one leaves the pipe.  (Last iteration:
@@ -182,8 +176,8 @@ __global__ void __launch_bounds__(256, 4) attn32_v3_kernel(const float* __restri
     const u32x4* s4 = reinterpret_cast<const u32x4*>(ring + (t & (AT_RING - 1)) * AT_SLOT_FLOATS) + lane;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
-      const bf16x8 vh = __builtin_bit_cast(bf16x8, s4[(4 + 2 * m + 0) * 64]);
-      const bf16x8 vl = __builtin_bit_cast(bf16x8, s4[(4 + 2 * m + 1) * 64]);
+      const bf16x8 vh = __builtin_bit_cast(bf16x8, s4[at_piece(AT_VT, m, AT_HI) * 64]);
+      const bf16x8 vl = __builtin_bit_cast(bf16x8, s4[at_piece(AT_VT, m, AT_LO) * 64]);
       o = MFMA_BF16(vh, ph[m], o);
       o = MFMA_BF16(vh, pl[m], o);
       o = MFMA_BF16(vl, ph[m], o);
@@ -209,9 +203,11 @@ __global__ void __launch_bounds__(256, 4) attn32_v3_kernel(const float* __restri
   }
 }
 
-void attn32_launch(unsigned grid, hipStream_t s, const float* q, int ldq, const char* blob, int L, int S, int H, int B, float scale, float* out,
-                   float* nlse_out = nullptr) {
+int attn32_launch(hipStream_t s, const float* q, int ldq, const char* blob, int L, int S, int H, int B, float scale, float* out, float* nlse_out) {
+  unsigned grid;
+  if (!map_work_grid(B * H, row_blocks(L), grid)) return NM_ERR_UNSUPPORTED;
   attn32_v3_kernel<<<grid, 256, 0, s>>>(q, ldq, blob, L, S, H, B, scale, out, nlse_out);
+  return nm_launch_status();
 }
 
 }  // namespace
@@ -225,20 +221,12 @@ extern "C" int nm_attention_presplit(const float* q, int ldq, const void* kv_slo
                                      nmStream_t stream) {
   NM_CHECK_ARG(q && kv_slots && out && B > 0 && L > 0 && S > 0 && heads > 0);
   if (ldq < 32 * heads || ldq % 4 || B > 65535 || heads > 65535) return NM_ERR_ARG;
-  const int nqb = ((L + 31) / 32 + 3) / 4;
-  const long long grid = (long long)((B * heads + 7) / 8) * 8 * nqb;
-  if (grid > 0x7fffffffLL) return NM_ERR_UNSUPPORTED;
-  attn32_launch((unsigned)grid, (hipStream_t)stream, q, ldq, (const char*)kv_slots, L, S, heads, B, scale, out);
-  return nm_launch_status();
+  return attn32_launch((hipStream_t)stream, q, ldq, (const char*)kv_slots, L, S, heads, B, scale, out, nullptr);
 }
 
 int nm_internal_attn_v2(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, int B, int L, int S, int heads,
                         float scale, void* workspace, float* out, hipStream_t s, float* nlse_out) {
   const int nt = (S + 31) / 32;
   kv_presplit_kernel<<<dim3(nt, heads, B), 256, 0, s>>>(k, v, ldk, ldv, S, heads, (char*)workspace);
-  const int nqb = ((L + 31) / 32 + 3) / 4;
-  const long long grid = (long long)((B * heads + 7) / 8) * 8 * nqb;
-  if (grid > 0x7fffffffLL) return NM_ERR_UNSUPPORTED;
-  attn32_launch((unsigned)grid, s, q, ldq, (const char*)workspace, L, S, heads, B, scale, out, nlse_out);
-  return nm_launch_status();
+  return attn32_launch(s, q, ldq, (const char*)workspace, L, S, heads, B, scale, out, nlse_out);
 }

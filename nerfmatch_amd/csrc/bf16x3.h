@@ -1,15 +1,12 @@
 // The split-bf16 vocabulary of the matrix-core kernels: every fp32 operand is two bf16 values (x = hi + lo) and a product is
 // w_hi x_hi + w_hi x_lo + w_lo x_hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (gemm_bf16.hip has the error budget).
-// Vector types, the hi / lo split, the accumulator layout and its re-packing, the 8 KiB weight-slot DMA, the fast exact-erf GELU.
+// Vector types, the hi / lo split, the re-packing of the accumulator layout (nrow, common.h), the 8 KiB weight-slot DMA, the fast exact-erf GELU.
 #pragma once
 #include "common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-// accumulator layout of a 32x32 MFMA block: register r of a lane in half `hi` holds row (A side) / feature nrow(r, hi) of the block
-__host__ __device__ __forceinline__ constexpr int nrow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // x = hi + lo with hi, lo bf16 (round to nearest even): 16 bits of mantissa survive.
 __device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {

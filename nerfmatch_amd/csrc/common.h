@@ -41,6 +41,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
+// accumulator layout of a 32x32 MFMA block: register r of a lane in half `hi` holds row (A side) / feature nrow(r, hi) of the block
+__host__ __device__ __forceinline__ constexpr int nrow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+
 // The build uses -ffp-contract=off: every fused multiply-add below is written explicitly so that the
 // plain mul/add sequences of the reference's elementwise torch ops are reproduced op for op.
 #define NM_FMA(a, b, c) __builtin_fmaf((a), (b), (c))

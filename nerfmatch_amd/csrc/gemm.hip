@@ -6,7 +6,7 @@
 // owns a 32-row x (32*NB)-column output tile: tokens on the A side (rows of D), output features on the B side
 // (columns of D = lanes), so every store instruction writes 128 contiguous bytes of one output row.
 // The same kernel (MODE_SIM) produces the dual-softmax similarity matrix with its scale / mask epilogue.
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -128,7 +128,6 @@ extern "C" int nm_linear(const float* x, const float* w, const float* bias, cons
   return launch_gemm<MODE_LINEAR>(a, (hipStream_t)stream);
 }
 
-// internal (used by match.hip): sim[M,N] = mask_fill(scale * im[M,C] . pt[N,C]^T)
 int nm_internal_sim(const float* im, const float* pt, int M, int N, int C, float scale, const uint8_t* im_mask,
                     const uint8_t* pt_mask, float* sim, hipStream_t s) {
   GemmArgs a{};

@@ -17,7 +17,8 @@
 //     with coalesced writes).  The epilogue therefore transposes the tile through the (by then idle) LDS ring, half a
 //     tile at a time, and writes 256-byte row segments; `pre` / residual / `gate` are read in the same coalesced layout,
 //     the bias is the accumulators' starting value.
-#include "bf16x3.h"
+#include "attention_tile.h"
+#include "internal.h"
 #include <utility>
 
 namespace {
@@ -198,9 +199,9 @@ __device__ __forceinline__ void epilogue_keys(const f32x16 (&acc)[4], char* slot
                         __builtin_bit_cast(unsigned short, h[2]), __builtin_bit_cast(unsigned short, h[3])};
       const u16x4 lv = {__builtin_bit_cast(unsigned short, l[0]), __builtin_bit_cast(unsigned short, l[1]),
                         __builtin_bit_cast(unsigned short, l[2]), __builtin_bit_cast(unsigned short, l[3])};
-      char* base = slot0 + ob * head_stride + (size_t)(((q >> 1) * 2) * 64 + (q & 1) * 32 + r) * 16 + 8 * hi;
+      char* base = slot0 + ob * head_stride + (size_t)(at_piece(AT_K, q >> 1, AT_HI) * 64 + (q & 1) * 32 + r) * 16 + 8 * hi;
       *reinterpret_cast<u16x4*>(base) = hv;
-      *reinterpret_cast<u16x4*>(base + 64 * 16) = lv;
+      *reinterpret_cast<u16x4*>(base + AT_PIECE_BYTES) = lv;  // the lo piece follows its hi piece
     }
 }
 
@@ -220,9 +221,9 @@ __device__ __forceinline__ void epilogue_values(const f32x16 (&acc)[4], char* sl
         h8[i] = h;
         l8[i] = (__bf16)(v - (float)h);
       }
-      u32x4* dst = reinterpret_cast<u32x4*>(slot0 + ob * head_stride) + (4 + ks * 2) * 64 + lane;
+      u32x4* dst = reinterpret_cast<u32x4*>(slot0 + ob * head_stride) + at_piece(AT_VT, ks, AT_HI) * 64 + lane;
       dst[0] = __builtin_bit_cast(u32x4, h8);
-      dst[64] = __builtin_bit_cast(u32x4, l8);
+      dst[64] = __builtin_bit_cast(u32x4, l8);  // the lo piece follows its hi piece
     }
 }
 
@@ -343,8 +344,8 @@ __global__ void __launch_bounds__(256, 4) gemm_bf16x3_kernel(GemmBArgs a) {
     if (m0 >= a.M) return;
     const int b = m0 / a.S, t = (m0 % a.S) >> 5, nt = a.S >> 5;
     const int head0 = (chunk * GB_COLS - a.n_q - (kind == 2 ? 32 * a.H : 0)) >> 5;
-    const size_t head_stride = (size_t)nt * 8192;
-    char* slot0 = a.kv_blob + (((size_t)b * a.H + head0) * nt + t) * 8192;
+    const size_t head_stride = (size_t)nt * NM_SLOT8K_BYTES;  // slot0: tile_slot(b, H, head0, nt, t)
+    char* slot0 = a.kv_blob + (((size_t)b * a.H + head0) * nt + t) * NM_SLOT8K_BYTES;
     if (kind == 1) epilogue_keys(acc, slot0, head_stride, lane);
     else epilogue_values(acc, slot0, head_stride, lane);
     return;
@@ -492,8 +493,8 @@ __global__ void __launch_bounds__(256, 1) gemm_bf16x3_small_kernel(GemmBArgs a) 
     if (m0 >= a.M) return;
     const int b = m0 / a.S, t = (m0 % a.S) >> 5, nt = a.S >> 5;
     const int head0 = (chunk * GB_COLS - a.n_q - (kind == 2 ? 32 * a.H : 0)) >> 5;
-    const size_t head_stride = (size_t)nt * 8192;
-    char* slot0 = a.kv_blob + (((size_t)b * a.H + head0) * nt + t) * 8192;
+    const size_t head_stride = (size_t)nt * NM_SLOT8K_BYTES;  // slot0: tile_slot(b, H, head0, nt, t)
+    char* slot0 = a.kv_blob + (((size_t)b * a.H + head0) * nt + t) * NM_SLOT8K_BYTES;
     if (kind == 1) epilogue_keys(acc, slot0, head_stride, lane);
     else epilogue_values(acc, slot0, head_stride, lane);
     return;
@@ -573,8 +574,6 @@ extern "C" int nm_linear_pack_t_bf16x3(const float* w, int N, int K, void* blob,
   return nm_launch_status();
 }
 
-// internal (used by match.hip): sim[M,N] = mask_fill(scale * im[M,C] . pt[N,C]^T) on the split-bf16 path; pt is packed
-// into `blob` (nm_linear_blob_bytes_bf16x3(N, C) bytes of workspace) first.  N % 8 == 0, C % 8 == 0.
 int nm_internal_sim_bf16x3(const float* im, const float* pt, int M, int N, int C, float scale, const uint8_t* im_mask,
                            const uint8_t* pt_mask, float* sim, void* blob, hipStream_t s) {
   if (N % 8 != 0 || C % 8 != 0) return NM_ERR_UNSUPPORTED;

@@ -13,12 +13,7 @@
 // `conf == conf.max()`; against the reference's softmax * softmax the values differ by rounding only (<= 3e-7 relative).
 // Algorithmic HBM bytes: 8*M*N when conf is returned (1 write + 1 read); this version moves 5 passes over
 // sim, read in 16-byte pieces.
-#include "common.h"
-
-int nm_internal_sim(const float* im, const float* pt, int M, int N, int C, float scale, const uint8_t* im_mask,
-                    const uint8_t* pt_mask, float* sim, hipStream_t s);
-int nm_internal_sim_bf16x3(const float* im, const float* pt, int M, int N, int C, float scale, const uint8_t* im_mask,
-                           const uint8_t* pt_mask, float* sim, void* blob, hipStream_t s);
+#include "internal.h"
 
 namespace {
 

@@ -138,9 +138,6 @@ __device__ __forceinline__ int launder(int v) {
   return v;
 }
 
-// neuron index inside a 32-block held by (register r, half hi)
-__host__ __device__ __forceinline__ constexpr int nrow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
 // One 128-sample tile (`bid` = tile index; `sm` = the workgroup's single LDS object)
 __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, float* const sm) {
   float* const sm_small = sm;
