@@ -542,6 +542,10 @@ int nm_linear_wgrad_bf16x3(const float* dy, const float* x, int M, int N, int K,
                            size_t workspace_bytes, nmStream_t stream);
 /* bias gradient out[N] (+)= sum_m dy[m,:] (float atomics: order-dependent in the last bits). */
 int nm_col_sum(const float* dy, int M, int N, int accumulate, float* out, nmStream_t stream);
+/* nm_col_sum with the row chunks' partial sums written to `workspace` (nm_col_sum_workspace_bytes(M,N) bytes, else NM_ERR_WORKSPACE) and added
+ * in a fixed order: the same bits on every run. */
+size_t nm_col_sum_workspace_bytes(int M, int N);
+int nm_col_sum_ordered(const float* dy, int M, int N, int accumulate, float* out, void* workspace, size_t workspace_bytes, nmStream_t stream);
 /* exact-erf GELU (nn.GELU(), modules/attention.py:136-154) as a separate pass over the pre-activations u (training keeps
  * u for the backward pass), and du = dh * gelu'(u).  n % 4 == 0. */
 int nm_gelu(const float* u, size_t n, float* h, nmStream_t stream);
@@ -553,6 +557,12 @@ int nm_relu_bwd(const float* h, const float* dh, size_t n, float* du, nmStream_t
  * (frozen parameters: the matching term of the iNeRF refinement, nerfmatch_evaluator.py:429-441).  dim in {64,128,256,512}. */
 int nm_layernorm_bwd(const float* x, const float* gamma, const float* dy, int rows, int dim, float eps, float* dx,
                      float* dgamma, float* dbeta, nmStream_t stream);
+/* nm_layernorm_bwd with parameter gradients (dgamma, dbeta not NULL; ADDED onto) whose per-workgroup partial sums go through `workspace`
+ * (nm_layernorm_bwd_workspace_bytes(rows,dim) bytes, else NM_ERR_WORKSPACE) and are added in a fixed order instead of with float atomics: the
+ * same bits on every run.  dx is that of nm_layernorm_bwd. */
+size_t nm_layernorm_bwd_workspace_bytes(int rows, int dim);
+int nm_layernorm_bwd_ordered(const float* x, const float* gamma, const float* dy, int rows, int dim, float eps, float* dx, float* dgamma,
+                             float* dbeta, void* workspace, size_t workspace_bytes, nmStream_t stream);
 /* backward of y = f / (|f| + 1e-6) (coarse_matching, nerfmatch_c2f_trainer.py:290-291). dim in {64,128,256,512}. */
 int nm_l2norm_bwd(const float* f, const float* dy, int rows, int dim, float* df, nmStream_t stream);
 
@@ -593,6 +603,32 @@ int nm_match_focal_loss_bwd(const uint8_t* conf_gt, const uint8_t* im_mask, cons
                             float alpha, float gamma, int clamp, float scale, const float* grad_loss, void* workspace,
                             size_t workspace_bytes, const double* acc, const float* row_t, const float* col_t, float* ddot,
                             double* dscale, nmStream_t stream);
+
+/* Coarse match supervision of a training batch, built on the device (supervision.hip).  Replaces the numpy code of the reference's
+ * dataset classes (nerfmatch/datasets/nerfmatch_dataset.py:302-353 and :553-583; project_points3d, nerfmatch/utils/geometry.py:119-136),
+ * which makes a dense float32 M x N matrix per pair on the host.
+ *   pt3d [B,N,3], K [B,3,3], w2c [B,3,4] (world-to-camera [R|t]); pt_mask [B,N] / im_mask [B,M] uint8, non-zero = valid, may be NULL;
+ *   H, W: image size in pixels, ds: the coarse stride; M: the number of coarse cells (image tokens), (H/ds)*(W/ds) in the reference.
+ * Outputs (all caller-allocated, device):
+ *   pt2d_proj [B,N,2]  = (K (p / p.z))[:2] with p = R X + t, plain fp32 multiplies / adds and a true division, in the reference's order;
+ *   gt_cell   [B,N] int32: with c = floor(pix / ds), the cell is visible iff min(cx, cy) > 0 && cx < W/ds && cy < H/ds; i = cx + cy * (W/ds)
+ *             clipped to [0, M-1]; gt_cell = i iff visible && pt_mask[b,j] && im_mask[b,i], else -1.  As in the reference, the strict `> 0`
+ *             excludes cell row 0 and cell column 0, and there is no depth test (a point behind the camera whose flipped projection lands
+ *             in the image counts).  p.z == 0 or a non-finite projection (undefined in the reference): invisible.
+ *             NULL: projection only (every argument after pt2d_proj must be NULL then; M, H, W, ds are ignored);
+ *   conf_gt   [B,M,N] uint8 (may be NULL): zero-filled on the stream, 1 at [b, gt_cell[b,j], j] -- what nm_focal_count / nm_match_focal_loss read;
+ *   b_ids, i_ids, j_ids [B*N] int64 and counts [B] int32 (all four or none): the entries of conf_gt in torch.where order (ascending b,
+ *             then i, then j), sum(counts) of them, the rest of the arrays is left unwritten; counts[b] = entries of batch element b.
+ *             Deterministic: the same inputs give the same bytes.  M <= 6400 (a per-cell histogram in LDS), else NM_ERR_UNSUPPORTED.
+ *   fallback  [B,2] int32 (i, j) (may be NULL; needs the triple): a batch element WITHOUT any entry gets row b of it as its only entry, in
+ *             conf_gt and in the triple (the reference's `if match_gt.sum() < 1`, nerfmatch_dataset.py:347-351; the caller draws the pair);
+ *             a row outside [0,M) x [0,N) is ignored.  gt_cell is geometry only and does not show the fallback entry.
+ * H % ds != 0 or W % ds != 0: NM_ERR_UNSUPPORTED.  workspace: nm_gt_supervision_workspace_bytes(B,M,N) bytes, needed for the triple only
+ * (NM_ERR_WORKSPACE).  Every check is made before anything is enqueued. */
+size_t nm_gt_supervision_workspace_bytes(int B, int M, int N);
+int nm_gt_supervision(const float* pt3d, const float* K, const float* w2c, const uint8_t* pt_mask, const uint8_t* im_mask, const int* fallback,
+                      int B, int M, int N, int H, int W, int ds, float* pt2d_proj, int* gt_cell, uint8_t* conf_gt, int64_t* b_ids,
+                      int64_t* i_ids, int64_t* j_ids, int* counts, void* workspace, size_t workspace_bytes, nmStream_t stream);
 
 #ifdef __cplusplus
 }

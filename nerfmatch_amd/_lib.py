@@ -115,10 +115,14 @@ SIGNATURES = {
     "nm_linear_wgrad": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
     "nm_linear_wgrad_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "nm_col_sum": (i32, [vp, i32, i32, i32, vp, vp]),
+    "nm_col_sum_workspace_bytes": (sz, [i32, i32]),
+    "nm_col_sum_ordered": (i32, [vp, i32, i32, i32, vp, vp, sz, vp]),
     "nm_gelu": (i32, [vp, sz, vp, vp]),
     "nm_gelu_bwd": (i32, [vp, vp, sz, vp, vp]),
     "nm_relu_bwd": (i32, [vp, vp, sz, vp, vp]),
     "nm_layernorm_bwd": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]),
+    "nm_layernorm_bwd_workspace_bytes": (sz, [i32, i32]),
+    "nm_layernorm_bwd_ordered": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, sz, vp]),
     "nm_l2norm_bwd": (i32, [vp, vp, i32, i32, vp, vp]),
     "nm_attention_bwd_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "nm_attention_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
@@ -127,6 +131,9 @@ SIGNATURES = {
     "nm_focal_count": (i32, [vp, sz, vp, vp]),
     "nm_match_focal_loss": (i32, [vp, i32, i32, i32, f32, f32, i32, vp, sz, vp, vp, vp, vp]),
     "nm_match_focal_loss_bwd": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, f32, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
+    # ground-truth supervision of a training batch (supervision.hip)
+    "nm_gt_supervision_workspace_bytes": (sz, [i32, i32, i32]),
+    "nm_gt_supervision": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
 }
 
 NM_NERF_SKIP_RGB = 1

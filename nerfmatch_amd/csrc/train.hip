@@ -267,7 +267,8 @@ __global__ void __launch_bounds__(256) wgrad_reduce4_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------------- column sums
 // grid (ceil(N/256), chunks); block 256: thread = column, rows of the chunk in sequence; merged with float atomics
 // (order-dependent in the last bits; `out` must be zeroed or hold the value to accumulate onto).
-__global__ void __launch_bounds__(256) col_sum_kernel(const float* __restrict__ dy, int M, int N, int rows_per, float* __restrict__ out) {
+__global__ void __launch_bounds__(256) col_sum_kernel(const float* __restrict__ dy, int M, int N, int rows_per, float* __restrict__ out,
+                                                      float* __restrict__ part) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= N) return;
   const int m0 = blockIdx.y * rows_per, m1 = min(M, m0 + rows_per);
@@ -280,7 +281,27 @@ __global__ void __launch_bounds__(256) col_sum_kernel(const float* __restrict__ 
     s3 += dy[(size_t)(m + 3) * N + c];
   }
   for (; m < m1; ++m) s0 += dy[(size_t)m * N + c];
-  atomicAdd(out + c, (s0 + s1) + (s2 + s3));
+  if (part) part[(size_t)blockIdx.y * N + c] = (s0 + s1) + (s2 + s3);  // nm_col_sum_ordered
+  else atomicAdd(out + c, (s0 + s1) + (s2 + s3));
+}
+
+// out0[i] (i < n0) / out1[i - n0] += the sum over `parts` partial rows of n floats, four interleaved partial sums added in a fixed order:
+// the same bits on every run (the ordered forms of the column sums and of the LayerNorm parameter gradients)
+__global__ void __launch_bounds__(256) sum_partials_kernel(const float* __restrict__ part, int parts, int n, float* __restrict__ out0, int n0,
+                                                            float* __restrict__ out1) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  int p = 0;
+  for (; p + 3 < parts; p += 4) {
+    s0 += part[(size_t)p * n + i];
+    s1 += part[(size_t)(p + 1) * n + i];
+    s2 += part[(size_t)(p + 2) * n + i];
+    s3 += part[(size_t)(p + 3) * n + i];
+  }
+  for (; p < parts; ++p) s0 += part[(size_t)p * n + i];
+  float* o = i < n0 ? out0 + i : out1 + (i - n0);
+  *o += (s0 + s1) + (s2 + s3);
 }
 
 // ---------------------------------------------------------------------------------------------------- GELU
@@ -320,7 +341,7 @@ __global__ void __launch_bounds__(256) gelu_bwd_kernel(const float* __restrict__
 template <int PER>
 __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                              const float* __restrict__ dy, int rows, float eps, float* __restrict__ dx,
-                                                             float* __restrict__ dgamma, float* __restrict__ dbeta) {
+                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ part) {
   // Round 6: a lane holds PER CONSECUTIVE columns (one 16-byte load per operand at dim 256 instead of four 4-byte ones) and the next row's
   // loads are issued before this row's four lane reductions; two workgroups per CU (the first version ran one wavefront per SIMD through a
   // chain of load -> reduce -> reduce -> reduce -> store per row with nothing to hide its latency behind: 24 us for 7200 x 256).
@@ -392,8 +413,14 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const float* __restr
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int c = lane + 64 * i;  // consecutive lanes, consecutive addresses
-    atomicAdd(dgamma + c, (red[0][0][c] + red[1][0][c]) + (red[2][0][c] + red[3][0][c]));
-    atomicAdd(dbeta + c, (red[0][1][c] + red[1][1][c]) + (red[2][1][c] + red[3][1][c]));
+    const float sg = (red[0][0][c] + red[1][0][c]) + (red[2][0][c] + red[3][0][c]), sb = (red[0][1][c] + red[1][1][c]) + (red[2][1][c] + red[3][1][c]);
+    if (part) {  // nm_layernorm_bwd_ordered: one partial row [dgamma | dbeta] per workgroup, summed in a fixed order by sum_partials_kernel
+      part[(size_t)blockIdx.x * 2 * dim + c] = sg;
+      part[(size_t)blockIdx.x * 2 * dim + dim + c] = sb;
+    } else {
+      atomicAdd(dgamma + c, sg);
+      atomicAdd(dbeta + c, sb);
+    }
   }
 }
 
@@ -496,7 +523,27 @@ extern "C" int nm_col_sum(const float* dy, int M, int N, int accumulate, float* 
   if (!accumulate && hipMemsetAsync(out, 0, (size_t)N * sizeof(float), s) != hipSuccess) return NM_ERR_LAUNCH;
   const int chunks = max(1, min(256, M / 64));
   const int rows_per = (M + chunks - 1) / chunks;
-  col_sum_kernel<<<dim3((N + 255) / 256, (M + rows_per - 1) / rows_per), 256, 0, s>>>(dy, M, N, rows_per, out);
+  col_sum_kernel<<<dim3((N + 255) / 256, (M + rows_per - 1) / rows_per), 256, 0, s>>>(dy, M, N, rows_per, out, nullptr);
+  return nm_launch_status();
+}
+
+extern "C" size_t nm_col_sum_workspace_bytes(int M, int N) {
+  if (M <= 0 || N <= 0) return 0;
+  return (size_t)max(1, min(256, M / 64)) * N * sizeof(float);
+}
+
+extern "C" int nm_col_sum_ordered(const float* dy, int M, int N, int accumulate, float* out, void* workspace, size_t workspace_bytes,
+                                  nmStream_t stream) {
+  NM_CHECK_ARG(dy && out && M > 0 && N > 0);
+  if (!workspace || workspace_bytes < nm_col_sum_workspace_bytes(M, N)) return NM_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  if (!accumulate && hipMemsetAsync(out, 0, (size_t)N * sizeof(float), s) != hipSuccess) return NM_ERR_LAUNCH;
+  const int chunks = max(1, min(256, M / 64));
+  const int rows_per = (M + chunks - 1) / chunks;
+  const int parts = (M + rows_per - 1) / rows_per;  // <= chunks
+  float* part = (float*)workspace;
+  col_sum_kernel<<<dim3((N + 255) / 256, parts), 256, 0, s>>>(dy, M, N, rows_per, nullptr, part);
+  sum_partials_kernel<<<(N + 255) / 256, 256, 0, s>>>(part, parts, N, out, N, nullptr);
   return nm_launch_status();
 }
 
@@ -520,18 +567,44 @@ extern "C" int nm_gelu_bwd(const float* u, const float* dh, size_t n, float* du,
   return nm_launch_status();
 }
 
+namespace {
+int ln_bwd_grid(int rows, bool param_grads) { return max(1, min((rows + 3) / 4, (param_grads ? 1 : 2) * nm_cu_count())); }  // (with parameter gradients: 2 dim atomics / one partial row per workgroup)
+int ln_bwd_launch(const float* x, const float* gamma, const float* dy, int rows, int dim, float eps, float* dx, float* dgamma, float* dbeta, float* part,
+                  hipStream_t s) {
+  const int grid = ln_bwd_grid(rows, dgamma != nullptr);
+  switch (dim) {
+    case 64: layernorm_bwd_kernel<1><<<grid, 256, 0, s>>>(x, gamma, dy, rows, eps, dx, dgamma, dbeta, part); break;
+    case 128: layernorm_bwd_kernel<2><<<grid, 256, 0, s>>>(x, gamma, dy, rows, eps, dx, dgamma, dbeta, part); break;
+    case 256: layernorm_bwd_kernel<4><<<grid, 256, 0, s>>>(x, gamma, dy, rows, eps, dx, dgamma, dbeta, part); break;
+    case 512: layernorm_bwd_kernel<8><<<grid, 256, 0, s>>>(x, gamma, dy, rows, eps, dx, dgamma, dbeta, part); break;
+    default: return NM_ERR_UNSUPPORTED;
+  }
+  return NM_OK;
+}
+}  // namespace
+
 extern "C" int nm_layernorm_bwd(const float* x, const float* gamma, const float* dy, int rows, int dim, float eps, float* dx,
                                 float* dgamma, float* dbeta, nmStream_t stream) {
   NM_CHECK_ARG(x && gamma && dy && dx && ((dgamma != nullptr) == (dbeta != nullptr)) && rows > 0);
+  const int rc = ln_bwd_launch(x, gamma, dy, rows, dim, eps, dx, dgamma, dbeta, nullptr, (hipStream_t)stream);
+  return rc != NM_OK ? rc : nm_launch_status();
+}
+
+extern "C" size_t nm_layernorm_bwd_workspace_bytes(int rows, int dim) {
+  if (rows <= 0 || dim <= 0) return 0;
+  return (size_t)ln_bwd_grid(rows, true) * 2 * dim * sizeof(float);
+}
+
+extern "C" int nm_layernorm_bwd_ordered(const float* x, const float* gamma, const float* dy, int rows, int dim, float eps, float* dx,
+                                        float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, nmStream_t stream) {
+  NM_CHECK_ARG(x && gamma && dy && dx && dgamma && dbeta && rows > 0);
+  if (dim != 64 && dim != 128 && dim != 256 && dim != 512) return NM_ERR_UNSUPPORTED;
+  if (!workspace || workspace_bytes < nm_layernorm_bwd_workspace_bytes(rows, dim)) return NM_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  const int grid = max(1, min((rows + 3) / 4, (dgamma ? 1 : 2) * nm_cu_count()));  // (with parameter gradients: 2 dim atomics per workgroup)
-  switch (dim) {
-    case 64: layernorm_bwd_kernel<1><<<grid, 256, 0, s>>>(x, gamma, dy, rows, eps, dx, dgamma, dbeta); break;
-    case 128: layernorm_bwd_kernel<2><<<grid, 256, 0, s>>>(x, gamma, dy, rows, eps, dx, dgamma, dbeta); break;
-    case 256: layernorm_bwd_kernel<4><<<grid, 256, 0, s>>>(x, gamma, dy, rows, eps, dx, dgamma, dbeta); break;
-    case 512: layernorm_bwd_kernel<8><<<grid, 256, 0, s>>>(x, gamma, dy, rows, eps, dx, dgamma, dbeta); break;
-    default: return NM_ERR_UNSUPPORTED;
-  }
+  float* part = (float*)workspace;
+  const int rc = ln_bwd_launch(x, gamma, dy, rows, dim, eps, dx, dgamma, dbeta, part, s);
+  if (rc != NM_OK) return rc;
+  sum_partials_kernel<<<(2 * dim + 255) / 256, 256, 0, s>>>(part, ln_bwd_grid(rows, true), 2 * dim, dgamma, dim, dbeta);
   return nm_launch_status();
 }
 

@@ -640,6 +640,12 @@ class NeRFMatcherMS(_MatcherBase):
             hit = self.__dict__["_gt_ids_cache"] = (weakref.ref(conf_gt), key, torch.where(conf_gt))
         return hit[2]
 
+    def seed_gt_ids(self, conf_gt, ids):
+        """Stores a ready (b_ids, i_ids, j_ids) triple -- equal to torch.where(conf_gt), e.g. supervision.coarse_supervision's "gt_ids" -- as
+        the cache entry of this tensor object in its current state: the step's _gt_ids(conf_gt) calls then return it without scanning the mask."""
+        b_ids, i_ids, j_ids = ids
+        self.__dict__["_gt_ids_cache"] = (weakref.ref(conf_gt), (conf_gt._version, tuple(conf_gt.shape)), (b_ids, i_ids, j_ids))
+
     def _train_preds(self, img, pt_feat, pt3d, im_mask, pt_mask, conf_gt, ret_feats=False, mutual=False, match_thres=0.0, alpha=0.25,
                      gamma=2.0, train_percent=0.3, pad_gt=True):
         """forward_match with ground truth (must run inside autograd.training()): encoders, cross attention, dual-softmax with

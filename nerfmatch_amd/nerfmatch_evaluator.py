@@ -146,9 +146,16 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
         """`--match_oracle` (reference :163-174): the ground-truth correspondences of `batch["conf_gt"]` (Q, M, N) instead of the
         model's -- points indexed by the point id, pixels = the points' projections `pt2d_proj` (c2f) or the coarse cell centres
         `pt2d` (coarse-only model).  The reference reads batch element 0 only (its eval batch is 1); here every query q gets
-        its own rows."""
+        its own rows.  A batch without "conf_gt" gets its supervision from its own geometry (K, c2w, pt3d: supervision.coarse_supervision,
+        triple and projections only -- no dense matrix, no fallback entry for a query that sees no point)."""
         Q = batch["image"].shape[0]
-        bid, i2d, i3d = (t.cpu() for t in torch.where(batch["conf_gt"]))
+        if "conf_gt" in batch:
+            ids = torch.where(batch["conf_gt"])
+        else:
+            from .supervision import coarse_supervision
+
+            ids = coarse_supervision(batch, ds=self.model.coarse_ds, dense=False)["gt_ids"]
+        bid, i2d, i3d = (t.cpu() for t in ids)
         pt3d = batch["pt3d"].cpu().reshape(Q, -1, 3)
         pix = batch["pt2d"].cpu() if self.coarse_only else batch["pt2d_proj"].cpu()
         per = []

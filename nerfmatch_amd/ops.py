@@ -947,12 +947,17 @@ def linear_wgrad_bias(dy, x):
     return dw, db
 
 
+_COLSUM_WS = {}
+_LN_BWD_WS = {}
+
+
 def col_sum(dy):
     dy = dy.contiguous()
     M, N = dy.shape
     out = torch.zeros(N, device=dy.device, dtype=torch.float32)
-    if M:
-        check(lib().nm_col_sum(dptr(dy), M, N, 1, dptr(out), stream()), "nm_col_sum")
+    if M:  # (the ordered form: partial sums added in a fixed order -- the same bits on every run)
+        ws = _scratch(_COLSUM_WS, dy.device, lib().nm_col_sum_workspace_bytes(M, N))
+        check(lib().nm_col_sum_ordered(dptr(dy), M, N, 1, dptr(out), dptr(ws, torch.uint8), ws.numel(), stream()), "nm_col_sum_ordered")
     return out
 
 
@@ -990,8 +995,12 @@ def layernorm_bwd(x, gamma, dy, eps=1e-5, param_grads=True):
     if param_grads:
         dg_db = torch.zeros(2, dim, device=x.device, dtype=torch.float32)  # (one fill launch for both)
         dg, db = dg_db[0], dg_db[1]
-    if x2.shape[0]:
-        check(lib().nm_layernorm_bwd(dptr(x2), dptr(gamma), dptr(dy2), x2.shape[0], dim, float(eps), dptr(dx), dptr(dg), dptr(db), stream()),
+    if x2.shape[0] and param_grads:  # (the ordered form: dgamma / dbeta summed in a fixed order -- the same bits on every run)
+        ws = _scratch(_LN_BWD_WS, x.device, lib().nm_layernorm_bwd_workspace_bytes(x2.shape[0], dim))
+        check(lib().nm_layernorm_bwd_ordered(dptr(x2), dptr(gamma), dptr(dy2), x2.shape[0], dim, float(eps), dptr(dx), dptr(dg), dptr(db),
+                                             dptr(ws, torch.uint8), ws.numel(), stream()), "nm_layernorm_bwd_ordered")
+    elif x2.shape[0]:
+        check(lib().nm_layernorm_bwd(dptr(x2), dptr(gamma), dptr(dy2), x2.shape[0], dim, float(eps), dptr(dx), None, None, stream()),
               "nm_layernorm_bwd")
     return dx.reshape(x.shape), dg, db
 
@@ -1070,3 +1079,37 @@ def fine_expectation_bwd(pt_f, win_f, d_expec, count, win=5):
         check(lib().nm_fine_expectation_bwd(dptr(pt_f), dptr(win_f), dptr(d_expec), dptr(count, torch.int32), K, int(win), Cc,
                                             dptr(d_pt), dptr(d_win), stream()), "nm_fine_expectation_bwd")
     return d_pt, d_win
+
+
+# ----------------------------------------------------------------------------- ground-truth supervision (supervision.hip)
+_SUPERVISION_WS = {}
+
+
+def gt_supervision(pt3d, K, w2c, pt_mask=None, im_mask=None, fallback=None, hw=None, ds=8, M=None, dense=True, triple=True):
+    """nm_gt_supervision: pt3d (B,N,3), K (B,3,3), w2c (B,3,4), masks (B,N) / (B,M) or None, fallback (B,2) int32 or None.
+    hw=None: projection only -> pt2d_proj (B,N,2).  Otherwise -> dict(pt2d_proj, gt_cell (B,N) int32, conf_gt (B,M,N) uint8 | None,
+    ids = (b_ids, i_ids, j_ids) int64 at capacity B*N and counts (B,) int32 | None): the caller trims the triple to counts.sum()."""
+    B, N = pt3d.shape[:2]
+    dev = pt3d.device
+    proj = torch.empty(B, N, 2, device=dev, dtype=torch.float32)
+    if B * N == 0:
+        raise _lib.NerfmatchAmdError("gt_supervision: empty point set")
+    if hw is None:
+        check(lib().nm_gt_supervision(dptr(pt3d), dptr(K), dptr(w2c), None, None, None, B, 0, N, 0, 0, 0, dptr(proj), None, None, None, None, None,
+                                      None, None, 0, stream()), "nm_gt_supervision")
+        return proj
+    H, W = int(hw[0]), int(hw[1])
+    M = (H // ds) * (W // ds) if M is None else int(M)
+    cell = torch.empty(B, N, device=dev, dtype=torch.int32)
+    conf = torch.empty(B, M, N, device=dev, dtype=torch.uint8) if dense else None
+    ids = [torch.empty(B * N, device=dev, dtype=torch.int64) for _ in range(3)] if triple else [None] * 3
+    counts = torch.empty(B, device=dev, dtype=torch.int32) if triple else None
+    ws, need = None, 0
+    if triple:
+        need = lib().nm_gt_supervision_workspace_bytes(B, M, N)
+        ws = _scratch(_SUPERVISION_WS, dev, need)
+    check(lib().nm_gt_supervision(dptr(pt3d), dptr(K), dptr(w2c), dptr(_mask_u8(pt_mask), torch.uint8), dptr(_mask_u8(im_mask), torch.uint8),
+                                  dptr(fallback, torch.int32), B, M, N, H, W, int(ds), dptr(proj), dptr(cell, torch.int32),
+                                  dptr(conf, torch.uint8), dptr(ids[0], torch.int64), dptr(ids[1], torch.int64), dptr(ids[2], torch.int64),
+                                  dptr(counts, torch.int32), dptr(ws, torch.uint8), need, stream()), "nm_gt_supervision")
+    return dict(pt2d_proj=proj, gt_cell=cell, conf_gt=conf, ids=tuple(ids) if triple else None, counts=counts)

@@ -16,6 +16,7 @@ import torch
 
 from . import dist as nmdist
 from .matcher import NeRFMatcherCoarse, NeRFMatcherMS
+from .supervision import supervise_batch
 
 
 class _TrainerBase:
@@ -92,6 +93,7 @@ class _TrainerBase:
         """forward + backward + gradient all-reduce + optimiser step; returns the metrics of the step (detached scalars)."""
         if self.optimizer is None:
             self.configure_optimizers()
+        supervise_batch(self.model, data)  # (a batch with K / c2w / pt3d but no conf_gt: supervision built on the device; else untouched)
         with torch.enable_grad():
             metrics = self.model_forward(data, training=True)
             self.optimizer.zero_grad(set_to_none=True)
@@ -102,6 +104,7 @@ class _TrainerBase:
         return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in metrics.items()}
 
     def validation_step(self, data, batch_idx=0):
+        supervise_batch(self.model, data)
         with torch.no_grad():  # the modules leave the autograd path when gradients are disabled
             return self.model_forward(data, training=False)
 
