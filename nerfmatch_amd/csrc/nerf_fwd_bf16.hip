@@ -29,7 +29,9 @@
 //     overhead of a K-step in the cycle trace); every wavefront then reads its A operands with conflict-free ds_read_b128
 //     (the ring layout is lane-linear, exactly what the DMA writes);
 //   * the tapped activations (feature output) are parked in an L2-resident workspace (32 x 1 KiB stores per wavefront)
-//     until the compositing weights are known, then reduced over the 32 samples of a wavefront with DPP adds;
+//     until the compositing weights are known, then reduced over the 32 samples of a wavefront with DPP adds -- except for a tap on
+//     layer 7 in a pass with colour heads (the coarse pass of the renderer): the densities exist before the views layer, so the
+//     weights are formed there and w * h7 is reduced straight from the registers that hold layer 7 (tap7_early: no round trip);
 //   * the integrated positional encoding is evaluated once per 128-sample chunk (each lane the 48 values of its wavefront
 //     half, fp32 sine with a 4-term Cody-Waite reduction of the exact argument 2^i x) and parked in LDS as ready-made
 //     B operands for layers 0 and 5.
@@ -120,13 +122,13 @@ __device__ __forceinline__ void quad_add8(float (&v)[8]) {  // v[i] += v[i] of l
         "v_add_f32_dpp %6, %6, %6 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\tv_add_f32_dpp %7, %7, %7 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
         : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
 }
-__device__ __forceinline__ f32x4 reduce_scatter_32rows(float (&v)[128], int lane) {
-  float s1[64];  // rows 0..15 | (lanes 16..31 of the half: rows 16..31)
-#pragma unroll
-  for (int i = 0; i < 64; ++i) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[64 + i]), false, false);
-    s1[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
+// distance 16 for one value of row c (x) and one of row c + 16 (y)
+__device__ __forceinline__ float reduce_scatter_step16(float x, float y) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+// distances 8 .. 1, from s1[i] = reduce_scatter_step16(v[i], v[64 + i]): rows 0..15 | (lanes 16..31 of the half: rows 16..31)
+__device__ __forceinline__ f32x4 reduce_scatter_16pairs(const float (&s1)[64], int lane) {
   float s2[32];  // 8 rows
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
@@ -158,6 +160,12 @@ __device__ __forceinline__ f32x4 reduce_scatter_32rows(float (&v)[128], int lane
   quad_add8<1>(t8);
   return (lane & 1) ? f32x4{t8[4], t8[5], t8[6], t8[7]} : f32x4{t8[0], t8[1], t8[2], t8[3]};
 }
+__device__ __forceinline__ f32x4 reduce_scatter_32rows(float (&v)[128], int lane) {
+  float s1[64];
+#pragma unroll
+  for (int i = 0; i < 64; ++i) s1[i] = reduce_scatter_step16(v[i], v[64 + i]);
+  return reduce_scatter_16pairs(s1, lane);
+}
 
 // Barriers of the tile's epilogue between tap_prefetch and the feature reduction: they order LDS traffic only (per-sample scratch), so they
 // wait for LDS only -- a __syncthreads() is also a memory fence and would sit out the read-back that is meant to overlap this phase.
@@ -181,9 +189,9 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
   float* const sm_dn = sm_mean + 3 * TILE;
   float* const sm_w = sm_dn + TILE;
   float* const sm_misc = sm_w + TILE;         // [32]
+  float* const sm_part = sm_misc + 32;        // [4 half wavefronts][8] partial per-ray sums (the scratch block has 128 floats to spare;
+                                              // not over sm_feat: with a tap composited early the feature partials are there first)
   float* const sm_feat = sm + LDS_FEAT;       // [4][256]
-  float* const sm_part = sm_feat;             // [4 half wavefronts][8] partial per-ray sums: written and read by wavefront 0/1
-                                              // before wavefront 0 stores its feature partials over them (program order)
   float* const sm_ex = sm + LDS_EX;           // [nr][48]
   int* const sm_lray = reinterpret_cast<int*>(sm + LDS_LEFT);  // [128] rays whose sample Sa is still to be evaluated
   float* const sm_lT = sm + LDS_LEFT + TILE;                   // [128] their transmittance after the first Sa samples
@@ -344,7 +352,10 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     cx.tapw = reinterpret_cast<f32x4*>(a.ws) + ((size_t)blockIdx.x * 4 + wave) * 32 * 64 + lane;
     cx.nslots = nslots; cx.wave = wave; cx.lane = lane; cx.hi = hi; cx.tap = need_tap ? tap : -1; cx.g = 0; cx.sig_part = 0.f;
     cx.vmax = 0.f; cx.rng = sm_rng + tid; cx.sc = 1.f;
-    cx.tap_pref = need_tap && !lo_pass; cx.rgb = need_rgb;
+    // A tap on layer 7 in a regular tile with colour heads is composited at the end of layer 7, from registers (tap7_early); the
+    // per-sample feature output (a debug output) and the leftover pass keep the workspace path.
+    const bool early = need_rgb && !lo_pass && tap == 7 && a.feat && !a.sfeat;
+    cx.tap_pref = need_tap && !lo_pass && !early; cx.rgb = need_rgb;
     cx.tap_ring = ring + wave * SLOT_FLOATS; cx.tap_ipe = sm_ipe + wave * (XS * 2 * 64 * 4);
     if constexpr (is_split<P>()) {
       // slots 0 and 1 landed (2 and 3 may stay in flight until the barrier of K-step 1), everybody's pieces: barrier
@@ -356,13 +367,139 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     load_half<P>(cx.opA, ring, lane, 0);
     if constexpr (P == 1) load_half<1>(cx.opB, ring, lane, 1);
     const float* ipe_src = sm_ipe + wave * (XS * 2 * 64 * 4) + lane * 4;
+
+    // ---- alpha compositing (identical to nerf_fwd.hip), in pieces: a tap on layer 7 needs the weights before the views layer ----------
+    // Piece 1, behind a barrier that follows the densities into sm_sigma: alpha, transmittance scan, weights -> sm_w, the leftover queue,
+    // the transmittance carried into the next chunk.  ONE copy of these expressions: the epilogue calls it, or tap7_early does.
+    auto composite_weights = [&]() __attribute__((always_inline)) {
+      const int tid2 = launder(threadIdx.x), lane2 = tid2 & 63, wave2 = tid2 >> 6;
+      float alpha = 0.f, incl = 1.f;
+      if (tid2 < TILE) {
+        const float sg = fmaxf(sm_sigma[tid2], 0.f);
+        const float delta = (sm_t1[tid2] - sm_t0[tid2]) * sm_dn[tid2];
+        alpha = 1.0f - expf(-sg * delta);
+        incl = (1.0f - alpha) + 1e-10f;
+        const int seg = SP < 64 ? SP : 64;
+#pragma unroll
+        for (int dlt = 1; dlt < 64; dlt <<= 1) {
+          const float up = __shfl_up(incl, dlt, 64);
+          if (dlt < seg && (lane2 & (seg - 1)) >= dlt) incl *= up;
+        }
+        if (lane2 == 63) sm_misc[wave2] = incl;
+      }
+      NM_EPI_BARRIER();
+      if (tid2 < TILE) {
+        const int seg = SP < 64 ? SP : 64;
+        float excl = __shfl_up(incl, 1, 64);
+        if ((lane2 & (seg - 1)) == 0) excl = 1.f;
+        if (SP == TILE && wave2 == 1) excl *= sm_misc[0];
+        excl *= carryT;
+        sm_w[tid2] = alpha * excl;
+        const int r2 = tid2 / SP, ray2 = bid * nr + r2;
+        if (left && chunk == nchunks - 1 && ray2 < R && tid2 % SP == SP - 1) {
+          // (zero-width tail) sample Sa is queued with the transmittance in front of it
+          sm_lray[nleft + r2] = ray2;
+          sm_lT[nleft + r2] = excl * ((1.0f - alpha) + 1e-10f);
+        }
+      }
+      if (nchunks > 1) carryT = carryT * (sm_misc[0] * sm_misc[1]);
+    };
+    // Piece 2, once the colours are in sm_rgb: the per-sample outputs and the per-ray sums, step 1 (weights from sm_w: own write or a
+    // barrier ago)
+    auto composite_sums = [&]() __attribute__((always_inline)) {
+      const int tid2 = launder(threadIdx.x);
+      if (tid2 < TILE) {
+        const float wgt = sm_w[tid2];
+        const int r2 = tid2 / SP, ray2 = bid * nr + r2;
+        if (ray2 < R) {
+          const int s2 = chunk * TILE + tid2 % SP;
+          a.weights[(size_t)ray2 * S + s2] = wgt;
+          if (left && chunk == nchunks - 1) {
+            // the zero-width tail carries weight exactly 0
+            for (int k = Sa + 1 + tid2 % SP; k < S; k += SP) a.weights[(size_t)ray2 * S + k] = 0.f;
+          }
+          if (a.raw && !NM_TRACE) {
+            f32x4 rv = {sm_rgb[tid2], sm_rgb[TILE + tid2], sm_rgb[2 * TILE + tid2], sm_sigma[tid2]};
+            *reinterpret_cast<f32x4*>(a.raw + ((size_t)ray2 * S + s2) * 4) = rv;
+          }
+        }
+        // w * {1, rgb, t_mid, mean} reduced over each 32-sample half wavefront
+        float pq[8] = {wgt, wgt * sm_rgb[tid2], wgt * sm_rgb[TILE + tid2], wgt * sm_rgb[2 * TILE + tid2],
+                       wgt * (0.5f * (sm_t0[tid2] + sm_t1[tid2])), wgt * sm_mean[tid2], wgt * sm_mean[TILE + tid2],
+                       wgt * sm_mean[2 * TILE + tid2]};
+        nm_half_sum_dpp8(pq);  // valid in lanes 16..31 / 48..63
+        if ((tid2 & 31) == 16) {
+          *reinterpret_cast<f32x4*>(sm_part + (tid2 >> 5) * 8) = f32x4{pq[0], pq[1], pq[2], pq[3]};
+          *reinterpret_cast<f32x4*>(sm_part + (tid2 >> 5) * 8 + 4) = f32x4{pq[4], pq[5], pq[6], pq[7]};
+        }
+      }
+    };
+    // feat_comb max, a barrier behind sm_w: the max-weight sample of each ray slot (over all chunks so far: best_w) -> sm_misc[8 + slot],
+    // and its mean as the point output
+    auto pick_best = [&]() __attribute__((always_inline)) {
+      const int tid2 = launder(threadIdx.x);
+      if (tid2 < 8 * nr) {
+        const int q = tid2 & 7, r2 = tid2 >> 3;
+        const float* wv = sm_w + r2 * SP;
+        float bw = wv[0];
+        int bi = 0;
+        for (int k = 1; k < SP; ++k)
+          if (wv[k] > bw) { bw = wv[k]; bi = k; }
+        const bool better = bw > best_w;
+        if (better) best_w = bw;
+        if (q == 0) sm_misc[8 + r2] = better ? __int_as_float(r2 * SP + bi) : __int_as_float(-1);
+        if (q >= 5 && better) red_acc = sm_mean[(q - 5) * TILE + r2 * SP + bi];
+      }
+    };
+    // Tap on layer 7 with colour heads, called by layer_pass right behind the density head (cx.sig_part), in front of the views layer:
+    // layer 7 is still in this wavefront's registers (c.hv) and every sample's raw density is one shuffle away, so the weights are formed
+    // now and sum_s w_s h7_s is taken from c.hv -- the 32 x 1 KiB per wavefront neither go to the workspace nor come back (5 GB each way per
+    // 4 x 4800 x 64 launch).  Same values, same multiplication order and same reduction as the workspace path; the eight accumulator blocks
+    // are free here (finish_layer moved them out), which is what the 128 products live in.
+    auto tap7_early = [&](Ctx& c) __attribute__((always_inline)) {
+      const int t2 = launder(threadIdx.x), jl = (t2 >> 6) * 32 + (t2 & 31), hl = (t2 >> 5) & 1;
+      const float sigma_raw = (c.sig_part + nm_shfl_xor32(c.sig_part)) + sm_small[OFF_MISC];  // (the epilogue stores the same value again)
+      if (hl == 0) sm_sigma[jl] = sigma_raw;
+      NM_EPI_BARRIER();  // (LDS only, like the epilogue's: the weight stream of the views layer stays in flight)
+      composite_weights();
+      NM_EPI_BARRIER();
+      if (feat_max) {
+        pick_best();
+        NM_EPI_BARRIER();
+      }
+      const float desc = sm_small[OFF_DESCALE + 7];  // back to true units (1 unless fp16x3): folded into the weight
+      const float wj = sm_w[jl] * desc;
+      const int best = feat_max ? __float_as_int(sm_misc[8 + jl / SP]) : -2;
+      const float mult = feat_max ? (jl == best ? desc : 0.f) : wj;  // (one multiplier per lane: see the workspace path below)
+      const float* bl = sm_small + OFF_BIAS + 7 * 256 + 4 * hl;
+      const float s7 = sm_small[OFF_SCALE + 7];
+      // row cq = 4 block + quad holds c.hv[4 cq ..], as dump_tap lays the workspace out; rows cq and cq + 16 are made together and go
+      // through the first reduction step at once, so that 64 values are live beside c.hv and not 128
+      float s1[64];
+#pragma unroll
+      for (int cq = 0; cq < HS; ++cq) {
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(bl + (cq >> 2) * 32 + 8 * (cq & 3));
+        const f32x4 b1 = *reinterpret_cast<const f32x4*>(bl + (4 + (cq >> 2)) * 32 + 8 * (cq & 3));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float x = mult * __builtin_fmaxf(__builtin_fmaf(c.hv[4 * cq + e], s7, b0[e]), 0.f);
+          const float y = mult * __builtin_fmaxf(__builtin_fmaf(c.hv[64 + 4 * cq + e], s7, b1[e]), 0.f);
+          s1[4 * cq + e] = reduce_scatter_step16(x, y);
+        }
+      }
+      const f32x4 sum4 = reduce_scatter_16pairs(s1, jl);
+      const int r = jl & 31;
+      float* prow = sm_feat + (jl >> 5) * 256 + 4 * hl;  // partial sums of this wavefront: read by the epilogue's cross-wavefront add
+      *reinterpret_cast<f32x4*>(prow + (r >> 2) * 32 + 16 * ((r >> 1) & 1) + 8 * (r & 1)) = sum4;
+    };
+    const Tap7InRegisters<decltype(tap7_early)> tap7{early, tap7_early};
     f32x16 acc[8];
     ipe_steps<P, true>(acc, cx, ipe_src);  // layer 0
     finish_layer<P>(acc, 0, cx);
     TRACE(3);
 #pragma unroll 1
     for (int l = 1; l < 8; ++l) {
-      layer_pass<P>(acc, l, cx, ipe_src);
+      layer_pass<P>(acc, l, cx, ipe_src, tap7);
       TRACE(3 + l);
     }
     float c_r = 0.f, c_g = 0.f, c_b = 0.f;
@@ -511,85 +648,28 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
       break;  // (the chunk loop; a leftover pass has a single chunk)
     }
 
-    // ---- alpha compositing (identical to nerf_fwd.hip) ---------------------------------------------------------------
-    float alpha = 0.f, incl = 1.f;
-    if (tid2 < TILE) {
-      const float sg = fmaxf(sm_sigma[tid2], 0.f);
-      const float delta = (sm_t1[tid2] - sm_t0[tid2]) * sm_dn[tid2];
-      alpha = 1.0f - expf(-sg * delta);
-      incl = (1.0f - alpha) + 1e-10f;
-      const int seg = SP < 64 ? SP : 64;
-#pragma unroll
-      for (int dlt = 1; dlt < 64; dlt <<= 1) {
-        const float up = __shfl_up(incl, dlt, 64);
-        if (dlt < seg && (lane2 & (seg - 1)) >= dlt) incl *= up;
-      }
-      if (lane2 == 63) sm_misc[wave2] = incl;
-    }
-    NM_EPI_BARRIER();
-    if (tid2 < TILE) {
-      const int seg = SP < 64 ? SP : 64;
-      float excl = __shfl_up(incl, 1, 64);
-      if ((lane2 & (seg - 1)) == 0) excl = 1.f;
-      if (SP == TILE && wave2 == 1) excl *= sm_misc[0];
-      excl *= carryT;
-      const float wgt = alpha * excl;
-      sm_w[tid2] = wgt;
-      const int r2 = tid2 / SP, ray2 = bid * nr + r2;
-      if (ray2 < R) {
-        const int s2 = chunk * TILE + tid2 % SP;
-        a.weights[(size_t)ray2 * S + s2] = wgt;
-        if (left && chunk == nchunks - 1) {
-          // the zero-width tail carries weight exactly 0; sample Sa is queued with the transmittance in front of it
-          for (int k = Sa + 1 + tid2 % SP; k < S; k += SP) a.weights[(size_t)ray2 * S + k] = 0.f;
-          if (tid2 % SP == SP - 1) {
-            sm_lray[nleft + r2] = ray2;
-            sm_lT[nleft + r2] = excl * ((1.0f - alpha) + 1e-10f);
-          }
-        }
-        if (a.raw && !NM_TRACE) {
-          f32x4 rv = {sm_rgb[tid2], sm_rgb[TILE + tid2], sm_rgb[2 * TILE + tid2], sm_sigma[tid2]};
-          *reinterpret_cast<f32x4*>(a.raw + ((size_t)ray2 * S + s2) * 4) = rv;
-        }
-      }
-      // per-ray sums, step 1: w * {1, rgb, t_mid, mean} reduced over each 32-sample half wavefront
-      float pq[8] = {wgt, wgt * sm_rgb[tid2], wgt * sm_rgb[TILE + tid2], wgt * sm_rgb[2 * TILE + tid2],
-                     wgt * (0.5f * (sm_t0[tid2] + sm_t1[tid2])), wgt * sm_mean[tid2], wgt * sm_mean[TILE + tid2],
-                     wgt * sm_mean[2 * TILE + tid2]};
-      nm_half_sum_dpp8(pq);  // valid in lanes 16..31 / 48..63
-      if ((tid2 & 31) == 16) {
-        *reinterpret_cast<f32x4*>(sm_part + (tid2 >> 5) * 8) = f32x4{pq[0], pq[1], pq[2], pq[3]};
-        *reinterpret_cast<f32x4*>(sm_part + (tid2 >> 5) * 8 + 4) = f32x4{pq[4], pq[5], pq[6], pq[7]};
-      }
-    }
-    if (nchunks > 1) carryT = carryT * (sm_misc[0] * sm_misc[1]);
+    if (!early) composite_weights();
+    composite_sums();
     NM_EPI_BARRIER();
 
     // ---- per-ray sums, step 2: combine the SP/32 half wavefronts of each ray ------------------------------------------
     if (tid2 < 8 * nr) {
       const int q = tid2 & 7, r2 = tid2 >> 3;
-      const float* wv = sm_w + r2 * SP;
       if (!feat_max || q < 5) {
         float sum = 0.f;
         for (int hw = r2 * (SP / 32); hw < (r2 + 1) * (SP / 32); ++hw) sum += sm_part[hw * 8 + q];
         red_acc += sum;
       }
-      if (feat_max) {
-        float bw = wv[0];
-        int bi = 0;
-        for (int k = 1; k < SP; ++k)
-          if (wv[k] > bw) { bw = wv[k]; bi = k; }
-        const bool better = bw > best_w;
-        if (better) best_w = bw;
-        if (q == 0) sm_misc[8 + r2] = better ? __int_as_float(r2 * SP + bi) : __int_as_float(-1);
-        if (q >= 5 && better) red_acc = sm_mean[(q - 5) * TILE + r2 * SP + bi];
-      }
     }
-    if (feat_max) NM_EPI_BARRIER();
+    if (feat_max && !early) {
+      pick_best();
+      NM_EPI_BARRIER();
+    }
 
     TRACE(14);
-    // ---- feature output: weighted sum over the 32 samples of this wavefront straight from registers ------------------
-    if (need_tap) {
+    // ---- feature output: weighted sum over the 32 samples of this wavefront, read back from the workspace --------------
+    // (tap7_early has done this at the end of layer 7 when `early`; what follows the barrier below is common to both)
+    if (need_tap && !early) {
       const int jl = launder(js), hl = launder(lane) >> 5;
       f32x4 tapv[2 * HS];
       {

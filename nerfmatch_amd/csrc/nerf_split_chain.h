@@ -673,10 +673,24 @@ __device__ __forceinline__ void ipe_steps(f32x16 (&acc)[8], Ctx& cx, const float
   }
 }
 
+// What a pass with colour heads does with a tap on layer 7, whose activations (cx.hv) the views layer is about to consume:
+//   Tap7Workspace: parks them in the workspace (dump_tap) until the epilogue knows the compositing weights;
+//   Tap7InRegisters{on, fn}: when `on`, calls fn(cx) right behind the density head instead -- the render kernel forms the weights there
+//     (every sample's density exists one shuffle later) and reduces w * h7 straight from cx.hv: no store, no read-back.
+struct Tap7Workspace {
+  static constexpr bool on = false;
+  __device__ __forceinline__ void fn(Ctx&) const {}
+};
+template <class F>
+struct Tap7InRegisters {
+  bool on;
+  F fn;
+};
+
 // One pts layer (l = 1..7): unit ks+1 of the finished layer l-1 (in cx.hv) is made in the shadow of K-step ks.
 // (feature_linear is no layer of this kernel: it has no activation, so nerf_pack_split multiplies it into the views layer.)
-template <int P>
-__device__ __forceinline__ void layer_pass(f32x16 (&acc)[8], int l, Ctx& cx, const float* ipe_src) {
+template <int P, class Tap7 = Tap7Workspace>
+__device__ __forceinline__ void layer_pass(f32x16 (&acc)[8], int l, Ctx& cx, const float* ipe_src, const Tap7& tap7 = Tap7()) {
   if (l - 1 == cx.tap) dump_tap(l - 1, cx);
 #pragma unroll
   for (int ks = 0; ks < HS; ks += 2) {  // (pairs: the parity of a K-step's position in the stream is a template argument)
@@ -704,8 +718,9 @@ __device__ __forceinline__ void layer_pass(f32x16 (&acc)[8], int l, Ctx& cx, con
                  // views K-loop, the register allocator spilled ~150 registers per tile)
     // (a pass without colour heads has no K-loop behind this point: it does the same after the layer loop, behind tap_prefetch)
     if (cx.rgb) {
-      if (cx.tap == 7) dump_tap(7, cx);
+      if (cx.tap == 7 && !tap7.on) dump_tap(7, cx);
       alpha_head(cx);
+      if (tap7.on) tap7.fn(cx);  // (here and not behind the loop for the same reason; the eight accumulator blocks are free at this point)
     }
   }
 }
