@@ -630,6 +630,35 @@ int nm_gt_supervision(const float* pt3d, const float* K, const float* w2c, const
                       int B, int M, int N, int H, int W, int ds, float* pt2d_proj, int* gt_cell, uint8_t* conf_gt, int64_t* b_ids,
                       int64_t* i_ids, int64_t* j_ids, int* counts, void* workspace, size_t workspace_bytes, nmStream_t stream);
 
+/* Batched PnP-RANSAC (pnp.hip): the 2D-3D matches of Q queries -> Q world-to-camera poses, three launches, no host round trip.
+ *   pt2d [K,2] pixels, pt3d [K,3], grouped by query: query q owns matches [offsets[q], offsets[q+1]); offsets [Q+1] int32 on the DEVICE
+ *   (the kernels clamp every range to [0, K], so no offset value can make them leave the arrays); offsets_host: the same Q+1 values on the
+ *   host, or NULL -- when given they are checked (non-decreasing, inside [0, K]) before anything is enqueued.  Kmat [Q,3,3], upper
+ *   triangular (fx, skew, cx; fy, cy; the last row is taken as 0 0 1).  thr_px: inlier threshold in pixels; n_hyps: hypotheses per query,
+ *   a multiple of 64, at most 4096; refine_iters >= 0 Levenberg-Marquardt steps; add_half_px != 0: 0.5 is added to every pixel coordinate
+ *   (in fp32) before use.  pt2d / pt3d may be NULL only if K == 0.
+ * Outputs (device, caller-allocated): pose [Q,12] fp32 row-major [R | t] (world to camera); n_inliers [Q] int32 -- a value below 4 means
+ *   NO POSE (pose is then the identity): fewer than four matches, no hypothesis with four inliers, or a refined pose that keeps fewer than
+ *   four in the final fp64 recount; inlier_mask [K] uint8 or NULL (zero outside every query's range and for a query without a pose).
+ *   Study outputs, NULL in production: hyp_pose [Q,n_hyps,12] fp32, the hypotheses as K [R | t] (all NaN: the sample gave none), and
+ *   hyp_count [Q,n_hyps] int32, their inlier counts.
+ * Sampling.  Hypothesis h of a query with n >= 4 matches draws four distinct indices; slot s = 0..3 takes
+ *       hash4(seed, h, s, attempt) % n,   attempt = 0, 1, ... until the index differs from the earlier slots'
+ *   (after 64 attempts: the smallest unused index), where, in 32-bit unsigned arithmetic,
+ *       mix(x):  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+ *       hash4(seed, h, s, a) = mix(mix(mix(mix(seed ^ 0x9E3779B9) + h) + s) + a).
+ *   The hash does not see the query's position in the batch.  Slots 0..2 feed a P3P minimal solve in fp64; of its up to four roots the one
+ *   that reprojects slot 3 best (in front of the camera) is the hypothesis.  A point is an inlier of a hypothesis iff its depth is positive
+ *   and its squared pixel residual is <= thr_px^2 (fp32).  The winner maximises (count << 32) | (0xFFFFFFFF - h): most inliers, ties to
+ *   the lowest h.  It is refined in fp64 with the inlier set re-evaluated at every step; a step is taken iff the inlier count does not
+ *   fall and the cost of the step's inlier set falls.  All sums run in an order fixed by the query's own matches: the outputs of a query
+ *   are the same bits alone, in any batch, and on every run.
+ * workspace: nm_pnp_ransac_workspace_bytes(Q, n_hyps) bytes (NM_ERR_WORKSPACE).  Every check is made before anything is enqueued. */
+size_t nm_pnp_ransac_workspace_bytes(int Q, int n_hyps);
+int nm_pnp_ransac(const float* pt2d, const float* pt3d, const int* offsets, const int* offsets_host, const float* Kmat, int Q, int K,
+                  float thr_px, int n_hyps, int refine_iters, uint32_t seed, int add_half_px, float* pose, int* n_inliers,
+                  uint8_t* inlier_mask, float* hyp_pose, int* hyp_count, void* workspace, size_t workspace_bytes, nmStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

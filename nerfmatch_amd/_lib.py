@@ -134,6 +134,9 @@ SIGNATURES = {
     # ground-truth supervision of a training batch (supervision.hip)
     "nm_gt_supervision_workspace_bytes": (sz, [i32, i32, i32]),
     "nm_gt_supervision": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    # batched PnP-RANSAC (pnp.hip)
+    "nm_pnp_ransac_workspace_bytes": (sz, [i32, i32]),
+    "nm_pnp_ransac": (i32, [vp, vp, vp, vp, vp, i32, i32, f32, i32, i32, C.c_uint32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
 }
 
 NM_NERF_SKIP_RGB = 1

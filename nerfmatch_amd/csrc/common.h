@@ -101,6 +101,9 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// number of lanes of the wavefront whose predicate holds (ballot + popcount: scalar, the same value in every lane)
+__device__ __forceinline__ int wave_count(bool pred) { return __popcll(__ballot(pred)); }
+
 // Exchange between the two 32-lane halves of a wavefront without the LDS round trip of ds_bpermute (gfx950:
 // v_permlane32_swap_b32 swaps the upper half of its first operand with the lower half of its second).  After the call
 // lo = the value of lane (l & 31), hi = the value of lane (l & 31) + 32, in BOTH halves: op(lo, hi) is the xor-32 reduction.

@@ -8,8 +8,8 @@ New: a batch may hold Q > 1 queries (the reference's `batch_size` argument exist
 the Q queries are rendered and matched as ONE launch sequence, and eval_data_loader software-pipelines consecutive batches
 across the matcher's single synchronisation point.  Out of scope: the dataset classes -- pass
 `dataset_factory` (or any iterable of batch dicts with the reference's schema as `data_loader`) -- and visualisation.
-PnP-RANSAC is third-party CPU code (pycolmap / OpenCV): used when importable, otherwise `solver="none"` returns the
-2D-3D matches and no pose.  iNeRF refinement (`inerf_refinement`) runs on the HIP
+PnP-RANSAC: `solver="gpu"` is the native batched solver (pnp_gpu.py, csrc/pnp.hip); "colmap" (the default, as in the reference) and
+"cv2" are third-party CPU code (pycolmap / OpenCV), used when importable; `solver="none"` returns the 2D-3D matches and no pose.  iNeRF refinement (`inerf_refinement`) runs on the HIP
 forward/backward kernels of nerfmatch_amd/inerf.py, including its optional matching loss (`use_match_loss`, c2f matcher).
 """
 import contextlib
@@ -37,7 +37,8 @@ def parse_nerf_stop_layer(scene_dir):
 
 
 def _solve_pnp(solver, pt2d, pt3d, K, rthres, center_subpixel):
-    """Returns (R, t, inliers) of the w2c pose or None.  Third-party CPU solvers, outside the hot path."""
+    """Returns (R, t, inliers) of the w2c pose or None, for ONE query.  "colmap" / "cv2": third-party CPU solvers; "gpu": the native
+    solver (pnp_gpu.py) -- a whole batch goes through _poses_from_matches' batched branch instead, this is the per-query route (iNeRF)."""
     if callable(solver):
         return solver(pt2d, pt3d, K, rthres)
     if len(pt2d) < 4:
@@ -50,6 +51,9 @@ def _solve_pnp(solver, pt2d, pt3d, K, rthres, center_subpixel):
         import cv2  # noqa: F401
         from .utils.pnp import estimate_pose
         return estimate_pose(pt2d, pt3d, K, ransac_thres=rthres)
+    if solver == "gpu":
+        from . import pnp_gpu
+        return pnp_gpu.solve_pnp(pt2d, pt3d, K, rthres=rthres, center_subpixel=center_subpixel)
     raise ValueError(f"{solver} is not supported!")
 
 
@@ -164,8 +168,76 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
             per.append((pix[q][i2d[sel]] if self.coarse_only else pix[q][i3d[sel]], pt3d[q][i3d[sel]]))
         return per
 
+    def _gpu_match_sets(self, batch, match_oracle):
+        """The match sets _poses_from_matches splits per query on the host, gathered on the device instead: -> (pt2d (n, 2), pt3d (n, 3),
+        per-query counts as host ints | sorted per-match query ids (n,) int64 on the device)."""
+        Q, dev = batch["image"].shape[0], self.device
+        if match_oracle or self.coarse_only:
+            pt3d = batch["pt3d"].to(dev).reshape(Q, -1, 3)
+            proj = batch.get("pt2d_proj")
+            if not match_oracle:
+                ids = batch["match_ids"]
+            elif "conf_gt" in batch:
+                ids = torch.where(batch["conf_gt"].to(dev))
+            else:  # the supervision of the batch's own geometry (as _oracle_matches), with the small per-query tensors taken to the device
+                from .supervision import supervision, w2c_from_c2w
+
+                on_dev = lambda k: None if batch.get(k) is None else batch[k].to(dev)
+                sup = supervision(pt3d, self._host(batch, "K").reshape(-1, 3, 3).to(dev), w2c_from_c2w(self._host(batch, "c2w").reshape(Q, -1, 4)).to(dev),
+                                  batch["image"].shape[-2:], ds=self.model.coarse_ds, pt_mask=on_dev("pt_mask"), im_mask=on_dev("im_mask"), dense=False)
+                ids, proj = sup["ids"], sup["pt2d_proj"]
+            bid, i2d, i3d = (t.to(dev) for t in ids)
+            if self.coarse_only:
+                return batch["pt2d"].to(dev)[bid, i2d], pt3d[bid, i3d], bid
+            return proj.to(dev)[bid, i3d], pt3d[bid, i3d], bid
+        pt2d, pt3d = batch["mpt2d_f"].detach(), batch["mpt3d"]
+        if "match_counts" in batch and batch["pt3d"].dim() == 3:
+            counts = [int(c) for c in batch["match_counts"]]
+            if sum(counts) == len(pt2d):  # (the coarse counts; a match list filtered by pred_mask is shorter: its ids say where it is cut)
+                return pt2d, pt3d, counts  # already on the host: validated there, no id scan
+        return pt2d, pt3d, batch["m_bids"] if Q > 1 else torch.zeros(len(pt2d), dtype=torch.int64, device=pt2d.device)
+
+    def _poses_gpu(self, batch, rthres, center_subpixel, match_oracle):
+        """solver="gpu": one nm_pnp_ransac call for the whole batch; Q x (12 + 1 + 1) numbers (pose, inlier count, match count) come back
+        through one pinned buffer.  A query with fewer than 4 inliers has no pose: (None, inf, inf, count), as a failed third-party solve."""
+        from . import pnp_gpu
+
+        Q = batch["image"].shape[0]
+        pt2d, pt3d, groups = self._gpu_match_sets(batch, match_oracle)
+        K = self._host(batch, "K").reshape(-1, 3, 3)
+        if not isinstance(groups, list):  # sorted per-match query ids: the offsets are built once, here, and serve the solver and the counts
+            groups = pnp_gpu.offsets_from_bids(groups.to(self.device).reshape(-1), Q)
+        w2c, n_inl, _ = pnp_gpu.solve_pnp_batch(pt2d, pt3d.to(self.device), groups, K, rthres=rthres, center_subpixel=center_subpixel)
+        cols = [w2c[:, :3].reshape(Q, 12), n_inl.reshape(Q, 1).float()]
+        if not isinstance(groups, list):
+            cols.append((groups[1:] - groups[:-1]).reshape(Q, 1).float())  # (match counts < 2^24: exact in fp32)
+        packed = torch.cat(cols, dim=1)
+        # one pinned buffer per evaluator, reused by every batch (it is read to the end below before the next solve is enqueued)
+        host = self.__dict__.get("_pnp_host")
+        if host is None or host.shape[0] < Q:
+            host = self.__dict__["_pnp_host"] = torch.empty(max(Q, 16), 14, dtype=torch.float32, pin_memory=True)
+        host = host[:Q, :packed.shape[1]]
+        host.copy_(packed, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        counts = groups if isinstance(groups, list) else host[:, 13].to(torch.int64).tolist()
+        inf = torch.tensor(float("inf"))
+        out = []
+        for q in range(Q):
+            if int(host[q, 12]) < 4:
+                out.append((None, inf, inf, counts[q]))
+                continue
+            w = torch.eye(4)
+            w[:3] = host[q, :12].reshape(3, 4)
+            c2w_est = torch.linalg.inv(w)
+            R_err, t_err = pose_err(self._host(batch, "c2w").reshape(-1, 4, 4)[q], c2w_est)
+            out.append((c2w_est, R_err, t_err, counts[q]))
+        return out
+
     def _poses_from_matches(self, batch, solver, rthres, center_subpixel, match_oracle=False):
-        """2D-3D matches of the batch -> per query (c2w_est | None, R_err, t_err, num_matches); PnP on the host (third party)."""
+        """2D-3D matches of the batch -> per query (c2w_est | None, R_err, t_err, num_matches).  solver="gpu": one batched solve on the
+        device (_poses_gpu); every other solver: the matches are split per query on the host and solved one after another."""
+        if solver == "gpu":
+            return self._poses_gpu(batch, rthres, center_subpixel, match_oracle)
         Q = batch["image"].shape[0]
         Ks = self._host(batch, "K").reshape(-1, 3, 3)
         inf = torch.tensor(float("inf"))

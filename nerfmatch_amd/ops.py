@@ -1113,3 +1113,28 @@ def gt_supervision(pt3d, K, w2c, pt_mask=None, im_mask=None, fallback=None, hw=N
                                   dptr(conf, torch.uint8), dptr(ids[0], torch.int64), dptr(ids[1], torch.int64), dptr(ids[2], torch.int64),
                                   dptr(counts, torch.int32), dptr(ws, torch.uint8), need, stream()), "nm_gt_supervision")
     return dict(pt2d_proj=proj, gt_cell=cell, conf_gt=conf, ids=tuple(ids) if triple else None, counts=counts)
+
+
+# ----------------------------------------------------------------------------- batched PnP-RANSAC (pnp.hip)
+_PNP_WS = {}
+
+
+def pnp_ransac(pt2d, pt3d, offsets, K, thr_px=1.0, n_hyps=1024, refine_iters=10, seed=0, add_half_px=False, want_inliers=False, study=False,
+               offsets_host=None):
+    """nm_pnp_ransac: pt2d (K,2), pt3d (K,3), offsets (Q+1,) int32 device, K (Q,3,3) -> pose (Q,12) fp32 [R|t] w2c, n_inliers (Q,) int32,
+    inlier_mask (K,) uint8 | None, and with study=True (hyp_pose (Q,n_hyps,12), hyp_count (Q,n_hyps)) else None.  offsets_host: the same
+    offsets as a list of Python ints (validated on the host before the launch) or None."""
+    Q, n = K.shape[0], pt2d.shape[0]
+    dev = K.device
+    pose = torch.empty(Q, 12, device=dev, dtype=torch.float32)
+    n_inl = torch.empty(Q, device=dev, dtype=torch.int32)
+    mask = torch.empty(n, device=dev, dtype=torch.uint8) if want_inliers else None
+    hyp = (torch.empty(Q, n_hyps, 12, device=dev, dtype=torch.float32), torch.empty(Q, n_hyps, device=dev, dtype=torch.int32)) if study else None
+    need = lib().nm_pnp_ransac_workspace_bytes(Q, int(n_hyps))
+    ws = _scratch(_PNP_WS, dev, need)
+    oh = None if offsets_host is None else (C.c_int * (Q + 1))(*[int(v) for v in offsets_host])
+    check(lib().nm_pnp_ransac(dptr(pt2d if n else None), dptr(pt3d if n else None), dptr(offsets, torch.int32), oh, dptr(K), Q, n, float(thr_px),
+                              int(n_hyps), int(refine_iters), int(seed) & 0xFFFFFFFF, int(bool(add_half_px)), dptr(pose), dptr(n_inl, torch.int32),
+                              dptr(mask, torch.uint8), dptr(hyp[0] if study else None), dptr(hyp[1] if study else None, torch.int32),
+                              dptr(ws, torch.uint8), need, stream()), "nm_pnp_ransac")
+    return pose, n_inl, mask, hyp

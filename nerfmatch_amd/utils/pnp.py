@@ -1,5 +1,5 @@
 """Thin wrappers over third-party CPU PnP-RANSAC solvers (used only when pycolmap / OpenCV are installed).
-Call signatures follow nerfmatch/utils/geometry.py:189-265; the solvers themselves are out of scope."""
+Call signatures follow nerfmatch/utils/geometry.py:189-265.  The native solver is nerfmatch_amd/pnp_gpu.py (solver="gpu")."""
 import numpy as np
 
 
