@@ -298,9 +298,8 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
       sm_dn[js] = dnorm;
     }
 
-    // start the weight stream: slots 0 and 1
-#pragma unroll
-    for (int g0 = 0; g0 < ring_ahead<P>(); ++g0) dma_slot<P>(blob_slots, g0, ring, wave, lane);
+    // start the weight stream
+    ring_open<P>(blob_slots, ring, wave, lane);
 
     // ---- integrated positional encoding -> B operands of the 6 IPE K-steps, parked in LDS -------------------------
     // K-slot (step m, half h, i) <-> encoding index f = 45 h + 8 m + i of the reference's order (8 m + i < 45; the last three slots of step 5
@@ -358,9 +357,7 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     cx.tap_pref = need_tap && !lo_pass && !early; cx.rgb = need_rgb;
     cx.tap_ring = ring + wave * SLOT_FLOATS; cx.tap_ipe = sm_ipe + wave * (XS * 2 * 64 * 4);
     if constexpr (is_split<P>()) {
-      // slots 0 and 1 landed (2 and 3 may stay in flight until the barrier of K-step 1), everybody's pieces: barrier
-      NM_WAIT_VMCNT(8);
-      __builtin_amdgcn_s_barrier();
+      ring_open_wait<P>(cx);
     } else {
       ring_acquire<P>(blob_slots, 0, nslots, ring, wave, lane);
     }
@@ -550,7 +547,7 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
         if constexpr (is_split<P>()) split8_p<P>(v8, exh[e], exl[e]);
         else exh[e] = exl[e] = pack8_f16(v8);
       }
-      views_extras<P>(av, cx, exh, exl);
+      views_extras<P>(av, cx, exh, exl, a.app_row == nullptr);
       TRACE(11);
       NM_MLP_DONE_WAIT();
       if (cx.tap_pref) tap_prefetch<0>(cx);

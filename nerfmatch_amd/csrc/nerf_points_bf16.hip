@@ -73,8 +73,7 @@ __device__ __forceinline__ void points_fwd_body(const PointsArgs& a) {
     __syncthreads();  // small block landed / the previous tile is through with the LDS
     const int sample = bid * TILE + wave * 32 + s;
     const size_t sc = (size_t)(sample < a.n ? sample : a.n - 1);
-#pragma unroll
-    for (int g0 = 0; g0 < ring_ahead<P>(); ++g0) dma_slot<P>(blob_slots, g0, ring, wave, lane);
+    ring_open<P>(blob_slots, ring, wave, lane);
     float vdir[3] = {0.f, 0.f, 0.f};  // "from rays": this sample's view direction (the views layer's extra inputs are made from it below)
     {  // the 6 IPE K-steps' B operands: this lane's 8 columns per step
       float* dst = sm_ipe + wave * (XS * 2 * 64 * 4) + lane * 4;
@@ -139,8 +138,7 @@ __device__ __forceinline__ void points_fwd_body(const PointsArgs& a) {
     cx.vmax = 0.f; cx.rng = nullptr; cx.sc = 1.f; cx.tap_pref = false; cx.rgb = true; cx.tap_ring = nullptr; cx.tap_ipe = nullptr;
     cx.gptr = a.gates + (size_t)bid * 9 * 256 + tid;
     cx.gbits[0] = cx.gbits[1] = cx.gbits[2] = cx.gbits[3] = 0u;
-    NM_WAIT_VMCNT(8);
-    __builtin_amdgcn_s_barrier();
+    ring_open_wait<P>(cx);
     load_half<P>(cx.opA, ring, lane, 0);
     const float* ipe_src = sm_ipe + wave * (XS * 2 * 64 * 4) + lane * 4;
     f32x16 acc[8];
@@ -187,7 +185,7 @@ __device__ __forceinline__ void points_fwd_body(const PointsArgs& a) {
         }
         split8_p<P>(v8, exh[e], exl[e]);
       }
-      views_extras<P>(av, cx, exh, exl);
+      views_extras<P>(av, cx, exh, exl, RAYS && a.app_row == nullptr);  // (!RAYS: the xd rows come from memory)
     }
     const float* bv = sm_small + OFF_BVIEWS + 4 * hh;
     const float* wr = sm_small + OFF_WRGB + 4 * hh;
@@ -334,8 +332,7 @@ __device__ __forceinline__ void points_bwd_body(const PointsArgs& a) {
     const int sample = bid * TILE + wave * 32 + s;
     const bool valid = sample < a.n;
     const size_t sc = (size_t)(valid ? sample : a.n - 1);
-#pragma unroll
-    for (int g0 = 0; g0 < ring_ahead<0>(); ++g0) dma_slot<0>(blob_slots, g0, ring, wave, lane);
+    ring_open<0>(blob_slots, ring, wave, lane);
     const u32x4* gt = a.gates + (size_t)bid * 9 * 256 + tid;
     const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.g4 + sc * 4);
     Ctx cx;
@@ -364,8 +361,7 @@ __device__ __forceinline__ void points_bwd_body(const PointsArgs& a) {
           }
         }
     }
-    NM_WAIT_VMCNT(8);
-    __builtin_amdgcn_s_barrier();
+    ring_open_wait<0>(cx);
     load_half<0>(cx.opA, ring, lane, 0);
     const u32x4 none = {0u, 0u, 0u, 0u};
     f32x16 acc[8];

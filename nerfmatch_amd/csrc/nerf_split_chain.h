@@ -103,18 +103,15 @@ __device__ __forceinline__ void ring_acquire(const char* blob_slots, int g, int 
 // (scripts/trace_nerf.py on the -DNM_ABL=2 build of scripts/variants/nerf_study_switches_r6.patch) put the per-K-step barrier at 196 of a K-step's 1150 cycles -- more than the weight DMA
 // (81), the operand reads (160) or the re-packing (143): four wavefronts on four SIMDs re-synchronised every 24 MFMAs pay the
 // slowest one's stalls every time.  Called in the middle of every ODD K-step g (8-block layers; at the start of it in the views
-// layer): slots g+1 and g+2 -- requested two K-steps ago, right behind the previous barrier -- must have landed (this wavefront's
-// pieces: vmcnt(0); everybody's: the barrier); then slots g+3 and g+4 are requested into the ring positions of slots g-1 and g,
-// whose last reads (the second-half operands of slot g, fetched in the first half of K-step g) every wavefront issued before it
-// arrived here.  The 4-slot ring suffices: two slots in use, two in flight.
-template <int P>
-__device__ __forceinline__ void ring_acquire_two(const char* blob_slots, int g, float* ring, int wave, int lane) {
+// layer): slots g+1 and g+2 -- requested one K-step ago, in the first half of K-step g-1 (ring_request) -- must have landed (this
+// wavefront's pieces: vmcnt(0); everybody's: the barrier).  Behind it the ring positions of slots g-1 and g are free for good: their
+// last reads (the second-half operands of slot g, fetched in the first half of K-step g) every wavefront issued before it arrived
+// here.  The 4-slot ring suffices: two slots in use, two in flight.
+__device__ __forceinline__ void ring_acquire_two() {
   // lgkmcnt(0): this wavefront's own reads of slot g (issued 8 MFMAs ago) have RETURNED before it signals the barrier -- the DMA
-  // another wavefront issues right behind the barrier overwrites that ring position
+  // another wavefront issues behind the barrier overwrites that ring position
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  dma_slot<P>(blob_slots, g + 3, ring, wave, lane);
-  dma_slot<P>(blob_slots, g + 4, ring, wave, lane);
 }
 
 // fp16x1, called in every EVEN K-step g: slots g+1 and g+2 have landed when at most the 6 DMA instructions of slots g+3..g+5
@@ -161,6 +158,8 @@ struct Ctx {
   int nslots, wave, lane, hi;
   int tap;          // layer whose activations are tapped (-1: none)
   int g;            // next weight slot
+  unsigned dma_voff;  // split modes, ring_request: this lane's byte offset inside a slot (its wavefront's quarter + 16 lane) and
+  unsigned dma_lds;   //   the LDS byte address of its wavefront's quarter of ring position 0 (uniform: an SGPR); set by ring_open_wait
   OpHalf opA;       // A operands of the next half slot, fetched one half slot ahead
   OpHalf opB;       // fp16x1: blocks 4-7 of the next slot (the whole slot is fetched one K-step ahead there)
   Unit xn;          // B operands of the next hidden K-step
@@ -173,6 +172,51 @@ struct Ctx {
   unsigned gbits[4]; // P = 4: ReLU gates of the layer being re-packed, 8 bits per unit (bit k < 4: element 2k, bit 4 + k: element 2k + 1)
   float hv[128];    // finished layer (raw accumulators, before bias/relu), lane local: hv[16 block + register]
 };
+
+// Split modes: every EVEN K-step g requests slots g+2 and g+3 into the ring positions of slots g-2 and g-1, which the barrier of K-step
+// g-1 freed -- one of the eight pieces behind each of eight MFMAs that carry little else (8-block layers: the tail of the first half;
+// views layer: MFMAs 4..11), and not as a burst right behind that barrier: eight pieces back to back were ~250 cycles in which this SIMD
+// issued no MFMA, paid by all four wavefronts together because the barrier had just re-aligned them.  The barrier of K-step g+1
+// (ring_acquire_two: vmcnt(0)) retires them, a K-step of ~1100 cycles after the request against 250-400 of L2-warm landing time.  A
+// tile opens with slots 0 and 1 (ring_open); past its last slot the stream runs on into the blob's padding, branch free.
+// Piece j & 3 of slot g + 2 + (j >> 2): the same address, M0 and immediate offsets as dma_slot's four.  Inline asm like tap_prefetch
+// (nerf_fwd_bf16.hip), M0 handed back as found: the compiler cannot tell these LDS writes from the operands the next ds_read fetches
+// and may wait vmcnt(0) in front of it; and the address is the uniform slot base in an SGPR pair plus the lane's 32-bit offset -- no
+// 64-bit VGPR pair kept alive beside the accumulators (the pointwise backward has none to spare).  One asm statement per piece and no
+// sched_barrier of its own where a work piece shares the gap: the K-loops' bodies are close to the size up to which `#pragma unroll`
+// unrolls fully, and a loop left rolled indexes cx.hv at run time -- Ctx in scratch.
+template <int P>
+__device__ __forceinline__ void ring_request(const Ctx& cx, int g, int j) {
+  const int slot = g + 2 + (j >> 2);
+  const char* base = cx.blob_slots + (size_t)slot * slot_bytes<P>();  // uniform
+  const unsigned lds = cx.dma_lds + (unsigned)(slot & (ring_slots<P>() - 1)) * slot_bytes<P>();
+  unsigned m0_saved;
+#define NM_DMA_PIECE(OFS)                                                                                                        \
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %2, %3 offset:" #OFS "\n\ts_mov_b32 m0, %0" \
+               : "=&s"(m0_saved) : "s"(lds), "v"(cx.dma_voff), "s"(base) : "memory")
+  switch (j & 3) {  // (a compile-time constant after unrolling)
+    case 0: NM_DMA_PIECE(0); break;
+    case 1: NM_DMA_PIECE(1024); break;
+    case 2: NM_DMA_PIECE(2048); break;
+    default: NM_DMA_PIECE(3072); break;
+  }
+#undef NM_DMA_PIECE
+}
+// Opens a tile's weight stream: the slots K-step 0 does not request itself
+template <int P>
+__device__ __forceinline__ void ring_open(const char* blob_slots, float* ring, int wave, int lane) {
+#pragma unroll
+  for (int g0 = 0; g0 < (is_split<P>() ? 2 : ring_ahead<P>()); ++g0) dma_slot<P>(blob_slots, g0, ring, wave, lane);
+}
+// ... and waits for them (split modes), everybody's pieces: barrier
+template <int P>
+__device__ __forceinline__ void ring_open_wait(Ctx& cx) {
+  cx.dma_voff = (unsigned)(cx.wave * (slot_bytes<P>() / 4) + cx.lane * 16);
+  const float* q = cx.ring + cx.wave * (slot_floats<P>() / 4);
+  cx.dma_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)q);
+  NM_WAIT_VMCNT(0);
+  __builtin_amdgcn_s_barrier();
+}
 
 // 8 gate bits of one unit from its four packed hi words (two bf16 halves each): bit k = low half of word k non-zero, bit 4 + k = high half
 __device__ __forceinline__ unsigned gate_byte(const u32x4& h) {
@@ -429,8 +473,8 @@ __device__ __forceinline__ void slot_step8_one(f32x16 (&acc)[8], Ctx& cx, const 
 
 // One K-step (slot cx.g) of an 8-block layer, software pipelined over half slots with a "consume first" order: every
 // batch of LDS reads is issued right AFTER four MFMAs that use the previously fetched operands:
-//   head(blocks 0-3, A) | fetch B = blocks 4-7 of slot g | tail(blocks 0-3, A)
-//   ring barrier of slot g+1 (+ DMA of slot g+3)
+//   head(blocks 0-3, A) | fetch B = blocks 4-7 of slot g | tail(blocks 0-3, A) [even position: + the DMA pieces of slots g+2, g+3]
+//   odd position: ring barrier of slots g+1, g+2
 //   head(blocks 4-7, B) | fetch A = blocks 0-3 of slot g+1 | tail(blocks 4-7, B)
 // work(j), j = 0..11, is VALU work independent of this slot's second half (re-packing of a later K-step's B operands);
 // piece j is issued right behind the j-th MFMA of the second half.
@@ -449,9 +493,19 @@ __device__ __forceinline__ void slot_step8(f32x16 (&acc)[8], Ctx& cx, const bf16
   load_half<P>(B, cx.ring + (g & (NRING - 1)) * SLOT_FLOATS, cx.lane, 1);
   work.prefetch();
   __builtin_amdgcn_sched_barrier(0);
-  mfma_tail<P, 8>(acc, 0, cx.opA, xh, xl);
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (!EVEN) ring_acquire_two<P>(cx.blob_slots, g, cx.ring, cx.wave, cx.lane);
+  if constexpr (EVEN) {  // mfma_tail with this K-step's weight request in its gaps
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+      acc[o & 3] = mfma_p<P>(o < 4 ? cx.opA.h[o & 3] : cx.opA.l[o & 3], o < 4 ? xl : xh, acc[o & 3]);
+      ring_request<P>(cx, g, o);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else {
+    mfma_tail<P, 8>(acc, 0, cx.opA, xh, xl);
+    __builtin_amdgcn_sched_barrier(0);
+    ring_acquire_two();
+    __builtin_amdgcn_sched_barrier(0);  // (the second half's first MFMA stays behind the barrier)
+  }
   // from here to the end of the K-step: ONE basic block (the work pieces must not be separated from their MFMAs)
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
@@ -512,7 +566,8 @@ __device__ __forceinline__ void slot_step4(f32x16 (&acc)[4], Ctx& cx, const bf16
   const int g = cx.g;
   const OpHalf C = cx.opA;
   work.prefetch();
-  if constexpr (!EVEN) ring_acquire_two<P>(cx.blob_slots, g, cx.ring, cx.wave, cx.lane);
+  if constexpr (!EVEN) ring_acquire_two();
+  // (an even position's weight request rides in gaps 4..11, behind the operand fetch)
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
     acc[o] = mfma_p<P>(C.h[o], xh, FIRST ? zero : acc[o]);
@@ -526,6 +581,7 @@ __device__ __forceinline__ void slot_step4(f32x16 (&acc)[4], Ctx& cx, const bf16
   for (int o = 0; o < 4; ++o) {
     acc[o] = mfma_p<P>(C.h[o], xl, acc[o]);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (EVEN) ring_request<P>(cx, g, o);
     work(4 + o);
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -533,6 +589,7 @@ __device__ __forceinline__ void slot_step4(f32x16 (&acc)[4], Ctx& cx, const bf16
   for (int o = 0; o < 4; ++o) {
     acc[o] = mfma_p<P>(C.l[o], xh, acc[o]);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (EVEN) ring_request<P>(cx, g, 4 + o);
     work(8 + o);
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -564,6 +621,7 @@ __device__ __forceinline__ void slot_step4x2(f32x16 (&av)[4], Ctx& cx, const bf1
   for (int o = 0; o < 4; ++o) {
     av[o] = mfma_p<P>(A.h[o], x0l, av[o]);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (EVEN) ring_request<P>(cx, g, o);
     w0(4 + o);
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -571,11 +629,15 @@ __device__ __forceinline__ void slot_step4x2(f32x16 (&av)[4], Ctx& cx, const bf1
   for (int o = 0; o < 4; ++o) {
     av[o] = mfma_p<P>(A.l[o], x0h, av[o]);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (EVEN) ring_request<P>(cx, g, 4 + o);
     w0(8 + o);
     __builtin_amdgcn_sched_barrier(0);
   }
-  // (all reads of this slot are issued: the barrier below may hand its ring position to slot g + 4)
-  if constexpr (!EVEN) ring_acquire_two<P>(cx.blob_slots, g, cx.ring, cx.wave, cx.lane);
+  // (all reads of this slot are issued: the barrier below frees its ring position for the K-step after next)
+  if constexpr (!EVEN) {
+    ring_acquire_two();
+    __builtin_amdgcn_sched_barrier(0);
+  }
   const bf16x8 x1h = __builtin_bit_cast(bf16x8, u1.h), x1l = __builtin_bit_cast(bf16x8, u1.l);
   w1.prefetch();
 #pragma unroll
@@ -635,20 +697,20 @@ __device__ __forceinline__ void views_hidden(f32x16 (&av)[4], Ctx& cx) {
     }
   }
 }
-// The three extra K-steps (direction encoding, appearance row, padding): split modes with NM_VIEWS_PAIRS -- the first two share a slot
+// The three extra K-steps (direction encoding, appearance row, padding): split modes with NM_VIEWS_PAIRS -- the first two share a slot.
+// no_app (wavefront-uniform: the launch has no appearance row): inputs 32..47 are all zero, and the third K-step, which would add exact
+// zeros, is left out with its barrier -- it is the tile's last, so nothing behind it counts stream positions (cx.g starts over).
 template <int P>
-__device__ __forceinline__ void views_extras(f32x16 (&av)[4], Ctx& cx, const bf16x8 (&eh)[VS], const bf16x8 (&el)[VS]) {
+__device__ __forceinline__ void views_extras(f32x16 (&av)[4], Ctx& cx, const bf16x8 (&eh)[VS], const bf16x8 (&el)[VS], bool no_app) {
   if constexpr (is_split<P>()) {
     Unit u1;
     u1.h = __builtin_bit_cast(u32x4, eh[1]); u1.l = __builtin_bit_cast(u32x4, el[1]);
     slot_step4x2<P, false, true>(av, cx, eh[0], el[0], u1, NoWork{}, NoWork{});   // stream position NSLOT_NORGB + 8: even
-    slot_step4<P, false, false>(av, cx, eh[2], el[2], NoWork{});                  // a single half slot at an odd position
+    if (!no_app) slot_step4<P, false, false>(av, cx, eh[2], el[2], NoWork{});     // a single half slot at an odd position
   } else {
-#pragma unroll
-    for (int e = 0; e < VS; ++e) {
-      if (e & 1) slot_step4<P, false, false>(av, cx, eh[e], el[e], NoWork{});  // (the views layer's extra K-steps sit at positions 16, 17, 18)
-      else slot_step4<P, false, true>(av, cx, eh[e], el[e], NoWork{});
-    }
+    slot_step4<P, false, true>(av, cx, eh[0], el[0], NoWork{});  // (the views layer's extra K-steps sit at positions 16, 17, 18)
+    slot_step4<P, false, false>(av, cx, eh[1], el[1], NoWork{});
+    if (!no_app) slot_step4<P, false, true>(av, cx, eh[2], el[2], NoWork{});
   }
 }
 
