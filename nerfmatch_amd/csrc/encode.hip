@@ -16,8 +16,7 @@
 #include "nerf_bf16_common.h"
 
 namespace {
-
-constexpr float HALF_PI_F32 = 1.57079637050628662109375f;  // fl32(0.5 * pi): the reference adds a python float to an fp32 tensor
+using nmsample::HALF_PI_F32;  // (nerf_sample.h, through nerf_bf16_common.h)
 
 // one thread per (row, s, axis): both halves of the encoding (phase 0 and fl32(pi/2))
 template <int ARITH>

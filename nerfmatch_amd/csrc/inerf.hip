@@ -10,31 +10,27 @@
 // Samples s >= S_act are not evaluated: with the reference's randomized resampler the intervals s > S/2 have zero
 // width, i.e. weight 0 and -- because d(alpha)/d(sigma) = delta exp(-sigma delta) = 0 and delta = dz |d| with dz = 0 --
 // gradient exactly 0 (cf. NM_NERF_ZERO_TAIL).  S_act = S evaluates everything.
-#include "common.h"
+#include "nerf_sample.h"
 
 namespace {
+// the sample math the render and points kernels inline too (nerf_sample.h)
+using nmsample::HALF_PI_F32, nmsample::frustum, nmsample::ray_consts, nmsample::ray_norm, nmsample::lift_var, nmsample::ipe_exact, nmsample::ipe_damp_exact;
+using nmsample::view_row_value, nmsample::attenuation, nmsample::alpha_of, nmsample::trans_factor, nmsample::sigmoid;
 
 constexpr int XI = 96;   // IPE columns (90 used)
 constexpr int XD = 48;   // view-direction PE (27) | appearance row (16) | padding
-constexpr float HALF_PI_F = 1.57079637050628662109375f;
 
 struct Gauss {
   float t_mean, var[3];
 };
 
-// conical frustum -> Gaussian of interval [t0, t1] (render_utils.py:365-374, :326-339); d = rays[3:6]
-__device__ __forceinline__ Gauss frustum(float t0, float t1, const float* d, float radius) {
-  const float mu = (t0 + t1) / 2.0f, hw = (t1 - t0) / 2.0f;
-  const float mu2 = mu * mu, hw2 = hw * hw, hw4 = hw2 * hw2;
-  const float denom = fmaxf(1.1920928955078125e-07f, 3.0f * mu2 + hw2);
+// Gaussian of interval [t0, t1] of the ray with direction d = rays[3:6]: t_mean and the lifted covariance (nerf_sample.h)
+__device__ __forceinline__ Gauss gauss_of(float t0, float t1, const float* d, float radius) {
   Gauss g;
-  g.t_mean = mu + (2.0f * mu * hw2) / denom;
-  const float t_var = hw2 / 3.0f - (float)(4.0 / 15.0) * ((hw4 * (12.0f * mu2 - hw2)) / (denom * denom));
-  const float r_var = (radius * radius) * ((mu2 / 4.0f + (float)(5.0 / 12.0) * hw2) - (float)(4.0 / 15.0) * hw4 / denom);
-  const float dsq[3] = {d[0] * d[0], d[1] * d[1], d[2] * d[2]};
-  const float dmag = fmaxf(1e-10f, (dsq[0] + dsq[1]) + dsq[2]);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) g.var[a] = t_var * dsq[a] + r_var * (1.0f - dsq[a] / dmag);
+  float t_var, r_var, dsq[3], nul[3], dnorm;
+  frustum(t0, t1, radius, g.t_mean, t_var, r_var);
+  ray_consts(d, dsq, nul, dnorm);  // (dnorm: unused here)
+  lift_var(t_var, r_var, dsq, nul, 0.f, g.var);
   return g;
 }
 
@@ -49,32 +45,19 @@ __global__ void inerf_encode_kernel(const float* __restrict__ rays, const float*
   const int r = (int)(n / Sa), s = (int)(n % Sa);
   const float* rp = rays + (size_t)r * 12;
   if (i < 15) {
-    const Gauss g = frustum(z[(size_t)r * (S + 1) + s], z[(size_t)r * (S + 1) + s + 1], rp + 3, rp[11]);
+    const Gauss g = gauss_of(z[(size_t)r * (S + 1) + s], z[(size_t)r * (S + 1) + s + 1], rp + 3, rp[11]);
     const float sc = (float)(1 << i);
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) {
       const float mean = rp[ax] + g.t_mean * rp[8 + ax];
       const float xe = mean * sc;
-      const float damp = expf(-0.5f * (g.var[ax] * (sc * sc)));
-      xi[n * XI + i * 3 + ax] = damp * nm_sinf(xe);
-      xi[n * XI + 45 + i * 3 + ax] = damp * nm_sinf(xe + HALF_PI_F);
+      xi[n * XI + i * 3 + ax] = ipe_exact(xe, g.var[ax], sc);
+      xi[n * XI + 45 + i * 3 + ax] = ipe_exact(xe + HALF_PI_F32, g.var[ax], sc);
     }
   } else {
 #pragma unroll
     for (int f = 90; f < XI; ++f) xi[n * XI + f] = 0.f;
-    for (int c = 0; c < XD; ++c) {
-      float v = 0.f;
-      if (c < 24) {
-        const int k = (c % 12) / 3, ax = c % 3;
-        const float xe = rp[8 + ax] * (float)(1 << k);
-        v = nm_sinf(c < 12 ? xe : xe + HALF_PI_F);
-      } else if (c < 27) {
-        v = rp[8 + (c - 24)];
-      } else if (c < 43) {
-        v = app_row ? app_row[c - 27] : 0.f;
-      }
-      xd[n * XD + c] = v;
-    }
+    for (int c = 0; c < XD; ++c) xd[n * XD + c] = view_row_value(c, rp[8 + c % 3], app_row);
   }
 }
 
@@ -95,7 +78,7 @@ __global__ void __launch_bounds__(256) inerf_encode_bwd_kernel(const float* __re
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* rp = rays + (size_t)r * 12;
   for (int sidx = tid; sidx < Sa; sidx += 256) {
-    const Gauss g = frustum(z[(size_t)r * (S + 1) + sidx], z[(size_t)r * (S + 1) + sidx + 1], rp + 3, rp[11]);
+    const Gauss g = gauss_of(z[(size_t)r * (S + 1) + sidx], z[(size_t)r * (S + 1) + sidx + 1], rp + 3, rp[11]);
     gauss[sidx][0] = g.t_mean;
     gauss[sidx][1] = g.var[0];
     gauss[sidx][2] = g.var[1];
@@ -117,7 +100,7 @@ __global__ void __launch_bounds__(256) inerf_encode_bwd_kernel(const float* __re
     const float sc = (float)(1 << i);
     const float mean = oa + t_mean * va;
     const float xe = mean * sc;
-    const float damp = expf(-0.5f * (var * (sc * sc)));
+    const float damp = ipe_damp_exact(var, sc);
     // d/dx [damp sin(x)] = damp cos(x);  d/dx [damp sin(fl(x + pi/2))] = damp cos(fl(x + pi/2)) = -damp sin(x) up to the rounding of the
     // argument (<= 1 ulp of x in the phase: 1e-7 relative on a GRADIENT) -- one range reduction serves both
     float sn, cs;
@@ -165,14 +148,12 @@ __global__ void __launch_bounds__(256) inerf_encode_bwd_kernel(const float* __re
     float gv = acc[3 + ax] + acc[6 + 24 + ax];
     for (int k = 0; k < 4; ++k) {
       const float sc = (float)(1 << k);
-      gv += (acc[6 + k * 3 + ax] * nm_cosf(v * sc) + acc[6 + 12 + k * 3 + ax] * nm_cosf(v * sc + HALF_PI_F)) * sc;
+      gv += (acc[6 + k * 3 + ax] * nm_cosf(v * sc) + acc[6 + 12 + k * 3 + ax] * nm_cosf(v * sc + HALF_PI_F32)) * sc;
     }
     g_o[(size_t)r * 3 + ax] = acc[ax];
     g_v[(size_t)r * 3 + ax] = gv;
   }
 }
-
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // one thread per ray: rgb_map = sum_s w_s c_s + (1 - sum_s w_s)   (white background, render_utils.py:224-225)
 __global__ void inerf_composite_kernel(const float* __restrict__ logit, const float* __restrict__ sig, int ld, const float* __restrict__ z,
@@ -181,18 +162,17 @@ __global__ void inerf_composite_kernel(const float* __restrict__ logit, const fl
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
   const float* rp = rays + (size_t)r * 12;
-  const float dn = sqrtf((rp[3] * rp[3] + rp[4] * rp[4]) + rp[5] * rp[5]);
+  const float dn = ray_norm(rp + 3);
   float T = 1.f, acc = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
   for (int s = 0; s < Sa; ++s) {
     const size_t n = (size_t)r * Sa + s;
-    const float sg = fmaxf(sig[n * ld], 0.f);
     const float delta = (z[(size_t)r * (S + 1) + s + 1] - z[(size_t)r * (S + 1) + s]) * dn;
-    const float alpha = 1.0f - expf(-sg * delta);
+    const float alpha = alpha_of(sig[n * ld], delta);
     const float w = alpha * T;
     if (w_out) w_out[n] = w;
-    c0 += w * sigmoidf(logit[n * ld]); c1 += w * sigmoidf(logit[n * ld + 1]); c2 += w * sigmoidf(logit[n * ld + 2]);
+    c0 += w * sigmoid(logit[n * ld]); c1 += w * sigmoid(logit[n * ld + 1]); c2 += w * sigmoid(logit[n * ld + 2]);
     acc += w;
-    T *= (1.0f - alpha) + 1e-10f;
+    T *= trans_factor(alpha);
   }
   rgb_map[(size_t)r * 3] = c0 + (1.0f - acc);
   rgb_map[(size_t)r * 3 + 1] = c1 + (1.0f - acc);
@@ -208,16 +188,15 @@ __global__ void inerf_composite_bwd_kernel(const float* __restrict__ logit, cons
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
   const float* rp = rays + (size_t)r * 12;
-  const float dn = sqrtf((rp[3] * rp[3] + rp[4] * rp[4]) + rp[5] * rp[5]);
+  const float dn = ray_norm(rp + 3);
   const float G0 = G[(size_t)r * 3], G1 = G[(size_t)r * 3 + 1], G2 = G[(size_t)r * 3 + 2];
   // forward sweep: park T_s in g_sig column 1 (scratch, cleared below)
   float T = 1.f;
   for (int s = 0; s < Sa; ++s) {
     const size_t n = (size_t)r * Sa + s;
-    const float sg = fmaxf(sig[n * ld], 0.f);
     const float delta = (z[(size_t)r * (S + 1) + s + 1] - z[(size_t)r * (S + 1) + s]) * dn;
     g_sig[n * ld + 1] = T;
-    T *= (1.0f - (1.0f - expf(-sg * delta))) + 1e-10f;
+    T *= trans_factor(alpha_of(sig[n * ld], delta));
   }
   // backward sweep: rgb_map = 1 + sum_s w_s (c_s - 1), w_s = alpha_s T_s, T_s = prod_{j<s} u_j, u = 1 - alpha + 1e-10
   float B = 0.f, gnorm = 0.f;  // B = sum_{s > j} q_s w_s
@@ -227,12 +206,12 @@ __global__ void inerf_composite_bwd_kernel(const float* __restrict__ logit, cons
     const float sg = fmaxf(raw, 0.f);
     const float dz = z[(size_t)r * (S + 1) + s + 1] - z[(size_t)r * (S + 1) + s];
     const float delta = dz * dn;
-    const float ex = expf(-sg * delta);
-    const float alpha = 1.0f - ex;
-    const float u = (1.0f - alpha) + 1e-10f;
+    const float ex = attenuation(raw, delta);
+    const float alpha = 1.0f - ex;  // (alpha_of's expression, from the ex the gradient needs anyway)
+    const float u = trans_factor(alpha);
     const float Ts = g_sig[n * ld + 1];
     const float w = alpha * Ts;
-    const float c0 = sigmoidf(logit[n * ld]), c1 = sigmoidf(logit[n * ld + 1]), c2 = sigmoidf(logit[n * ld + 2]);
+    const float c0 = sigmoid(logit[n * ld]), c1 = sigmoid(logit[n * ld + 1]), c2 = sigmoid(logit[n * ld + 2]);
     float q = (G0 * (c0 - 1.0f) + G1 * (c1 - 1.0f)) + G2 * (c2 - 1.0f);  // d loss / d w_s
     if (g_w) q += g_w[n];
     g_logit[n * ld] = G0 * w * (c0 * (1.0f - c0));
@@ -273,9 +252,9 @@ __device__ __forceinline__ CmpSample cmp_sample(const float* __restrict__ out4, 
   c.sg = fmaxf(c.raw, 0.f);
   c.dz = valid ? zr[sidx + 1] - zr[sidx] : 0.f;
   c.delta = c.dz * dn;
-  c.ex = expf(-c.sg * c.delta);
-  c.alpha = valid ? 1.0f - c.ex : 0.f;
-  c.u = (1.0f - c.alpha) + 1e-10f;
+  c.ex = attenuation(c.raw, c.delta);
+  c.alpha = valid ? 1.0f - c.ex : 0.f;  // (alpha_of's expression, from the ex the backward needs anyway)
+  c.u = trans_factor(c.alpha);
   return c;
 }
 // inclusive prefix product over the lanes; returns it, *excl = the exclusive one (1 in lane 0)
@@ -298,7 +277,7 @@ __global__ void __launch_bounds__(256) inerf_composite4_kernel(const float* __re
   if (r >= R) return;
   const float* rp = rays + (size_t)r * 12;
   const float* zr = z + (size_t)r * (S + 1);
-  const float dn = sqrtf((rp[3] * rp[3] + rp[4] * rp[4]) + rp[5] * rp[5]);
+  const float dn = ray_norm(rp + 3);
   float T0 = 1.f, acc = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
   for (int base = 0; base < Sa; base += 64) {
     const int sidx = base + lane;
@@ -309,7 +288,7 @@ __global__ void __launch_bounds__(256) inerf_composite4_kernel(const float* __re
     const float p = prefix_prod(c.u, lane, &excl);
     const float w = c.alpha * (T0 * excl);
     if (w_out && valid) w_out[n] = w;
-    c0 += w * sigmoidf(c.o[0]); c1 += w * sigmoidf(c.o[1]); c2 += w * sigmoidf(c.o[2]);
+    c0 += w * sigmoid(c.o[0]); c1 += w * sigmoid(c.o[1]); c2 += w * sigmoid(c.o[2]);
     acc += w;
     T0 *= __shfl(p, 63, 64);
   }
@@ -332,7 +311,7 @@ __global__ void __launch_bounds__(256) inerf_composite4_bwd_kernel(const float* 
   if (r >= R) return;
   const float* rp = rays + (size_t)r * 12;
   const float* zr = z + (size_t)r * (S + 1);
-  const float dn = sqrtf((rp[3] * rp[3] + rp[4] * rp[4]) + rp[5] * rp[5]);
+  const float dn = ray_norm(rp + 3);
   const float G0 = G[(size_t)r * 3], G1 = G[(size_t)r * 3 + 1], G2 = G[(size_t)r * 3 + 2];
   // forward sweep: the transmittance at the start of every chunk
   float carry[CMP_MAX_CHUNKS];
@@ -363,7 +342,7 @@ __global__ void __launch_bounds__(256) inerf_composite4_bwd_kernel(const float* 
     prefix_prod(c.u, lane, &excl);
     const float Ts = carry[k] * excl;
     const float w = c.alpha * Ts;
-    const float s0 = sigmoidf(c.o[0]), s1 = sigmoidf(c.o[1]), s2 = sigmoidf(c.o[2]);
+    const float s0 = sigmoid(c.o[0]), s1 = sigmoid(c.o[1]), s2 = sigmoid(c.o[2]);
     float q = (G0 * (s0 - 1.0f) + G1 * (s1 - 1.0f)) + G2 * (s2 - 1.0f);  // d loss / d w_s
     if (g_w && valid) q += g_w[n];
     const float qw = valid ? q * w : 0.f;
@@ -414,7 +393,7 @@ __global__ void __launch_bounds__(256) inerf_ray_sums_kernel(const float* __rest
   if (c < 3) {
     float acc = 0.f;
     for (int s = 0; s < Sa; ++s) {
-      const Gauss g = frustum(z[(size_t)r * (S + 1) + s], z[(size_t)r * (S + 1) + s + 1], rp + 3, rp[11]);
+      const Gauss g = gauss_of(z[(size_t)r * (S + 1) + s], z[(size_t)r * (S + 1) + s + 1], rp + 3, rp[11]);
       acc += wr[s] * (rp[3 + c] * g.t_mean + rp[c]);
     }
     pts[(size_t)r * 3 + c] = acc;
@@ -442,7 +421,7 @@ __global__ void __launch_bounds__(256) inerf_ray_sums_bwd_kernel(const float* __
   for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
   if (lane == 0) {
     const float* rp = rays + (size_t)r * 12;
-    const Gauss g = frustum(z[(size_t)r * (S + 1) + s], z[(size_t)r * (S + 1) + s + 1], rp + 3, rp[11]);
+    const Gauss g = gauss_of(z[(size_t)r * (S + 1) + s], z[(size_t)r * (S + 1) + s + 1], rp + 3, rp[11]);
 #pragma unroll
     for (int a = 0; a < 3; ++a) dot += g_pts[(size_t)r * 3 + a] * (rp[3 + a] * g.t_mean + rp[a]);
     g_w[n] = dot;

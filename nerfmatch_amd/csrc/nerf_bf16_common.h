@@ -3,9 +3,12 @@
 // types, split8, pack_bf16, nrow, MFMA_BF16 -- is bf16x3.h).
 #pragma once
 #include "bf16x3.h"
+#include "nerf_sample.h"
 #include <string.h>
 
 namespace nmbf {
+using nmsample::launder;  // (one definition for every NeRF kernel: nerf_sample.h)
+using nmsample::sin32;
 
 constexpr int TILE = 128;
 constexpr int SLOT_BYTES = 16384;
@@ -77,11 +80,7 @@ struct NerfArgs {
 #define NM_TRACE 0
 #endif
 
-__device__ __forceinline__ int launder(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-// the same for a wavefront-uniform value that must stay in an SGPR
+// (launder: nerf_sample.h)  The same for a wavefront-uniform value that must stay in an SGPR
 __device__ __forceinline__ int launder_s(int v) {
   asm volatile("" : "+s"(v));
   return v;
@@ -109,23 +108,5 @@ template <class T>
 __device__ __forceinline__ void pin(T& v) {
   asm volatile("" : "+v"(v));
 }
-// fp32 sine for the positional encoding: q = rint(x / pi), 4-term Cody-Waite reduction (q * 3.140625 is exact up to
-// q = 2^16), odd polynomial of degree 9 (SLEEF's sinf coefficients).  |error| <= 1e-7 for |x| < 6.5e4 (checked against
-// fp64 on 8e4 random arguments).
-__device__ __forceinline__ float sin32(float x) {
-  const float q = __builtin_rintf(x * 0.318309886183790671537767526745028724f);
-  float d = __builtin_fmaf(q, -3.140625f, x);
-  d = __builtin_fmaf(q, -0.0009670257568359375f, d);
-  d = __builtin_fmaf(q, -6.2771141529083251953e-07f, d);
-  d = __builtin_fmaf(q, -1.2154201256553420762e-10f, d);
-  const float s = d * d;
-  d = ((int)q & 1) ? -d : d;
-  float u = 2.6083159809786593541503e-06f;
-  u = __builtin_fmaf(u, s, -0.0001981069071916863322258f);
-  u = __builtin_fmaf(u, s, 0.00833307858556509017944336f);
-  u = __builtin_fmaf(u, s, -0.166666597127914428710938f);
-  return __builtin_fmaf(s, u * d, d);
-}
-
 
 }  // namespace nmbf

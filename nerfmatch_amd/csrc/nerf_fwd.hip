@@ -17,14 +17,19 @@
 //   * The transmittance scan along the ray is a wavefront shuffle scan (segments of min(S,64) lanes), carried
 //     across wavefronts / 128-sample chunks through LDS for S >= 128.
 // HBM traffic per sample is ~100 B in / ~10 B out against 1.2 MFLOP: the kernel is bound by the fp32 MFMA rate.
-#include "common.h"
+#include "nerf_sample.h"
 
 namespace {
+// the sample math shared with the other NeRF kernels (nerf_sample.h)
+using nmsample::HALF_PI_F32, nmsample::SCAN_TILE, nmsample::launder, nmsample::frustum, nmsample::ray_consts, nmsample::lift_var, nmsample::ipe_exact;
+using nmsample::alpha_of, nmsample::trans_factor, nmsample::sigmoid, nmsample::scan_before_barrier, nmsample::scan_after_barrier, nmsample::scan_carry;
+using nmsample::first_max;
 
 constexpr int TILE = 128;          // samples per workgroup pass
 constexpr int XK = 45;             // k-steps of the 90-d IPE input (pair = sin / cos(=sin(.+pi/2)) of one (scale, axis))
 constexpr int HK = 128;            // k-steps of a 256-d hidden input
 constexpr int VK = 150;            // views layer: 128 (feature) + 14 (27-d direction PE, padded) + 8 (16-d appearance)
+static_assert(TILE == SCAN_TILE, "the compositing scan of nerf_sample.h spans two wavefronts");
 constexpr int STASH_LD = 260;      // padded row (floats) of the tapped-feature stash: 1040 B -> conflict-free b128 stores
 
 // ---- blob layout (floats) -------------------------------------------------------------------------------------
@@ -130,14 +135,6 @@ __device__ __forceinline__ void gemm_part(f32x16 (&acc)[4 * NOBG], wsrc_t rs, in
   }
 }
 
-// Opaque copy of a lane-varying int: values derived from the copy cannot be hoisted above this point.  Used so that
-// cheap epilogue-only quantities (LDS addresses, view-direction encodings) are recomputed where they are needed
-// instead of being kept live (= spilled to scratch) across the ~9,500 MFMAs of the MLP.
-__device__ __forceinline__ int launder(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
 // One 128-sample tile (`bid` = tile index; `sm` = the workgroup's single LDS object)
 __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, float* const sm) {
   float* const sm_small = sm;
@@ -172,10 +169,8 @@ __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, 
   const float* rp = a.rays + (size_t)rc * 12;
   const float o0 = rp[0], o1 = rp[1], o2 = rp[2], d0 = rp[3], d1 = rp[4], d2 = rp[5];
   const float radius = rp[11];
-  const float dsq0 = d0 * d0, dsq1 = d1 * d1, dsq2 = d2 * d2;
-  const float dmag = fmaxf(1e-10f, (dsq0 + dsq1) + dsq2);
-  const float dnorm = sqrtf((dsq0 + dsq1) + dsq2);
-  const float nul0 = 1.0f - dsq0 / dmag, nul1 = 1.0f - dsq1 / dmag, nul2 = 1.0f - dsq2 / dmag;
+  float dsq[3], nul[3], dnorm;
+  ray_consts(rp + 3, dsq, nul, dnorm);
 
   // ---- per-thread state of the reduction phase (valid for thread roles described below) -----------------------
   float red_acc = 0.f;      // threads < 8*nr: running sum of quantity q for ray slot r
@@ -192,17 +187,11 @@ __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, 
     const float t1 = a.t[(size_t)rc * (S + 1) + sidx + 1];
 
     // conical frustum -> Gaussian (stable form), lifted to 3-D with a diagonal covariance
-    const float mu = (t0 + t1) / 2.0f, hw = (t1 - t0) / 2.0f;
-    const float mu2 = mu * mu, hw2 = hw * hw, hw4 = hw2 * hw2;
-    const float denom = fmaxf(1.1920928955078125e-07f, 3.0f * mu2 + hw2);
-    const float t_mean = mu + (2.0f * mu * hw2) / denom;
-    const float t_var = hw2 / 3.0f - (float)(4.0 / 15.0) * ((hw4 * (12.0f * mu2 - hw2)) / (denom * denom));
-    const float r_var = (radius * radius) * ((mu2 / 4.0f + (float)(5.0 / 12.0) * hw2) - (float)(4.0 / 15.0) * hw4 / denom);
+    float t_mean, t_var, r_var;
+    frustum(t0, t1, radius, t_mean, t_var, r_var);
     float mean[3] = {d0 * t_mean + o0, d1 * t_mean + o1, d2 * t_mean + o2};
-    float var[3] = {t_var * dsq0 + r_var * nul0, t_var * dsq1 + r_var * nul1, t_var * dsq2 + r_var * nul2};
-    if (a.var_scale > 0.f) {
-      var[0] *= a.var_scale; var[1] *= a.var_scale; var[2] *= a.var_scale;
-    }
+    float var[3];
+    lift_var(t_var, r_var, dsq, nul, a.var_scale, var);
 
     // integrated positional encoding, generated per k-step (scale i, axis ax) right where the MFMA consumes it:
     // lanes 0-31 hold the sin entry, lanes 32-63 the sin(. + pi/2) entry of the same (i, ax) - the two K indices
@@ -211,9 +200,7 @@ __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, 
       const int i = ks / 3, ax = ks % 3;
       const float sc = (float)(1 << i);
       const float xe = mean[ax] * sc;
-      const float arg = hi ? (xe + 1.57079637050628662109375f) : xe;
-      const float ye = var[ax] * (sc * sc);
-      return expf(-0.5f * ye) * nm_sinf(arg);
+      return ipe_exact(hi ? (xe + HALF_PI_F32) : xe, var[ax], sc);
     };
 
     // ---- the 8 pts layers + feature_linear, activations register resident ------------------------------------
@@ -280,7 +267,7 @@ __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, 
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
           const float xe = vd[ax] * (float)(1 << i);
-          vx[i * 3 + ax] = nm_sinf(hi ? (xe + 1.57079637050628662109375f) : xe);
+          vx[i * 3 + ax] = nm_sinf(hi ? (xe + HALF_PI_F32) : xe);
         }
       vx[12] = hi ? v1 : v0;
       vx[13] = hi ? 0.f : v2;
@@ -317,9 +304,9 @@ __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, 
       pr = (pr + nm_shfl_xor32(pr)) + sm_small[OFF_MISC + 1];
       pg = (pg + nm_shfl_xor32(pg)) + sm_small[OFF_MISC + 2];
       pb = (pb + nm_shfl_xor32(pb)) + sm_small[OFF_MISC + 3];
-      c_r = 1.0f / (1.0f + expf(-pr));
-      c_g = 1.0f / (1.0f + expf(-pg));
-      c_b = 1.0f / (1.0f + expf(-pb));
+      c_r = sigmoid(pr);
+      c_g = sigmoid(pg);
+      c_b = sigmoid(pb);
     }
     const int jsw = launder(js);
     if ((launder(lane) >> 5) == 0) {
@@ -332,31 +319,17 @@ __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, 
     }
     __syncthreads();
 
-    // ---- alpha compositing: thread j < 128 owns sample slot j; wavefront shuffle scan of (1 - alpha + 1e-10) ----
+    // ---- alpha compositing: thread j < 128 owns sample slot j; wavefront shuffle scan of the transmittance factors (nerf_sample.h) ----
     float alpha = 0.f, incl = 1.f;
     const int tid = launder(threadIdx.x), lane = tid & 63, wave = tid >> 6;
     if (tid < TILE) {
-      const float sg = fmaxf(sm_sigma[tid], 0.f);
-      const float delta = (sm_t1[tid] - sm_t0[tid]) * sm_dn[tid];
-      alpha = 1.0f - expf(-sg * delta);
-      incl = (1.0f - alpha) + 1e-10f;
-      const int seg = SP < 64 ? SP : 64;
-#pragma unroll
-      for (int dlt = 1; dlt < 64; dlt <<= 1) {
-        const float up = __shfl_up(incl, dlt, 64);
-        if (dlt < seg && (lane & (seg - 1)) >= dlt) incl *= up;
-      }
-      if (lane == 63) sm_misc[wave] = incl;  // product over this wavefront's last segment (whole wave when SP >= 64)
+      alpha = alpha_of(sm_sigma[tid], (sm_t1[tid] - sm_t0[tid]) * sm_dn[tid]);
+      incl = scan_before_barrier(trans_factor(alpha), lane, wave, SP, sm_misc);
     }
     __syncthreads();
     float wgt = 0.f;
     if (tid < TILE) {
-      const int seg = SP < 64 ? SP : 64;
-      float excl = __shfl_up(incl, 1, 64);
-      if ((lane & (seg - 1)) == 0) excl = 1.f;
-      if (SP == TILE && wave == 1) excl *= sm_misc[0];
-      excl *= carryT;
-      wgt = alpha * excl;
+      wgt = alpha * scan_after_barrier(incl, lane, wave, SP, sm_misc, carryT);
       sm_w[tid] = wgt;
       const int r2 = tid / SP, ray2 = bid * nr + r2;
       if (ray2 < R) {
@@ -368,7 +341,7 @@ __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, 
         }
       }
     }
-    if (nchunks > 1) carryT = carryT * (sm_misc[0] * sm_misc[1]);  // S > 128: one ray per workgroup
+    if (nchunks > 1) carryT = scan_carry(carryT, sm_misc);  // S > 128: one ray per workgroup
     __syncthreads();
 
     // ---- per-ray sums: thread (r, q) for q in {acc, r, g, b, depth, x, y, z} ----------------------------------
@@ -394,13 +367,8 @@ __device__ __forceinline__ void nerf_fwd_tile(const NerfArgs& a, const int bid, 
         red_acc += sum;
       }
       if (feat_max) {
-        // first maximum of the weights (torch.max semantics); strict > across chunks keeps the earliest
-        float bw = wv[0];
-        int bi = 0;
-        for (int k = 1; k < SP; ++k)
-          if (wv[k] > bw) { bw = wv[k]; bi = k; }
-        const bool better = bw > best_w;
-        if (better) best_w = bw;
+        int bi;
+        const bool better = first_max(wv, SP, best_w, bi);
         if (q == 0) sm_misc[8 + r2] = better ? __int_as_float(r2 * SP + bi) : __int_as_float(-1);
         if (q >= 5 && better) red_acc = sm_mean[(q - 5) * TILE + r2 * SP + bi];
       }

@@ -41,6 +41,11 @@
 
 namespace {
 using namespace nmbf;
+// the sample math shared with the fp32 and iNeRF kernels (nerf_sample.h)
+using nmsample::HALF_PI_F32, nmsample::SCAN_TILE, nmsample::frustum, nmsample::ray_consts, nmsample::lift_var, nmsample::ipe_fast, nmsample::view_row_value;
+using nmsample::alpha_of, nmsample::trans_factor, nmsample::sigmoid, nmsample::scan_before_barrier, nmsample::scan_after_barrier, nmsample::scan_carry;
+using nmsample::first_max;
+static_assert(TILE == SCAN_TILE, "the compositing scan of nerf_sample.h spans two wavefronts");
 
 // Start the read-back of this wavefront's 32 tapped rows: LDS-DMA into the weight ring and the IPE region (nobody needs them before the
 // next tile), the last four rows into registers.  Called when the tile's last K-loop is over; between here and the reduction that
@@ -234,22 +239,12 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
   else if (bid >= ntiles) break;
   const int nent = lo_pass ? nleft : 0;
   TRACE(0);
-  // extra inputs of the views layer, one value per thread (they depend on the ray only):
-  // f = 0..11 sin(2^k d), 12..23 sin(2^k d + pi/2), 24..26 raw d, 27..42 appearance, 43..47 padding
+  // extra inputs of the views layer, one value per thread (they depend on the ray only): column f of view_row_value's row (nerf_sample.h)
   if (need_rgb && !lo_pass && tid < nr * 48) {
     const int r2 = tid / 48, f = tid % 48;
     const int ray2 = bid * nr + r2;
     const float* rq = a.rays + (size_t)(ray2 < R ? ray2 : R - 1) * 12 + 8;
-    float v = 0.f;
-    if (f < 24) {
-      const int k = (f % 12) / 3;
-      const float xe = rq[f % 3] * (float)(1 << k);
-      v = nm_sinf(f < 12 ? xe : xe + 1.57079637050628662109375f);
-    } else if (f < 27) {
-      v = rq[f - 24];
-    } else if (f < 43) {
-      v = a.app_row ? a.app_row[f - 27] : 0.f;
-    }
+    float v = view_row_value(f, rq[f % 3], a.app_row);
     if constexpr (P == 2) {  // (straight from the blob: sm_small may not have landed yet in the first tile)
       v *= reinterpret_cast<const float*>(a.blob)[OFF_INSCALE + (f < 27 ? 1 : 2)];
       __hip_atomic_fetch_max(sm_rng + 9 * 256 + tid, __float_as_uint(fabsf(v)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -266,10 +261,8 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
   const int rc = lo_pass ? sm_lray[js < nent ? js : 0] : (ray < R ? ray : R - 1);
   const float* rp = a.rays + (size_t)rc * 12;
   const float o0 = rp[0], o1 = rp[1], o2 = rp[2], d0 = rp[3], d1 = rp[4], d2 = rp[5], radius = rp[11];
-  const float dsq0 = d0 * d0, dsq1 = d1 * d1, dsq2 = d2 * d2;
-  const float dmag = fmaxf(1e-10f, (dsq0 + dsq1) + dsq2);
-  const float dnorm = sqrtf((dsq0 + dsq1) + dsq2);
-  const float nul0 = 1.0f - dsq0 / dmag, nul1 = 1.0f - dsq1 / dmag, nul2 = 1.0f - dsq2 / dmag;
+  float dsq[3], nul[3], dnorm;
+  ray_consts(rp + 3, dsq, nul, dnorm);
 
   float red_acc = 0.f;
   float carryT = 1.f;
@@ -281,17 +274,11 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     const int sidx = lo_pass ? Sa : chunk * TILE + (js % SP);
     const float t0 = a.t[(size_t)rc * (S + 1) + sidx];
     const float t1 = a.t[(size_t)rc * (S + 1) + sidx + 1];
-    const float mu = (t0 + t1) / 2.0f, hw = (t1 - t0) / 2.0f;
-    const float mu2 = mu * mu, hw2 = hw * hw, hw4 = hw2 * hw2;
-    const float denom = fmaxf(1.1920928955078125e-07f, 3.0f * mu2 + hw2);
-    const float t_mean = mu + (2.0f * mu * hw2) / denom;
-    const float t_var = hw2 / 3.0f - (float)(4.0 / 15.0) * ((hw4 * (12.0f * mu2 - hw2)) / (denom * denom));
-    const float r_var = (radius * radius) * ((mu2 / 4.0f + (float)(5.0 / 12.0) * hw2) - (float)(4.0 / 15.0) * hw4 / denom);
+    float t_mean, t_var, r_var;
+    frustum(t0, t1, radius, t_mean, t_var, r_var);
     float mean[3] = {d0 * t_mean + o0, d1 * t_mean + o1, d2 * t_mean + o2};
-    float var[3] = {t_var * dsq0 + r_var * nul0, t_var * dsq1 + r_var * nul1, t_var * dsq2 + r_var * nul2};
-    if (a.var_scale > 0.f) {
-      var[0] *= a.var_scale; var[1] *= a.var_scale; var[2] *= a.var_scale;
-    }
+    float var[3];
+    lift_var(t_var, r_var, dsq, nul, a.var_scale, var);
     if (hi == 0) {
       sm_t0[js] = t0; sm_t1[js] = t1;
       sm_mean[js] = mean[0]; sm_mean[TILE + js] = mean[1]; sm_mean[2 * TILE + js] = mean[2];
@@ -310,35 +297,17 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     // Every lane evaluates only the 48 encodings its wavefront half feeds to the MFMAs, directly in fp32: the argument
     // 2^scale * x is exact, sin32 (4-term Cody-Waite + degree-9 polynomial, |err| <= 1e-7 for |arg| < 6.5e4) replaces the
     // earlier fp64 angle-doubling recurrence (which both halves had to run over all 90 values), and the second half of
-    // the encoding takes sin(fl32(arg + fl32(pi/2))) literally like the reference (x + 0.f is x).
+    // the encoding takes sin(fl32(arg + fl32(pi/2))) literally like the reference (x + 0.f is x; -0 becomes +0, its sine a zero either way).
     {
-      float* dst = sm_ipe + wave * (XS * 2 * 64 * 4) + lane * 4;
       const float ipe_scale = sm_small[OFF_INSCALE];
-      const float phl = hi ? 1.57079637050628662109375f : 0.f;
-#pragma unroll
-      for (int m = 0; m < XS; ++m) {
-        float v8[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int idx = 8 * m + i;                     // compile time
-          const bool live = idx < 45;
-          const int ax = (live ? idx : 0) % 3, sb = (live ? idx : 0) / 3;
-          const float mu = mean[ax], vr = var[ax];
-          const float sc = (float)(1 << sb);
-          const float xe = mu * sc;
-          float v = __builtin_amdgcn_exp2f((-0.5f * (vr * (sc * sc))) * 1.44269504088896340736f) * sin32(xe + phl);
-          if constexpr (P == 2) v *= ipe_scale;  // 2^c_ipe (|v| <= 1: no saturation possible for c_ipe <= 15)
-          v8[i] = live ? v : 0.f;
-        }
-        if constexpr (is_split<P>()) {
-          bf16x8 h8, l8;
-          split8_p<P>(v8, h8, l8);
-          *reinterpret_cast<u32x4*>(dst + (m * 2 + 0) * 256) = __builtin_bit_cast(u32x4, h8);
-          *reinterpret_cast<u32x4*>(dst + (m * 2 + 1) * 256) = __builtin_bit_cast(u32x4, l8);
-        } else {
-          *reinterpret_cast<u32x4*>(dst + m * 256) = __builtin_bit_cast(u32x4, pack8_f16(v8));
-        }
-      }
+      const float phl = hi ? HALF_PI_F32 : 0.f;
+      park_ipe<P>(sm_ipe + wave * (XS * 2 * 64 * 4) + lane * 4, [&](int idx) {  // (idx: compile time)
+        const int ax = idx % 3;
+        const float sc = (float)(1 << (idx / 3));
+        float v = ipe_fast(mean[ax] * sc + phl, var[ax], sc);
+        if constexpr (P == 2) v *= ipe_scale;  // 2^c_ipe (|v| <= 1: no saturation possible for c_ipe <= 15)
+        return v;
+      });
     }
 
     TRACE(2);
@@ -365,41 +334,29 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     if constexpr (P == 1) load_half<1>(cx.opB, ring, lane, 1);
     const float* ipe_src = sm_ipe + wave * (XS * 2 * 64 * 4) + lane * 4;
 
-    // ---- alpha compositing (identical to nerf_fwd.hip), in pieces: a tap on layer 7 needs the weights before the views layer ----------
+    // ---- alpha compositing (nerf_sample.h: the expressions nerf_fwd.hip inlines too), in pieces: a tap on layer 7 needs the weights before
+    // the views layer ----------
     // Piece 1, behind a barrier that follows the densities into sm_sigma: alpha, transmittance scan, weights -> sm_w, the leftover queue,
     // the transmittance carried into the next chunk.  ONE copy of these expressions: the epilogue calls it, or tap7_early does.
     auto composite_weights = [&]() __attribute__((always_inline)) {
       const int tid2 = launder(threadIdx.x), lane2 = tid2 & 63, wave2 = tid2 >> 6;
       float alpha = 0.f, incl = 1.f;
       if (tid2 < TILE) {
-        const float sg = fmaxf(sm_sigma[tid2], 0.f);
-        const float delta = (sm_t1[tid2] - sm_t0[tid2]) * sm_dn[tid2];
-        alpha = 1.0f - expf(-sg * delta);
-        incl = (1.0f - alpha) + 1e-10f;
-        const int seg = SP < 64 ? SP : 64;
-#pragma unroll
-        for (int dlt = 1; dlt < 64; dlt <<= 1) {
-          const float up = __shfl_up(incl, dlt, 64);
-          if (dlt < seg && (lane2 & (seg - 1)) >= dlt) incl *= up;
-        }
-        if (lane2 == 63) sm_misc[wave2] = incl;
+        alpha = alpha_of(sm_sigma[tid2], (sm_t1[tid2] - sm_t0[tid2]) * sm_dn[tid2]);
+        incl = scan_before_barrier(trans_factor(alpha), lane2, wave2, SP, sm_misc);
       }
       NM_EPI_BARRIER();
       if (tid2 < TILE) {
-        const int seg = SP < 64 ? SP : 64;
-        float excl = __shfl_up(incl, 1, 64);
-        if ((lane2 & (seg - 1)) == 0) excl = 1.f;
-        if (SP == TILE && wave2 == 1) excl *= sm_misc[0];
-        excl *= carryT;
+        const float excl = scan_after_barrier(incl, lane2, wave2, SP, sm_misc, carryT);
         sm_w[tid2] = alpha * excl;
         const int r2 = tid2 / SP, ray2 = bid * nr + r2;
         if (left && chunk == nchunks - 1 && ray2 < R && tid2 % SP == SP - 1) {
           // (zero-width tail) sample Sa is queued with the transmittance in front of it
           sm_lray[nleft + r2] = ray2;
-          sm_lT[nleft + r2] = excl * ((1.0f - alpha) + 1e-10f);
+          sm_lT[nleft + r2] = excl * trans_factor(alpha);
         }
       }
-      if (nchunks > 1) carryT = carryT * (sm_misc[0] * sm_misc[1]);
+      if (nchunks > 1) carryT = scan_carry(carryT, sm_misc);
     };
     // Piece 2, once the colours are in sm_rgb: the per-sample outputs and the per-ray sums, step 1 (weights from sm_w: own write or a
     // barrier ago)
@@ -438,12 +395,8 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
       if (tid2 < 8 * nr) {
         const int q = tid2 & 7, r2 = tid2 >> 3;
         const float* wv = sm_w + r2 * SP;
-        float bw = wv[0];
-        int bi = 0;
-        for (int k = 1; k < SP; ++k)
-          if (wv[k] > bw) { bw = wv[k]; bi = k; }
-        const bool better = bw > best_w;
-        if (better) best_w = bw;
+        int bi;
+        const bool better = first_max(wv, SP, best_w, bi);
         if (q == 0) sm_misc[8 + r2] = better ? __int_as_float(r2 * SP + bi) : __int_as_float(-1);
         if (q >= 5 && better) red_acc = sm_mean[(q - 5) * TILE + r2 * SP + bi];
       }
@@ -523,23 +476,14 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
           const f32x4 e0 = *reinterpret_cast<const f32x4*>(exr + 16 * e), e1 = *reinterpret_cast<const f32x4*>(exr + 16 * e + 4);
           v8[0] = e0[0]; v8[1] = e0[1]; v8[2] = e0[2]; v8[3] = e0[3]; v8[4] = e1[0]; v8[5] = e1[1]; v8[6] = e1[2]; v8[7] = e1[3];
         } else {
-          // leftover pass: every lane has its own ray, so the per-slot table does not apply; same formulas, in registers
+          // leftover pass: every lane has its own ray, so the per-slot table does not apply; the same view_row_value, in registers
           const float* rq = a.rays + (size_t)launder(rc) * 12 + 8;
           const float vd0 = rq[0], vd1 = rq[1], vd2 = rq[2];
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
             const int f = 16 * e + 8 * hh + i;
             const int ax = f % 3;
-            const float dax = ax == 0 ? vd0 : ax == 1 ? vd1 : vd2;
-            float v = 0.f;
-            if (f < 24) {
-              const float xe = dax * (float)(1 << ((f % 12) / 3));
-              v = nm_sinf(f < 12 ? xe : xe + 1.57079637050628662109375f);
-            } else if (f < 27) {
-              v = dax;  // f - 24 == f % 3
-            } else if (f < 43) {
-              v = a.app_row ? a.app_row[f - 27] : 0.f;
-            }
+            float v = view_row_value(f, ax == 0 ? vd0 : ax == 1 ? vd1 : vd2, a.app_row);
             if constexpr (P == 2) v *= sm_small[OFF_INSCALE + (f < 27 ? 1 : 2)];
             v8[i] = v;
           }
@@ -574,9 +518,9 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
       pr = (pr + nm_shfl_xor32(pr)) + sm_small[OFF_MISC + 1];
       pg = (pg + nm_shfl_xor32(pg)) + sm_small[OFF_MISC + 2];
       pb = (pb + nm_shfl_xor32(pb)) + sm_small[OFF_MISC + 3];
-      c_r = 1.0f / (1.0f + expf(-pr));
-      c_g = 1.0f / (1.0f + expf(-pg));
-      c_b = 1.0f / (1.0f + expf(-pb));
+      c_r = sigmoid(pr);
+      c_g = sigmoid(pg);
+      c_b = sigmoid(pb);
       if (cx.tap_pref) tap_prefetch<1>(cx);
     }
     const float sigma_raw = (cx.sig_part + nm_shfl_xor32(cx.sig_part)) + sm_small[OFF_MISC];
@@ -597,9 +541,7 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
       // its contributions are ADDED (atomics: they execute at L2, where this workgroup's earlier plain stores are)
       if (tid2 < nent) {
         const int ray2 = sm_lray[tid2];
-        const float sg = fmaxf(sm_sigma[tid2], 0.f);
-        const float delta = (sm_t1[tid2] - sm_t0[tid2]) * sm_dn[tid2];
-        const float wgt = (1.0f - expf(-sg * delta)) * sm_lT[tid2];
+        const float wgt = alpha_of(sm_sigma[tid2], (sm_t1[tid2] - sm_t0[tid2]) * sm_dn[tid2]) * sm_lT[tid2];
         sm_w[tid2] = wgt;
         a.weights[(size_t)ray2 * S + Sa] = wgt;
         if (a.acc) atomicAdd(a.acc + ray2, wgt);

@@ -18,6 +18,7 @@
 
 namespace {
 using namespace nmbf;
+using nmsample::HALF_PI_F32, nmsample::frustum, nmsample::ray_consts, nmsample::lift_var, nmsample::ipe_exact, nmsample::view_row_value;  // nerf_sample.h
 
 struct PointsArgs {
   const char* blob;
@@ -78,58 +79,26 @@ __device__ __forceinline__ void points_fwd_body(const PointsArgs& a) {
     {  // the 6 IPE K-steps' B operands: this lane's 8 columns per step
       float* dst = sm_ipe + wave * (XS * 2 * 64 * 4) + lane * 4;
       if constexpr (RAYS) {
-        // encode here (round 4: saves nm_inerf_encode and the 144 floats per sample it writes): the formulas of nm_inerf_encode /
-        // the reference's cast_rays + PositionalEncodingMIP (render_utils.py:326-402, embedding.py:66-84), exact sine and exponential
+        // encode here (round 4: saves nm_inerf_encode and the 144 floats per sample it writes): nerf_sample.h's functions, the ones
+        // nm_inerf_encode calls (the reference's cast_rays + PositionalEncodingMIP, render_utils.py:326-402, embedding.py:66-84), exact flavour
         const int r = (int)(sc / (size_t)a.Sa), si = (int)(sc % (size_t)a.Sa);
         const float* rp = a.rays + (size_t)r * 12;
         const float t0 = a.z[(size_t)r * (a.S + 1) + si], t1 = a.z[(size_t)r * (a.S + 1) + si + 1];
-        const float d0 = rp[3], d1 = rp[4], d2 = rp[5], radius = rp[11];
         vdir[0] = rp[8]; vdir[1] = rp[9]; vdir[2] = rp[10];
-        const float mu = (t0 + t1) / 2.0f, hw = (t1 - t0) / 2.0f;
-        const float mu2 = mu * mu, hw2 = hw * hw, hw4 = hw2 * hw2;
-        const float denom = fmaxf(1.1920928955078125e-07f, 3.0f * mu2 + hw2);
-        const float t_mean = mu + (2.0f * mu * hw2) / denom;
-        const float t_var = hw2 / 3.0f - (float)(4.0 / 15.0) * ((hw4 * (12.0f * mu2 - hw2)) / (denom * denom));
-        const float r_var = (radius * radius) * ((mu2 / 4.0f + (float)(5.0 / 12.0) * hw2) - (float)(4.0 / 15.0) * hw4 / denom);
-        const float dsq[3] = {d0 * d0, d1 * d1, d2 * d2};
-        const float dmag = fmaxf(1e-10f, (dsq[0] + dsq[1]) + dsq[2]);
-        float mean[3], var[3];
+        float t_mean, t_var, r_var, dsq[3], nul[3], dnorm, mean[3], var[3];
+        frustum(t0, t1, rp[11], t_mean, t_var, r_var);
+        ray_consts(rp + 3, dsq, nul, dnorm);  // (dnorm unused: the compositing is another kernel)
+        lift_var(t_var, r_var, dsq, nul, 0.f, var);
 #pragma unroll
-        for (int ax = 0; ax < 3; ++ax) {
-          mean[ax] = rp[ax] + t_mean * vdir[ax];  // (nm_inerf_encode: origin + t_mean * view direction; rays[:, 3:6] == rays[:, 8:11] there)
-          var[ax] = t_var * dsq[ax] + r_var * (1.0f - dsq[ax] / dmag);
-        }
-        const float phl = hi ? 1.57079637050628662109375f : 0.f;
-#pragma unroll
-        for (int m = 0; m < XS; ++m) {
-          float v8[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int idx = 8 * m + i;  // K-slot (m, half, i) <-> encoding 45 half + idx (see nerf_fwd_body, nerf_fwd_bf16.hip)
-            const bool live = idx < 45;
-            const int ax = (live ? idx : 0) % 3, sb = (live ? idx : 0) / 3;
-            const float scl = (float)(1 << sb);
-            const float xe = mean[ax] * scl;
-            const float v = expf(-0.5f * (var[ax] * (scl * scl))) * nm_sinf(xe + phl);  // (x + 0.f is x)
-            v8[i] = live ? v : 0.f;
-          }
-          bf16x8 h8, l8;
-          split8_p<P>(v8, h8, l8);
-          *reinterpret_cast<u32x4*>(dst + (m * 2 + 0) * 256) = __builtin_bit_cast(u32x4, h8);
-          *reinterpret_cast<u32x4*>(dst + (m * 2 + 1) * 256) = __builtin_bit_cast(u32x4, l8);
-        }
+        for (int ax = 0; ax < 3; ++ax) mean[ax] = rp[ax] + t_mean * vdir[ax];  // (the iNeRF form of the mean: nerf_sample.h, lift_var)
+        const float phl = hi ? HALF_PI_F32 : 0.f;
+        park_ipe<P>(dst, [&](int idx) {
+          const float scl = (float)(1 << (idx / 3));
+          return ipe_exact(mean[idx % 3] * scl + phl, var[idx % 3], scl);
+        });
       } else {
         const float* row = a.xi + sc * 96 + 45 * hi;  // xi is in the reference's order: this half's part (sin | shifted sin) starts at 45 half
-#pragma unroll
-        for (int m = 0; m < XS; ++m) {
-          float v8[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v8[i] = (8 * m + i) < 45 ? row[8 * m + i] : 0.f;
-          bf16x8 h8, l8;
-          split8_p<P>(v8, h8, l8);
-          *reinterpret_cast<u32x4*>(dst + (m * 2 + 0) * 256) = __builtin_bit_cast(u32x4, h8);
-          *reinterpret_cast<u32x4*>(dst + (m * 2 + 1) * 256) = __builtin_bit_cast(u32x4, l8);
-        }
+        park_ipe<P>(dst, [&](int idx) { return row[idx]; });
       }
     }
     Ctx cx;
@@ -162,22 +131,12 @@ __device__ __forceinline__ void points_fwd_body(const PointsArgs& a) {
 #pragma unroll
       for (int e = 0; e < VS; ++e) {
         float v8[8];
-        if constexpr (RAYS) {  // xd row of nm_inerf_encode: sin(2^k v), sin(2^k v + pi/2), v, appearance row, padding
+        if constexpr (RAYS) {  // xd row of nm_inerf_encode: view_row_value (nerf_sample.h)
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
             const int f = 16 * e + 8 * hh + i;
             const int ax = f % 3;
-            const float dax = ax == 0 ? vdir[0] : ax == 1 ? vdir[1] : vdir[2];
-            float v = 0.f;
-            if (f < 24) {
-              const float xe = dax * (float)(1 << ((f % 12) / 3));
-              v = nm_sinf(f < 12 ? xe : xe + 1.57079637050628662109375f);
-            } else if (f < 27) {
-              v = dax;
-            } else if (f < 43) {
-              v = a.app_row ? a.app_row[f - 27] : 0.f;
-            }
-            v8[i] = v;
+            v8[i] = view_row_value(f, ax == 0 ? vdir[0] : ax == 1 ? vdir[1] : vdir[2], a.app_row);
           }
         } else {
           const f32x4 e0 = *reinterpret_cast<const f32x4*>(row + 16 * e), e1 = *reinterpret_cast<const f32x4*>(row + 16 * e + 4);

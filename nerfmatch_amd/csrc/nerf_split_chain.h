@@ -61,6 +61,30 @@ __device__ __forceinline__ bf16x8 pack8_f16(const float (&v)[8]) {
   const u32x4 r = {pack_f16(v[0], v[1]), pack_f16(v[2], v[3]), pack_f16(v[4], v[5]), pack_f16(v[6], v[7])};
   return __builtin_bit_cast(bf16x8, r);
 }
+// Parks the B operands of the 6 IPE K-steps of one wavefront in LDS (dst: the lane's 16 bytes of the wavefront's block).  K-slot (step m,
+// half h, i) holds encoding 45 h + idx, idx = 8 m + i < 45 (the last three slots of step 5 are padding); value(idx) yields this lane's
+// value -- idx is a compile-time constant after unrolling.  Split modes store hi and lo operands, fp16x1 the one rounded operand.
+template <int P, class F>
+__device__ __forceinline__ void park_ipe(float* dst, F value) {
+#pragma unroll
+  for (int m = 0; m < XS; ++m) {
+    float v8[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int idx = 8 * m + i;
+      if (idx < 45) v8[i] = value(idx);
+      else v8[i] = 0.f;
+    }
+    if constexpr (is_split<P>()) {
+      bf16x8 h8, l8;
+      split8_p<P>(v8, h8, l8);
+      *reinterpret_cast<u32x4*>(dst + (m * 2 + 0) * 256) = __builtin_bit_cast(u32x4, h8);
+      *reinterpret_cast<u32x4*>(dst + (m * 2 + 1) * 256) = __builtin_bit_cast(u32x4, l8);
+    } else {
+      *reinterpret_cast<u32x4*>(dst + m * 256) = __builtin_bit_cast(u32x4, pack8_f16(v8));
+    }
+  }
+}
 
 // The 4 pieces share ONE global address and ONE M0 (LDS base) and differ only in the instruction's immediate offset,
 // which the hardware adds on both sides -- measured 31 instead of 58 cycles of issue per piece beside the MFMAs.

@@ -63,7 +63,7 @@ def main():
     new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
     out = dict(weights=new(R, S), feat=new(R, 256), pts=new(R, 3), rgb=new(R, 3), depth=new(R), acc=new(R))
     ws = ops._nerf_workspace(dev)
-    status = {"fp16x3": (dptr(blob_c.nm_guard.status, torch.int32),)}.get(a.precision, ())
+    status = (dptr(blob_c.nm_guard.status, torch.int32),) if a.precision == "fp16x3" else ()  # (only an fp16x3 blob carries a guard)
 
     def args(blob, t, tap):
         return (dptr(blob, blob.dtype), dptr(rays), dptr(t), None, R, S, tap, 0, -1.0, 0, dptr(out["weights"]), dptr(out["feat"]), dptr(out["pts"]),
