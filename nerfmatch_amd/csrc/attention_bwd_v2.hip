@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(256, 3) attn32_bwd_dq_v2_kernel(BwdArgs2 a) {
     const bool raise = first || mx > RAISE;
     if (__builtin_amdgcn_ballot_w64(raise) != 0) {
       const float delta = raise ? mx : 0.f;
-      lrun *= __builtin_amdgcn_exp2f(-delta);
+      if (!first) lrun *= __builtin_amdgcn_exp2f(-delta);  // (first tile: lrun is 0, and 2^-delta is inf for a row maximum below -128)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         sc[i] -= delta;

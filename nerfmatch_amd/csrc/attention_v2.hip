@@ -154,7 +154,8 @@ __global__ void __launch_bounds__(256, 4) attn32_v3_kernel(const float* __restri
       nm_swap32(nm_max16(sc), mlo, mhi);
       const float mx = nm_max3(mlo, mhi, mhi);  // row maximum over the tile's 32 keys (both wavefront halves)
       const float delta = (t == 0 || mx > 64.0f) ? mx : 0.f;
-      const float alpha = __builtin_amdgcn_exp2f(-delta);
+      // (first tile: nothing to rescale yet, and with a row maximum below -128 the factor 2^-delta is inf: 0 * inf = NaN)
+      const float alpha = t == 0 ? 1.0f : __builtin_amdgcn_exp2f(-delta);
       lrun *= alpha;
       ps = 0.f;
 #pragma unroll
