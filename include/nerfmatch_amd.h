@@ -302,6 +302,45 @@ int nm_inerf_ray_sums(const float* weights, const float* feats, int C, const flo
 int nm_inerf_ray_sums_bwd(const float* weights, const float* feats, int C, const float* rays, const float* z, const float* g_pt_feat,
                           const float* g_pts, int R, int S, int S_act, float* g_feats, float* g_weights, nmStream_t stream);
 
+/* ---- NeRF scene training (csrc/nerf_train.hip) ---------------------------------------------------------------------------
+ * The per-ray kernels of one training step of NerfRenderer.render_rays(validation=False) (nerfmatch/nerf/renderer.py:182-295) and
+ * compute_nerf_metrics (nerfmatch/utils/metrics.py:59-96); the two MLPs run on nm_linear* / nm_linear_wgrad*.  No gradient flows
+ * through t, the frustum Gaussians or the encodings (render_utils.py:299-310, :581-597: sampling under no_grad, stop_grad=True). */
+
+/* rays[R,12], t[R,S+1] -> xi[R*S,96], xd[R*S,48] in the layout of nm_inerf_encode, with the forward render kernels' mean d * t_mean + o
+ * (d = rays[:,3:6]; the direction PE from rays[:,8:11]) and var_scale as in nm_nerf_fwd.  Appearance: row ray_id[r] (int64, device) of
+ * table[V,16] per ray (embedding_a(ray_id), renderer.py:225); table NULL = none, ray_id NULL = id 1 for every ray (renderer.py:298-299).
+ * ray_id_host (may be NULL): the same ids on the host -- an id outside [0, V) is then NM_ERR_ARG before anything is enqueued.  On the
+ * device such an id is clamped into the table and counted in *status (int, device, may be NULL; add-only). */
+int nm_nerf_train_encode(const float* rays, const float* t, int R, int S, const long long* ray_id, const long long* ray_id_host,
+                         const float* table, int V, float var_scale, float* xi, float* xd, int* status, nmStream_t stream);
+/* volume_render_radiance_field in training mode (render_utils.py:176-230): out4[R*S,4] = rgb logits | raw sigma,
+ * density = relu(raw sigma + noise[R,S] * noise_std) (noise NULL: none), white_bg either way, the +1e-10 in the transmittance product
+ * -> rgb[R,3], depth[R], acc[R], weights[R,S] (the last three may be NULL).  One wavefront per ray, S <= 1024.
+ * _bwd: g_rgb[R,3], g_weights[R,S] (NULL = none) -> g_out4[R*S,4]; the density gate is raw sigma + noise * noise_std > 0. */
+int nm_nerf_train_composite(const float* out4, const float* t, const float* rays, const float* noise, float noise_std, int white_bg, int R,
+                            int S, float* rgb, float* depth, float* acc, float* weights, nmStream_t stream);
+int nm_nerf_train_composite_bwd(const float* out4, const float* t, const float* rays, const float* noise, float noise_std, int white_bg,
+                                const float* g_rgb, const float* g_weights, int R, int S, float* g_out4, nmStream_t stream);
+/* s[R,S+1] = t_to_s(t, min t, max t) (render_utils.py:618-636; minimum and maximum over the WHOLE batch, reduced on the device; g's
+ * in-place eps as the reference applies it) and, with weights[R,S], lossfun_distortion (metrics.py:453-465) per ray -> loss_ray[R] and
+ * its mean -> loss_mean[1] (may be NULL).  t_is_s != 0: `t` already holds s (s and workspace may then be NULL).
+ * workspace: nm_nerf_distortion_workspace_bytes() bytes.  S <= 1024.
+ * _bwd: g_weights[R,S] = scale / R * (2 sum_j w_j |u_i - u_j| + 2 w_i (s_{i+1} - s_i) / 3), u the interval midpoints of s. */
+size_t nm_nerf_distortion_workspace_bytes(void);
+int nm_nerf_distortion(const float* t, int t_is_s, const float* weights, int R, int S, void* workspace, float* s, float* loss_ray,
+                       float* loss_mean, nmStream_t stream);
+int nm_nerf_distortion_bwd(const float* s, const float* weights, int R, int S, float scale, float* g_weights, nmStream_t stream);
+/* acc[0] = 0.5 mean(mask (rgb_c - gt)^2), acc[1] = the same of rgb_f (double, fixed summation order; mask[R] NULL = 1; metrics.py:74, :80);
+ * g_rgb_c / g_rgb_f [R,3] (may be NULL) = the gradients of coarse_weight * acc[0] + acc[1]. */
+int nm_nerf_photo_loss(const float* rgb_c, const float* rgb_f, const float* gt, const float* mask, float coarse_weight, int R, double* acc,
+                       float* g_rgb_c, float* g_rgb_f, nmStream_t stream);
+/* d loss / d appearance table: columns 27..42 of g_xd_a (+ g_xd_b, may be NULL) [R*S,48] summed per ray into g_ray[R,16] (scratch), then
+ * ADDED into g_table[V,16] rows by ray_id (clamped as in nm_nerf_train_encode; NULL = id 1) in a fixed order: no float atomics, two
+ * runs give the same bits, and the row of an id that does not occur is left as it is. */
+int nm_nerf_app_grad(const float* g_xd_a, const float* g_xd_b, const long long* ray_id, int R, int S, int V, float* g_ray, float* g_table,
+                     nmStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Matcher half
  * ---------------------------------------------------------------------------------------------- */

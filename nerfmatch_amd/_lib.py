@@ -73,6 +73,15 @@ SIGNATURES = {
     "nm_inerf_composite_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "nm_inerf_ray_sums": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
     "nm_inerf_ray_sums_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    # NeRF scene training (nerf_train.hip)
+    "nm_nerf_train_encode": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, f32, vp, vp, vp, vp]),
+    "nm_nerf_train_composite": (i32, [vp, vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "nm_nerf_train_composite_bwd": (i32, [vp, vp, vp, vp, f32, i32, vp, vp, i32, i32, vp, vp]),
+    "nm_nerf_distortion_workspace_bytes": (sz, []),
+    "nm_nerf_distortion": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "nm_nerf_distortion_bwd": (i32, [vp, vp, i32, i32, f32, vp, vp]),
+    "nm_nerf_photo_loss": (i32, [vp, vp, vp, vp, f32, i32, vp, vp, vp, vp]),
+    "nm_nerf_app_grad": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "nm_linear": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "nm_linear_blob_bytes_bf16x3": (sz, [i32, i32]),
     "nm_linear_qkv_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -6,8 +6,9 @@ so `load_nerf_render_from_ckpt` and the evaluator keep working.  What differs is
 render is 5 kernel launches (ray generation, stratified sampling, fused pass, re-sampling, fused pass) instead of
 ~40 eager ops per 16k-sample chunk, and nothing but the pose touches the host.
 
-Only the validation/inference path of the mip configuration (`embedding.type == "mip"`, view directions on) is
-built; training-mode outputs (`s_fine`, noise, perturb) are out of scope.
+Only the mip configuration (`embedding.type == "mip"`, view directions on) is built.  The validation / inference path
+runs on the fused kernels; the training path (`validation=False`: density noise, `s_fine` / `weights_fine`, gradients
+towards the parameters) is nerf/train_render.py.
 
 Randomness: the reference samples stochastically even at inference (render_utils.py:276, :444, :483).  Here the
 two random tensors are explicit optional arguments (`t_rand`, `jitter`); when omitted they are drawn with
@@ -218,17 +219,84 @@ class NerfRenderer(nn.Module):
                 net._blob.pop((dev, "fp16x3"), None)
 
     # ------------------------------------------------------------------------------------------------------
-    def render_rays(self, rays, ray_id=None, validation=False, t_rand=None, jitter=None, lean=False, debug=False, rgb_fine=True):
+    def render_rays(self, rays, ray_id=None, validation=False, t_rand=None, jitter=None, lean=False, debug=False, rgb_fine=True,
+                    noise_coarse=None, noise_fine=None):
         """Coarse -> fine rendering (reference: renderer.py:182-295).
 
-        lean=True computes only what `render_novel_view` returns (rgb_fine, pts_fine, feat_fine): the coarse pass
-        then skips its colour heads and its (unused) feature sum; with rgb_fine=False the fine pass skips
-        feature_linear / views / rgb as well (localisation reads only pts_fine and feat_fine: SURVEY.md 8a quirk 6).
-        debug=True adds per-sample tensors."""
+        validation=True: the inference path on the fused kernels.  lean=True computes only what `render_novel_view` returns (rgb_fine,
+        pts_fine, feat_fine): the coarse pass then skips its colour heads and its (unused) feature sum; with rgb_fine=False the fine pass
+        skips feature_linear / views / rgb as well (localisation reads only pts_fine and feat_fine: SURVEY.md 8a quirk 6).
+        debug=True adds per-sample tensors.  `pfeat_mask` (a boolean mask over the rays, nerf_trainer.py:28-32, :45) keeps only the masked
+        rays' rows of feat_* (renderer.py:250-253).
+
+        validation=False: the training path (nerf/train_render.py) -> rgb_{coarse,fine}, depth_{coarse,fine}, s_fine, weights_fine
+        (renderer.py:283-290), differentiable towards the parameters of both networks and the appearance table.  While `self.training`
+        is set the densities carry noise_std * randn (noise_coarse / noise_fine (R,S): the draws, made on the device when absent).
+        debug=True adds t_coarse, t_fine and weights_coarse."""
         if not validation:
-            raise NotImplementedError("training-mode rendering (noise, s_fine/weights_fine outputs) is out of scope")
-        if self.pfeat_mask is not None:
-            raise NotImplementedError("pfeat_mask is a training-time option (nerf_trainer.py:45)")
+            if self.ret_pfeat:
+                raise NotImplementedError("ret_pfeat=True with validation=False: point features are rendered by the validation path only "
+                                          "(the reference's trainer never asks for them in a training render, nerf_trainer.py:141)")
+            return self._render_rays_train(rays, ray_id, t_rand, jitter, noise_coarse, noise_fine, debug)
+        preds = self._render_rays_val(rays, ray_id, t_rand=t_rand, jitter=jitter, lean=lean, debug=debug, rgb_fine=rgb_fine)
+        if self.pfeat_mask is not None and self.ret_pfeat:
+            mask = torch.as_tensor(self.pfeat_mask).reshape(-1).to(torch.bool)
+            if mask.numel() != rays.shape[0]:
+                raise ValueError(f"pfeat_mask has {mask.numel()} entries for {rays.shape[0]} rays")
+            sel = torch.nonzero(mask).reshape(-1).to(rays.device)
+            for key in ("feat_coarse", "feat_fine"):
+                if key in preds:
+                    preds[key] = preds[key][sel]
+        return preds
+
+    train_chunk_bytes = 2 << 30  # saved activations of one network per chunk of rays in a training render (train_chunk_rays overrides)
+    train_chunk_rays = None
+
+    def _render_rays_train(self, rays, ray_id, t_rand, jitter, noise_coarse, noise_fine, debug):
+        from . import train_render as tr
+
+        dev = rays.device
+        R = rays.shape[0]
+        rays = rays.to(torch.float32).contiguous()
+        if rays.shape[1] < 12:
+            raise ValueError("mip rendering needs the 12-column ray layout [o, d, near, far, viewdir, radius]")
+        S = self.num_pts_coarse  # (the fine pass has the coarse pass's sample count: see _render_rays_val)
+        ids = ids_host = None
+        if self.appearance_embedding and ray_id is not None:
+            ids = torch.as_tensor(ray_id).reshape(-1).to(torch.int64)
+            if ids.numel() != R:
+                raise ValueError(f"ray_id has {ids.numel()} entries for {R} rays")
+            if ids.device.type == "cpu":
+                ids_host = ids.contiguous()  # (checked against the table's size on the host; ids that live on the device are clamped and counted)
+            ids = ids.to(dev).contiguous()
+        f32 = lambda x: None if x is None else x.to(dev, torch.float32).contiguous()
+        noisy = self.training and self.noise_std > 0
+        status = self.__dict__.get("_train_status")
+        if status is None or status.device != dev:
+            status = self.__dict__["_train_status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        a = tr.RenderArgs(
+            rays=rays, S=S, ray_id=ids, ray_id_host=ids_host, status=status,
+            t_rand=f32(t_rand) if t_rand is not None else torch.rand(R, S + 1, device=dev),
+            jitter=f32(jitter) if jitter is not None else torch.rand(R, S + 1, device=dev), jitter_scale=1.0 if jitter is not None else 1.0 / (S + 1) - F32_EPS,
+            noise_coarse=(f32(noise_coarse) if noise_coarse is not None else torch.randn(R, S, device=dev)) if noisy else None,
+            noise_fine=(f32(noise_fine) if noise_fine is not None else torch.randn(R, S, device=dev)) if noisy else None,
+            noise_std=float(self.noise_std) if noisy else 0.0, white_bg=bool(self.white_bg), var_scale=float(self.mip_var_scale),
+            padding=self.resample_padding, chunk_rays=self.train_chunk_rays or tr.chunk_rays_for(S, self.train_chunk_bytes))
+        params = tr.net_parameters(self.nerf_coarse) + tr.net_parameters(self.nerf_fine)
+        if self.appearance_embedding:
+            params.append(self.embedding_a.weight)
+        rgb_c, depth_c, rgb_f, depth_f, w_f, s_f, t_c, t_f, w_c = tr.TrainRender.apply(a, *params)
+        preds = dict(rgb_coarse=rgb_c, depth_coarse=depth_c, rgb_fine=rgb_f, depth_fine=depth_f, s_fine=s_f, weights_fine=w_f)
+        if debug:
+            preds.update(t_coarse=t_c, t_fine=t_f, weights_coarse=w_c)
+        return preds
+
+    def train_id_errors(self):
+        """Appearance ids outside the table that training renders met on the device so far (they were clamped); one synchronisation."""
+        status = self.__dict__.get("_train_status")
+        return 0 if status is None else int(status.item())
+
+    def _render_rays_val(self, rays, ray_id=None, validation=True, t_rand=None, jitter=None, lean=False, debug=False, rgb_fine=True):
         dev = rays.device
         R = rays.shape[0]
         rays = rays.to(torch.float32).contiguous()
@@ -302,7 +370,7 @@ class NerfRenderer(nn.Module):
         for u in uniq.tolist():
             sel = torch.nonzero(ids == u).reshape(-1)
             sel_d = sel.to(dev)
-            sub = self.render_rays(rays[sel_d].contiguous(), ray_id=torch.full((1,), u, dtype=torch.long).expand(sel.numel()),
+            sub = self._render_rays_val(rays[sel_d].contiguous(), ray_id=torch.full((1,), u, dtype=torch.long).expand(sel.numel()),
                                    t_rand=None if t_rand is None else t_rand[sel.to(t_rand.device)],
                                    jitter=None if jitter is None else jitter[sel.to(jitter.device)], **kw)
             for k, v in sub.items():

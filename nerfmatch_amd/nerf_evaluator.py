@@ -114,7 +114,7 @@ class NerfEvaluator(GenericModelEvaluator):
             return preds
         rgb_gt = batch["rgbs"].reshape(h, w, -1).to(self.device)
         masks = batch["mask"].reshape(h, w, -1).to(self.device) if "mask" in batch else None
-        return preds, compute_nerf_metrics(preds, rgb_gt, mask_loss=masks)
+        return preds, compute_nerf_metrics(preds, rgb_gt, mask_loss=masks, validation_mode=True)
 
     def unnorm(self, unnorm_scene, org_mat):
         """Normalised points -> world (reference :234-238 does this on the host; here nm_unnormalize_points)."""

@@ -1,0 +1,98 @@
+"""Training of a NeRF scene model without pytorch-lightning (reference: NerfTrainer, nerfmatch/nerf_trainer.py:28-188, launched by
+train() :307-397).  Host-side plumbing: the training render and the losses are the kernels of nerf/train_render.py under
+torch.autograd.Function, the optimiser and schedule table is trainer._TrainerBase's (the NeRF yamls set `optim.lr`), data parallelism
+is one process per GPU with dist.GradBuckets as in the matcher trainers.
+
+Batches carry the reference's keys: `rays` (1,R,12), `rgbs` (1,R,3), `ts` (1,R) appearance ids, `mask` (R,1) (read when
+loss.use_sem_mask), `seq_ind`, `img_idx`, `img_wh`.  Not built: the two-view pose metrics of log_step (compute_nerf_pose_metrics, :125-136)
+and image logging; validation_step returns the scalar metrics."""
+import torch
+
+from . import dist as nmdist
+from .nerf.renderer import NerfRenderer
+from .nerf.train_render import training_metrics
+from .nerf_evaluator import save_nerf_ckpt
+from .trainer import _TrainerBase
+from .utils.metrics import compute_nerf_metrics
+
+
+def init_pfeat_mask(img_wh, ds=8, sample_num=1):
+    """Boolean mask (sample_num, img_wh[0], img_wh[1], 1) of the rays whose point features a validation render keeps: every ds-th pixel
+    from ds // 2 (reference :28-32)."""
+    pfeat_mask = torch.zeros(sample_num, *img_wh, 1).bool()
+    pfeat_mask[:, ds // 2 :: ds, ds // 2 :: ds] = 1
+    return pfeat_mask
+
+
+class NerfTrainer(_TrainerBase):
+    def __init__(self, config, num_frames=300, device="cuda", bucket_mb=64, optimizer_factory=None, scheduler_factory=None, closest_ind=None):
+        self.config = config
+        self.closest_ind = closest_ind
+        sample_num = 2 if getattr(config.data, "train_pair_txt", None) else 1
+        self.model = NerfRenderer(config, num_frames).to(device)
+        self.model.pfeat_mask = init_pfeat_mask(config.data.img_wh, ds=8, sample_num=sample_num)
+        self.cnfg_loss = getattr(config, "loss", None)
+        self.mask_loss = bool(getattr(self.cnfg_loss, "use_sem_mask", False)) if self.cnfg_loss else False
+        self.gpu_num = getattr(config, "gpu_num", None) or nmdist.world()[1]
+        self.current_epoch = self.global_step = 0
+        self.optimizer = self.scheduler = None
+        self._opt_factory, self._sched_factory = optimizer_factory, scheduler_factory
+        nmdist.broadcast_module(self.model, src=0)
+        self.buckets = nmdist.GradBuckets(self.model.parameters(), bucket_mb=bucket_mb)
+
+    @staticmethod
+    def _rows(x, cols):
+        return x.reshape(-1, cols)
+
+    def training_step(self, data, batch_idx=0, **render_kw):
+        """forward + backward + gradient all-reduce + optimiser step (reference :140-158); returns the step's metrics (detached).
+        render_kw: explicit random draws for the render (t_rand, jitter, noise_coarse, noise_fine)."""
+        if self.optimizer is None:
+            self.configure_optimizers()
+        m = self.model
+        m.ret_pfeat = False
+        m.set_training_mode(True)
+        rays = self._rows(data["rays"], data["rays"].shape[-1])
+        dev = next(m.parameters()).device
+        with torch.enable_grad():
+            preds = m.forward(rays.to(dev), step=self.global_step, ray_id=data["ts"].reshape(-1) if "ts" in data else None, **render_kw)
+            mask = data["mask"].to(dev) if self.mask_loss else None
+            metrics = training_metrics(preds, self._rows(data["rgbs"], 3).to(dev), mask, self.cnfg_loss)
+            self.optimizer.zero_grad(set_to_none=True)
+            self.buckets.start()
+            metrics["loss"].backward()
+        self.buckets.finish()
+        self.optimizer.step()  # (in-place updates bump the parameters' versions: the inference blobs are re-packed on their next use)
+        self.global_step += 1
+        return {k: v.detach() for k, v in metrics.items()}
+
+    def validation_step(self, data, batch_idx=0, **render_kw):
+        """Validation render (ret_pfeat=True, pfeat_mask honoured) and its scalar metrics (reference :160-180)."""
+        m = self.model
+        m.ret_pfeat = True
+        m.set_training_mode(False)
+        rays = self._rows(data["rays"], data["rays"].shape[-1])
+        dev = next(m.parameters()).device
+        seq = torch.as_tensor(data["seq_ind"]).reshape(-1).long()
+        ray_id = seq.repeat_interleave(rays.shape[0] // len(seq))
+        with torch.no_grad():
+            preds = m.forward(rays.to(dev), ray_id=ray_id, validation=True, **render_kw)
+            mask = data["mask"].to(dev) if self.mask_loss else None
+            metrics = compute_nerf_metrics(preds, self._rows(data["rgbs"], 3).to(dev), mask_loss=mask, validation_mode=True, cnfg_loss=self.cnfg_loss)
+        return metrics
+
+    def fit(self, loader, max_epochs=1, log=None):
+        from ._lib import steady_gc
+
+        for _ in range(max_epochs):
+            with steady_gc():
+                for i, batch in enumerate(loader):
+                    metrics = self.training_step(batch, i)
+                    if log is not None:
+                        log(self.current_epoch, i, metrics)
+            self.on_epoch_end()
+
+    def save_checkpoint(self, path):
+        """A checkpoint in the reference's Lightning layout, as load_nerf_render_from_ckpt reads it."""
+        sd = {k: v.detach().cpu() for k, v in self.model.state_dict().items()}
+        save_nerf_ckpt(path, self.config, sd, unnorm_scene=self.model.unnorm_scene, epoch=self.current_epoch, global_step=self.global_step)

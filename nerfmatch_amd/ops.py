@@ -932,17 +932,21 @@ def linear_wgrad(dy, x, out=None):
     return dw
 
 
-def linear_wgrad_bias(dy, x):
-    """(dw, db) = (dy^T @ x, column sums of dy): one launch on the split-bf16 path (dy read once), two otherwise."""
+def linear_wgrad_bias(dy, x, out=None):
+    """(dw, db) = (dy^T @ x, column sums of dy): one launch on the split-bf16 path (dy read once), two otherwise.  out = (dw, db): both are
+    added onto (the chunks of a NeRF training step)."""
     dy, x = _aligned16(dy.contiguous()), _aligned16(x.contiguous())
     M, N = dy.shape
     K = x.shape[1]
     if not (LINEAR_PRECISION == "bf16x3" and N % 2 == 0 and K % 4 == 0 and M > 0):
-        return linear_wgrad(dy, x), col_sum(dy)
-    dw = torch.empty(N, K, device=dy.device, dtype=torch.float32)
-    db = torch.empty(N, device=dy.device, dtype=torch.float32)
+        if out is None:
+            return linear_wgrad(dy, x), col_sum(dy)
+        return linear_wgrad(dy, x, out=out[0]), col_sum(dy, out=out[1])
+    acc = out is not None
+    dw = out[0] if acc else torch.empty(N, K, device=dy.device, dtype=torch.float32)
+    db = out[1] if acc else torch.empty(N, device=dy.device, dtype=torch.float32)
     ws = _scratch(_WGRAD_WS, dy.device, lib().nm_linear_wgrad_workspace_bytes(M, N, K))
-    check(lib().nm_linear_wgrad_bf16x3(dptr(dy), dptr(x), M, N, K, 0, dptr(dw), dptr(db), dptr(ws, torch.uint8), ws.numel(), stream()),
+    check(lib().nm_linear_wgrad_bf16x3(dptr(dy), dptr(x), M, N, K, int(acc), dptr(dw), dptr(db), dptr(ws, torch.uint8), ws.numel(), stream()),
           "nm_linear_wgrad_bf16x3")
     return dw, db
 
@@ -951,10 +955,12 @@ _COLSUM_WS = {}
 _LN_BWD_WS = {}
 
 
-def col_sum(dy):
+def col_sum(dy, out=None):
+    """column sums of dy (M, N) (added onto `out` when given)."""
     dy = dy.contiguous()
     M, N = dy.shape
-    out = torch.zeros(N, device=dy.device, dtype=torch.float32)
+    if out is None:
+        out = torch.zeros(N, device=dy.device, dtype=torch.float32)
     if M:  # (the ordered form: partial sums added in a fixed order -- the same bits on every run)
         ws = _scratch(_COLSUM_WS, dy.device, lib().nm_col_sum_workspace_bytes(M, N))
         check(lib().nm_col_sum_ordered(dptr(dy), M, N, 1, dptr(out), dptr(ws, torch.uint8), ws.numel(), stream()), "nm_col_sum_ordered")

@@ -76,15 +76,52 @@ def average_pose_metrics(metr_all, print_out=True):
     return avg
 
 
-def compute_nerf_metrics(preds, rgb_gt, mask_loss=None):
-    """Validation branch of the reference's compute_nerf_metrics: 0.5 * mean(mask * (rgb - gt)^2) and its PSNR for the
-    coarse and fine images (the 0.5 is the reference's)."""
-    m = torch.round(mask_loss) if mask_loss is not None else 1
+def mse2psnr(mse):
+    return -10 * torch.log10(mse)
+
+
+def lossfun_distortion(t, w):
+    """iint w[i] w[j] |t[i] - t[j]| di dj per ray (reference :453-465): t (R,S+1) fence posts (or (R,S): a zero is put in front), w (R,S)."""
+    if w.shape[-1] == t.shape[-1]:
+        t = torch.hstack((t[:, :1] * 0, t))
+    ut = (t[..., 1:] + t[..., :-1]) / 2
+    dut = torch.abs(ut[..., :, None] - ut[..., None, :])
+    loss_inter = torch.sum(w * torch.sum(w[..., None, :] * dut, dim=-1), dim=-1)
+    loss_intra = torch.sum(w**2 * (t[..., 1:] - t[..., :-1]), dim=-1) / 3
+    return loss_inter + loss_intra
+
+
+def distortion_loss(s, w):
+    """The distortion regulariser of mip-NeRF 360 (reference :448-450)."""
+    return torch.mean(lossfun_distortion(s, w))
+
+
+def compute_nerf_metrics(preds, rgb_gt, mask_loss=None, validation_mode=False, cnfg_loss=None):
+    """The reference's compute_nerf_metrics (:59-96) in plain differentiable torch: 0.5 * mean(mask * (rgb - gt)^2) and its PSNR for the
+    coarse and fine images (the 0.5 is the reference's), `loss` = coarse_weight * coarse + fine and, when training, + ray_reg_weight *
+    distortion_loss(s_fine, weights_fine).  The mask is rounded in validation only.  (The reference's `app_coarse` term is dead code -- its
+    renderer never sets that key -- and is not built.)  A training step on the GPU takes nerf.train_render.training_metrics, the same
+    quantities on the fused loss kernels."""
+    if mask_loss is None:
+        m = 1
+    else:
+        m = torch.round(mask_loss) if validation_mode else mask_loss
     out = {}
-    for key in ("coarse", "fine"):
-        if f"rgb_{key}" in preds:
-            mse = 0.5 * (m * (preds[f"rgb_{key}"] - rgb_gt) ** 2).mean()
-            out[f"rgb_{key}_mse"], out[f"rgb_{key}_psnr"] = mse, -10 * torch.log10(mse)
-    if "rgb_fine_mse" not in out:
+    loss = 0
+    if "rgb_coarse" in preds:
+        mse = 0.5 * (m * (preds["rgb_coarse"] - rgb_gt) ** 2).mean()
+        loss = loss + mse * getattr(cnfg_loss, "coarse_weight", 1.0)
+        out["rgb_coarse_mse"], out["rgb_coarse_psnr"] = mse, mse2psnr(mse)
+    if "rgb_fine" in preds:
+        mse = 0.5 * (m * (preds["rgb_fine"] - rgb_gt) ** 2).mean()
+        loss = loss + mse
+        out["rgb_fine_mse"], out["rgb_fine_psnr"] = mse, mse2psnr(mse)
+    else:
         out["rgb_fine_mse"], out["rgb_fine_psnr"] = out["rgb_coarse_mse"], out["rgb_coarse_psnr"]
+    if not validation_mode:
+        reg = getattr(cnfg_loss, "ray_reg_weight", None)
+        if "s_fine" in preds and reg:
+            loss = loss + distortion_loss(preds["s_fine"], preds["weights_fine"]) * reg
+    out["loss"] = loss
     return out
+

@@ -1,0 +1,453 @@
+"""GPU: NeRF scene training -- the per-ray kernels of csrc/nerf_train.hip, the GEMM-chain weight gradients, the training render end to end
+against the reference's recorded step and the fp64 helper (tests/nerf_train_util.py), chunking and the trainer.
+
+R = 37 rays, S in {32, 64, 128}: half a wavefront, one wavefront and two samples per lane for the one-wavefront-per-ray kernels; n = R S is
+ragged against the 128-row GEMM tiles (9.25 and 18.5 tiles; 37 whole tiles at S = 128).
+
+Why the end-to-end gradient check is a whole-network L2 distance and not per tensor: the distance between two independently rounded runs
+of the same step is bimodal per tensor (one ReLU or density gate flipping under rounding moves a small tensor by 1e-4 ... 2e-2, the fp32
+oracle against the fp64 oracle already does that), while all gradient tensors of a network taken as one vector move by < 5e-5.  Per-tensor
+agreement IS asserted where it is well defined: with the gates shared (test_mlp_gradients_with_shared_gates)."""
+from argparse import Namespace
+
+import pytest
+import torch
+
+import nerf_train_util as ntu
+from conftest import load_golden
+from nerfmatch_amd import synth
+from oracle import nerf_oracle as no
+
+pytestmark = pytest.mark.gpu
+
+R = 37
+SS = (32, 64, 128)
+CEIL = {"fp32": 2e-3, "bf16x3": 5e-3}  # the project's bars for a training step's weight gradients (test_training_step_mid_size_vs_oracle)
+rel = lambda a, b: float((a.double().cpu() - b.double().cpu()).abs().max()) / max(float(b.abs().max()), 1e-30)
+
+
+def make_rays(n, seed, scale=1.3):
+    """rays[:, 3:6] = scale x rays[:, 8:11]: direction and view direction cannot be confused."""
+    g = torch.Generator().manual_seed(seed)
+    o = (torch.rand(n, 3, generator=g) - 0.5) * 0.4
+    v = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    od = (o * v).sum(1, keepdim=True)
+    far = torch.sqrt(od * od + 1.0 - (o * o).sum(1, keepdim=True)) - od
+    return torch.cat([o, scale * v, torch.full((n, 1), 0.01), far / scale, v, torch.full((n, 1), 2.0 / 12**0.5 / 525.0)], 1).contiguous()
+
+
+def sorted_t(n, S, g, lo=0.05, hi=1.5):
+    return (lo + (hi - lo) * torch.sort(torch.rand(n, S + 1, generator=g), dim=1).values).contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------------------- per-ray kernels
+@pytest.mark.parametrize("S,white,noisy,with_gw", [(32, False, False, False), (32, True, True, True), (64, True, False, True),
+                                                   (64, False, True, False), (128, True, True, False), (128, False, False, True)])
+def test_composite_forward_backward_vs_fp64(gpu, built_lib, S, white, noisy, with_gw):
+    """nm_nerf_train_composite / _bwd against fp64 autograd over the oracle's compositing from the SAME out4 / t / noise; |raw + noise| > 1e-3
+    keeps the density gate unambiguous.  Bar: 5e-6 of the largest entry (that of test_wavefront_compositing_vs_per_ray_loops)."""
+    from nerfmatch_amd.nerf import train_render as tr
+
+    g = torch.Generator().manual_seed(S + 2 * white + noisy)
+    n = R * S
+    out4 = torch.randn(n, 4, generator=g)
+    out4[:, 3] = out4[:, 3] * 40 + 10
+    noise = torch.randn(R, S, generator=g) if noisy else None
+    std = 1.0 if noisy else 0.0
+    eff = out4[:, 3].reshape(R, S) + (noise * std if noisy else 0)
+    fix = eff.abs() <= 1e-3
+    out4[:, 3] = torch.where(fix.reshape(-1), out4[:, 3] + 0.01, out4[:, 3])
+    rays, t = make_rays(R, 5), sorted_t(R, S, g)
+    G, g_w = torch.randn(R, 3, generator=g), (torch.randn(R, S, generator=g) if with_gw else None)
+    with torch.enable_grad():
+        o64 = out4.double().requires_grad_(True)
+        raw = o64.reshape(R, S, 4)
+        sig = raw[..., 3] + (noise.double() * std if noisy else 0)
+        want = no.composite(torch.cat([torch.sigmoid(raw[..., :3]), sig[..., None]], -1), t.double(), rays[:, 3:6].double(), white)
+        obj = (want[0] * G.double()).sum() + ((want[3] * g_w.double()).sum() if with_gw else 0)
+        (g_want,) = torch.autograd.grad(obj, o64)
+    d = lambda x: None if x is None else x.to(gpu).contiguous()
+    got = tr.composite(d(out4), d(t), d(rays), d(noise), std, white)
+    g4 = tr.composite_bwd(d(out4), d(t), d(rays), d(G), d(g_w), d(noise), std, white)
+    errs = {k: rel(a, b.detach()) for k, a, b in zip(("rgb", "depth", "acc", "weights"), got, want)}
+    errs["g_logit"], errs["g_sigma"] = rel(g4[:, :3], g_want[:, :3]), rel(g4[:, 3], g_want[:, 3])
+    print(f"composite S={S} white={white} noise={noisy} g_w={with_gw}: " + "  ".join(f"{k} {v:.1e}" for k, v in errs.items()))
+    assert float(g_want[:, 3].abs().max()) > 0 and float(g_want[:, :3].abs().max()) > 0
+    closed = (out4[:, 3] + (noise.reshape(-1) * std if noisy else 0)) <= 0
+    assert closed.any() and not g4[:, 3].cpu()[closed].any() and not g_want[:, 3][closed].any()  # the gate is raw + noise, not raw
+    assert all(v < 5e-6 for v in errs.values()), errs
+
+
+@pytest.mark.parametrize("S", SS)
+def test_distortion_and_s_vs_fp64(gpu, built_lib, S):
+    """s, the per-ray and mean distortion loss and its gradient against fp64 from the same t / weights.  Rays 0 and 1 span very different
+    ranges: s must come from the BATCH-wide near and far (a per-ray normalisation would put every ray on [0, 1])."""
+    from nerfmatch_amd.nerf import train_render as tr
+
+    g = torch.Generator().manual_seed(S)
+    t = sorted_t(R, S, g)
+    t[0] = 0.01 + 0.01 * torch.sort(torch.rand(S + 1, generator=g)).values
+    t[1] = 1.0 + 4.0 * torch.sort(torch.rand(S + 1, generator=g)).values
+    w = torch.rand(R, S, generator=g) / S * 3
+    with torch.enable_grad():
+        w64 = w.double().requires_grad_(True)
+        s_want = ntu.t_to_s(t.double())
+        per_ray = ntu.lossfun_distortion(s_want, w64)
+        (g_want,) = torch.autograd.grad(per_ray.mean() * 0.37, w64)
+    s = tr.t_to_s(t.to(gpu))
+    _, got_ray, got_mean = tr._distortion(s, True, w.to(gpu).contiguous())
+    g_w = tr.distortion_bwd(s, w.to(gpu).contiguous(), 0.37)
+    errs = dict(s=rel(s, s_want), per_ray=rel(got_ray, per_ray.detach()), mean=abs(float(got_mean) - float(per_ray.mean())) / float(per_ray.mean()),
+                g_w=rel(g_w, g_want))
+    print(f"distortion S={S}: " + "  ".join(f"{k} {v:.1e}" for k, v in errs.items()))
+    assert float(s_want[0].max()) < 0.6 and float(s_want[1].min()) > 0.9  # the fixture: neither ray covers [0, 1] on its own
+    assert all(v < 5e-6 for v in errs.values()), errs
+
+
+@pytest.mark.parametrize("masked", [False, True])
+def test_photo_loss_vs_fp64(gpu, built_lib, masked):
+    from nerfmatch_amd.nerf import train_render as tr
+
+    g = torch.Generator().manual_seed(3 + masked)
+    rgb_c, rgb_f, gt = (torch.rand(R, 3, generator=g) for _ in range(3))
+    mask = torch.rand(R, 1, generator=g) if masked else None
+    with torch.enable_grad():
+        c64, f64 = rgb_c.double().requires_grad_(True), rgb_f.double().requires_grad_(True)
+        m = mask.double() if masked else 1
+        mse_c, mse_f = 0.5 * (m * (c64 - gt.double()) ** 2).mean(), 0.5 * (m * (f64 - gt.double()) ** 2).mean()
+        gc, gf = torch.autograd.grad(0.7 * mse_c + mse_f, [c64, f64])
+        cg, fg = rgb_c.to(gpu).requires_grad_(True), rgb_f.to(gpu).requires_grad_(True)
+        total, mse = tr._PhotoLoss.apply(cg, fg, gt.to(gpu), None if mask is None else mask.to(gpu), 0.7)
+        total.backward()
+    errs = dict(mse_c=abs(float(mse[0]) - float(mse_c)) / float(mse_c), mse_f=abs(float(mse[1]) - float(mse_f)) / float(mse_f),
+                total=abs(float(total) - float(0.7 * mse_c + mse_f)) / float(0.7 * mse_c + mse_f), g_c=rel(cg.grad, gc), g_f=rel(fg.grad, gf))
+    print(f"photo loss masked={masked}: " + "  ".join(f"{k} {v:.1e}" for k, v in errs.items()))
+    assert all(v < 5e-6 for v in errs.values()), errs
+
+
+@pytest.mark.parametrize("S", SS)
+def test_encode_vs_helper(gpu, built_lib, S):
+    """xi / xd against the helper's fp32 encodings of the same fence posts at the encoders' pinned 2e-7 (absolute; values in [-1, 1]); the
+    appearance columns are each ray's own table row; var_scale on; an id outside the table is clamped and counted, and refused when the
+    ids are on the host."""
+    from nerfmatch_amd import _lib
+    from nerfmatch_amd.nerf import train_render as tr
+
+    g = torch.Generator().manual_seed(S)
+    rays, t = make_rays(R, 7), sorted_t(R, S, g, 0.01, 0.9)
+    table = torch.randn(5, 16, generator=g)
+    ids = torch.randint(0, 5, (R,), generator=g)
+    x_pts, x_dir, x_app = ntu.encode(rays, t, ids, table, var_scale=0.5)
+    xi, xd = tr.encode(rays.to(gpu), t.to(gpu), ids.to(gpu), table.to(gpu), var_scale=0.5)
+    xi, xd = xi.cpu(), xd.cpu()
+    e_pts, e_dir = float((xi[:, :90] - x_pts).abs().max()), float((xd[:, :27] - x_dir).abs().max())
+    print(f"encode S={S}: |xi - helper| {e_pts:.2e}  |xd - helper| {e_dir:.2e}")
+    assert e_pts <= 2e-7 and e_dir <= 2e-7
+    assert torch.equal(xd[:, 27:43], x_app) and not xi[:, 90:].any() and not xd[:, 43:].any()
+    # var_scale off differs (the option is not ignored); no table: zero appearance columns
+    xi0, xd0 = tr.encode(rays.to(gpu), t.to(gpu))
+    assert float((xi0.cpu() - xi).abs().max()) > 1e-3 and not xd0[:, 27:].any()
+    bad = ids.clone()
+    bad[3], bad[11] = 5, -2
+    status = torch.zeros(1, dtype=torch.int32, device=gpu)
+    _, xdb = tr.encode(rays.to(gpu), t.to(gpu), bad.to(gpu), table.to(gpu), status=status)
+    assert int(status) == 2
+    assert torch.equal(xdb[3 * S, 27:43].cpu(), table[4]) and torch.equal(xdb[11 * S, 27:43].cpu(), table[0])
+    with pytest.raises(_lib.NerfmatchAmdError):
+        tr.encode(rays.to(gpu), t.to(gpu), bad.to(gpu), table.to(gpu), ray_id_host=bad)
+
+
+@pytest.mark.parametrize("S", SS)
+def test_app_grad_fixed_order(gpu, built_lib, S):
+    from nerfmatch_amd.nerf import train_render as tr
+
+    g = torch.Generator().manual_seed(S)
+    ga, gb = torch.randn(R * S, 48, generator=g), torch.randn(R * S, 48, generator=g)
+    ids = torch.randint(0, 4, (R,), generator=g)
+    ids[ids == 2] = 4  # id 2 never occurs
+    want = torch.zeros(5, 16, dtype=torch.float64)
+    want.index_add_(0, ids, (ga + gb).double().reshape(R, S, 48)[:, :, 27:43].sum(1))
+    runs = [tr.app_grad(ga.to(gpu), gb.to(gpu), ids.to(gpu), R, S, torch.zeros(5, 16, device=gpu)) for _ in range(2)]
+    one = tr.app_grad(ga.to(gpu), None, ids.to(gpu), R, S, torch.zeros(5, 16, device=gpu))
+    want_one = torch.zeros(5, 16, dtype=torch.float64).index_add_(0, ids, ga.double().reshape(R, S, 48)[:, :, 27:43].sum(1))
+    print(f"app grad S={S}: {rel(runs[0], want):.1e} (two inputs)  {rel(one, want_one):.1e} (one)")
+    assert torch.equal(runs[0], runs[1])
+    assert not runs[0][2].any() and runs[0][[0, 1, 3, 4]].abs().min() > 0
+    assert rel(runs[0], want) < 5e-6 and rel(one, want_one) < 5e-6
+
+
+# ------------------------------------------------------------------------------------------------------------------- MLP gradients
+def shared_gate_grads(P, saved, g4, app):
+    """fp64 gradients of one network's 24 parameters for d loss / d out4 = g4, with the ReLU gates of the activations the GPU forward saved:
+    dW_l = (g_l * [h_l > 0])^T h_{l-1}, db_l, and the dX chain through those gates."""
+    xi, xd, h, feat, hv = [[y.double().cpu() for y in x] if isinstance(x, list) else x.double().cpu() for x in saved]
+    P = [p.double().cpu() for p in P]
+    W, b = P[0:16:2], P[1:16:2]
+    Wa, _, Wf, _, Wv, _, Wr, _ = P[16:24]
+    g4 = g4.double().cpu()
+    g_logit, g_sig = g4[:, :3], g4[:, 3:4]
+    out = {}
+    out[22], out[23] = g_logit.T @ hv, g_logit.sum(0)
+    dy_v = (g_logit @ Wr) * (hv > 0)
+    out[20], out[21] = dy_v.T @ torch.cat([feat, xd[:, : 27 + app]], 1), dy_v.sum(0)
+    g_xd = dy_v @ Wv[:, 256:]
+    g_feat = dy_v @ Wv[:, :256]
+    out[18], out[19] = g_feat.T @ h[7], g_feat.sum(0)
+    out[16], out[17] = g_sig.T @ h[7], g_sig.sum(0)
+    gcur = (g_feat @ Wf + g_sig @ Wa) * (h[7] > 0)
+    for l in range(7, 0, -1):
+        x = torch.cat([xi[:, :90], h[4]], 1) if l == 5 else h[l - 1]
+        out[2 * l], out[2 * l + 1] = gcur.T @ x, gcur.sum(0)
+        gcur = (gcur @ W[l][:, -256:]) * (h[l - 1] > 0)
+    out[0], out[1] = gcur.T @ xi[:, :90], gcur.sum(0)
+    return [out[i] for i in range(24)], g_xd
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+@pytest.mark.parametrize("net,S", [("nerf_fine", 32), ("nerf_fine", 64), ("nerf_fine", 128), ("nerf_coarse", 32)])
+def test_mlp_gradients_with_shared_gates(gpu, built_lib, precision, net, S):
+    """Every weight / bias gradient of the GEMM chain (dW through ops.linear_wgrad_bias, two GEMMs for the skip and views layers written into
+    column blocks, padding dropped) and d loss / d xd against fp64 with the gates of the activations the GPU forward saved: given the gates
+    the map g_out4 -> gradients is linear, so every tensor is asserted.  Ceiling 2e-3 (fp32) / 5e-3 (bf16x3) of the largest entry; a wrong
+    gate, block or transpose is an O(1) error.  Measured on MI355X: see DESIGN.md section 5."""
+    import nerfmatch_amd
+    from nerfmatch_amd.nerf import train_render as tr
+
+    g = torch.Generator().manual_seed(S)
+    sd = synth.nerf_state_dict(seed=0, app_vocab=5, density_bias=3.0)
+    names = [f"{net}.pts_linears.{l}.{k}" for l in range(8) for k in ("weight", "bias")]
+    names += [f"{net}.{m}.{k}" for m in tr.HEAD for k in ("weight", "bias")]
+    P = [sd[k].to(gpu).contiguous() for k in names]
+    rays, t = make_rays(R, 9), sorted_t(R, S, g, 0.01, 0.9)
+    ids = torch.randint(0, 5, (R,), generator=g)
+    xi, xd = tr.encode(rays.to(gpu), t.to(gpu), ids.to(gpu), sd["embedding_a.weight"].to(gpu))
+    g4 = torch.randn(R * S, 4, generator=g).to(gpu)
+    nerfmatch_amd.set_precision(precision)
+    try:
+        chain = tr.Chain(P)
+        out4, saved = chain.forward(xi, xd)
+        grads = tr.Chain.new_grads(gpu)
+        g_xd = chain.backward(g4, saved, grads, want_g_xd=True)
+        got = chain.finish(grads)
+    finally:
+        nerfmatch_amd.set_precision("fp32")
+    want, want_xd = shared_gate_grads(P, saved, g4, 16)
+    errs = {k: rel(a, b) for k, a, b in zip(names, got, want)}
+    errs["g_xd"] = rel(g_xd[:, :43], want_xd)
+    print(f"shared-gate gradients {net} S={S} {precision}: worst {max(errs.values()):.2e} ({max(errs, key=errs.get)})  median {sorted(errs.values())[12]:.2e}")
+    for k, a, b in zip(names, got, want):
+        assert a.shape == sd[k].shape and float(b.abs().max()) > 0, k
+    assert not g_xd[:, 43:].any()
+    assert all(v < CEIL[precision] for v in errs.values()), {k: v for k, v in errs.items() if v >= CEIL[precision]}
+
+
+# ------------------------------------------------------------------------------------------------------------------- end to end
+def scene(app, seed=0):
+    cfg = synth.nerf_config("cambridge" if app else "7scenes", num_pts=32, img_wh=(8, 8))
+    sd = synth.nerf_state_dict(seed=seed, app_vocab=5 if app else 0, density_bias=3.0)
+    return cfg, sd
+
+
+def renderer_for(cfg, sd, gpu, app, S):
+    from nerfmatch_amd.nerf.renderer import NerfRenderer
+
+    cfg.coarse_nerf.num_pts = cfg.fine_nerf.num_pts = S
+    ren = NerfRenderer(cfg, num_frames=5 if app else None, training=True)
+    ren.load_state_dict(sd)
+    return ren.to(gpu)
+
+
+def gpu_step(ren, rays, gt, draws, ray_id, mask, cnfg_loss, gpu):
+    """one training render + loss + backward on the GPU -> preds (debug), metrics, {state-dict name: gradient}"""
+    from nerfmatch_amd.nerf import train_render as tr
+
+    d = lambda x: None if x is None else x.to(gpu)
+    ren.zero_grad(set_to_none=True)
+    with torch.enable_grad():
+        preds = ren.render_rays(d(rays), ray_id=d(ray_id), validation=False, debug=True, **{k: d(v) for k, v in draws.items()})
+        metrics = tr.training_metrics(preds, d(gt), d(mask), cnfg_loss)
+        metrics["loss"].backward()
+    grads = {k: p.grad.detach().cpu() for k, p in ren.named_parameters() if p.grad is not None}
+    return preds, metrics, grads
+
+
+def draws_for(n, S, seed):
+    g = torch.Generator().manual_seed(seed)
+    return dict(t_rand=torch.rand(n, S + 1, generator=g), jitter=synth.resample_jitter((n, S + 1), seed + 1),
+                noise_coarse=torch.randn(n, S, generator=g), noise_fine=torch.randn(n, S, generator=g))
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+@pytest.mark.parametrize("app,S", [(False, 32), (True, 32), (True, 64), (False, 128)])
+def test_training_step_vs_fp64_helper(gpu, built_lib, precision, app, S):
+    """The whole step (render with draws given, losses, backward) against the helper in fp64, evaluated at the GPU path's own fence posts
+    (the resampler's parity is tested elsewhere and no gradient flows through it).  Preds at 1e-4 of scale, loss at 1e-5 relative, the
+    WHOLE-NETWORK relative L2 distance of the gradients per network and for the appearance table under the 2e-3 / 5e-3 ceiling (the fp32
+    oracle's own distance to fp64 is <= 4.3e-5; a flipped gate costs ~1e-5, a wrong layer O(1)).  Per-tensor distances are printed only.
+    One id (2) never occurs: its table row's gradient must be exactly zero."""
+    import nerfmatch_amd
+
+    cfg, sd = scene(app)
+    ren = renderer_for(cfg, sd, gpu, app, S)
+    g = torch.Generator().manual_seed(17 + S)
+    rays, gt = make_rays(R, 11), torch.rand(R, 3, generator=g)
+    ids = mask = None
+    if app:
+        ids = torch.randint(0, 4, (R,), generator=g)
+        ids[ids == 2] = 4
+        mask = torch.rand(R, 1, generator=g)
+    draws = draws_for(R, S, 23)
+    nerfmatch_amd.set_precision(precision)
+    try:
+        preds, metrics, grads = gpu_step(ren, rays, gt, draws, ids, mask, cfg.loss, gpu)
+    finally:
+        nerfmatch_amd.set_precision("fp32")
+    ref = ntu.train_step(sd, rays, gt, noise_coarse=draws["noise_coarse"], noise_fine=draws["noise_fine"], noise_std=1.0, white_bg=app, ray_id=ids,
+                         mask=mask, ray_reg_weight=cfg.loss.ray_reg_weight, t_coarse=preds["t_coarse"].cpu(), t_fine=preds["t_fine"].cpu())
+    assert set(preds) == {"rgb_coarse", "depth_coarse", "rgb_fine", "depth_fine", "s_fine", "weights_fine", "t_coarse", "t_fine", "weights_coarse"}
+    for k in ("rgb_coarse", "rgb_fine", "depth_coarse", "depth_fine", "s_fine", "weights_fine"):
+        e = rel(preds[k], ref["preds"][k])
+        print(f"  {k}: {e:.2e}")
+        assert e < 1e-4, (k, e)
+    e_loss = abs(float(metrics["loss"]) - float(ref["loss"])) / float(ref["loss"])
+    print(f"  loss {float(metrics['loss']):.6f} vs {float(ref['loss']):.6f}: {e_loss:.2e}")
+    assert e_loss < 1e-5
+    assert abs(float(metrics["rgb_fine_psnr"]) - float(ref["metrics"]["rgb_fine_psnr"])) < 1e-3
+    for k, gr in ref["grads"].items():
+        assert float(gr.abs().max()) > 0, k
+        print(f"    {k}: {rel(grads[k], gr):.2e}")
+    nets = list(ntu.NETS) + (["embedding_a"] if app else [])
+    dist = {n: ntu.net_l2(grads, ref["grads"], n) for n in nets}
+    print(f"training step app={app} S={S} {precision}: whole-network L2 " + "  ".join(f"{k} {v:.2e}" for k, v in dist.items()))
+    assert all(v < CEIL[precision] for v in dist.values()), dist
+    if app:
+        assert not grads["embedding_a.weight"][2].any() and not ref["grads"]["embedding_a.weight"][2].any()
+        assert all(grads["embedding_a.weight"][i].abs().max() > 0 for i in (0, 1, 3, 4))
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+@pytest.mark.parametrize("name", ["nerf_train_7s", "nerf_train_cam"])
+def test_training_step_vs_reference_fixture(gpu, built_lib, precision, name):
+    """The same step against what the REFERENCE recorded (tests/golden/make_golden_nerf_train.py: its NerfRenderer in training mode,
+    compute_nerf_metrics, backward; draws replayed from the fixture): preds at 1e-4 of scale, loss at 1e-5, whole-network gradient L2 under
+    the ceiling -- full tensors for the biases, heads and table, the fixture's strided subsample for the 256-wide matrices."""
+    import nerfmatch_amd
+
+    fx = load_golden(name)
+    app, S = bool(fx["app"]), int(fx["S"])
+    cfg, sd = scene(app, seed=int(fx["weights_seed"]))
+    ren = renderer_for(cfg, sd, gpu, app, S)
+    draws = {k: fx[k] for k in ("t_rand", "jitter", "noise_coarse", "noise_fine")}
+    nerfmatch_amd.set_precision(precision)
+    try:
+        preds, metrics, grads = gpu_step(ren, fx["rays"], fx["rgbs"], draws, fx["ray_id"] if app else None, fx["mask"] if app else None, cfg.loss, gpu)
+    finally:
+        nerfmatch_amd.set_precision("fp32")
+    for k in ("rgb_coarse", "rgb_fine", "depth_coarse", "depth_fine", "s_fine", "weights_fine"):
+        e = rel(preds[k], fx[f"pred_{k}"])
+        print(f"  {k}: {e:.2e}")
+        assert e < 1e-4, (k, e)
+    e_loss = abs(float(metrics["loss"]) - float(fx["loss"])) / float(fx["loss"])
+    print(f"  loss: {e_loss:.2e}")
+    assert e_loss < 1e-5
+    stride = int(fx["sub_stride"])
+    num, den = {}, {}
+    for k, gr in grads.items():
+        net = k.split(".")[0]
+        if f"g_{k}" in fx:
+            a, b = gr.double().reshape(-1), fx[f"g_{k}"].double().reshape(-1)
+        else:
+            a, b = gr.double().reshape(-1)[::stride], fx[f"gsub_{k}"].double()
+            n_rel = abs(float(gr.double().norm()) - float(fx[f"gnorm_{k}"])) / float(fx[f"gnorm_{k}"])
+            assert n_rel < CEIL[precision], (k, n_rel)
+        assert float(b.abs().max()) > 0, k
+        num[net], den[net] = num.get(net, 0.0) + float(((a - b) ** 2).sum()), den.get(net, 0.0) + float((b**2).sum())
+    dist = {n: (num[n] / den[n]) ** 0.5 for n in num}
+    print(f"{name} {precision}: whole-network L2 against the reference " + "  ".join(f"{k} {v:.2e}" for k, v in dist.items()))
+    assert set(dist) == {"nerf_coarse", "nerf_fine"} | ({"embedding_a"} if app else set())
+    assert all(v < CEIL[precision] for v in dist.values()), dist
+
+
+def test_chunked_step_matches_one_chunk(gpu, built_lib):
+    """A chunk of 16 rays (three chunks, the last ragged) against one chunk: preds at 1e-5 of scale (a GEMM may tile another row count another
+    way), gradients within 1e-5 whole-network L2 (the chunks' weight gradients are summed in another order)."""
+    cfg, sd = scene(True)
+    g = torch.Generator().manual_seed(5)
+    rays, gt, ids, mask = make_rays(R, 13), torch.rand(R, 3, generator=g), torch.randint(0, 5, (R,), generator=g), torch.rand(R, 1, generator=g)
+    draws = draws_for(R, 32, 29)
+    out = []
+    for chunk in (None, 16):
+        ren = renderer_for(cfg, sd, gpu, True, 32)
+        ren.train_chunk_rays = chunk
+        out.append(gpu_step(ren, rays, gt, draws, ids, mask, cfg.loss, gpu))
+    (p1, m1, g1), (p2, m2, g2) = out
+    assert all(rel(p2[k], p1[k]) < 1e-5 for k in p1), {k: rel(p2[k], p1[k]) for k in p1}
+    dist = {n: ntu.net_l2(g2, g1, n) for n in list(ntu.NETS) + ["embedding_a"]}
+    print("chunk of 16 rays against one chunk: " + "  ".join(f"{k} {v:.2e}" for k, v in dist.items()))
+    assert all(v < 1e-5 for v in dist.values()), dist
+    from nerfmatch_amd.nerf import train_render as tr
+    assert tr.chunk_rays_for(128, 2 << 30) * 128 * tr.SAVED_FLOATS * 4 <= 2 << 30 < (tr.chunk_rays_for(128, 2 << 30) + 1) * 128 * tr.SAVED_FLOATS * 4
+
+
+def test_training_flags(gpu, built_lib):
+    """training off with validation=False: no noise (the given draws are not read); ret_pfeat=True with validation=False keeps raising."""
+    cfg, sd = scene(False)
+    ren = renderer_for(cfg, sd, gpu, False, 32)
+    rays = make_rays(R, 3).to(gpu)
+    draws = {k: v.to(gpu) for k, v in draws_for(R, 32, 31).items()}
+    noisy = ren.render_rays(rays, validation=False, **draws)
+    ren.set_training_mode(False)
+    quiet = ren.render_rays(rays, validation=False, **draws)
+    again = ren.render_rays(rays, validation=False, t_rand=draws["t_rand"], jitter=draws["jitter"])
+    assert torch.equal(quiet["rgb_fine"], again["rgb_fine"]) and not torch.equal(quiet["rgb_fine"], noisy["rgb_fine"])
+    assert set(quiet) == {"rgb_coarse", "depth_coarse", "rgb_fine", "depth_fine", "s_fine", "weights_fine"}
+    ren.ret_pfeat = True
+    with pytest.raises(NotImplementedError, match="ret_pfeat"):
+        ren.render_rays(rays, validation=False)
+
+
+# ------------------------------------------------------------------------------------------------------------------- trainer
+def test_trainer_steps_checkpoint_and_pfeat_mask(gpu, built_lib, tmp_path):
+    """Four training steps on a fixed 64-ray batch reduce the loss; the validation render after them equals, bit for bit, that of a fresh
+    renderer loaded from the saved checkpoint (no stale packed blob or calibration survives optimizer.step()) and differs from the render
+    before training; pfeat_mask keeps the masked rays' feature rows; a mask of the wrong length raises."""
+    from nerfmatch_amd.nerf_evaluator import load_nerf_render_from_ckpt
+    from nerfmatch_amd.nerf_trainer import NerfTrainer
+
+    cfg, sd = scene(True)
+    cfg.optim = Namespace(optimizer="adam", lr=5e-4, weight_decay=0.0, lr_scheduler=None)
+    tr = NerfTrainer(cfg, num_frames=5, device=gpu)
+    tr.model.load_state_dict(sd)
+    n = 64
+    g = torch.Generator().manual_seed(41)
+    batch = dict(rays=make_rays(n, 15, scale=1.0)[None].to(gpu), rgbs=torch.rand(1, n, 3, generator=g).to(gpu), ts=torch.randint(0, 5, (1, n), generator=g),
+                 mask=torch.rand(n, 1, generator=g).to(gpu), seq_ind=[1], img_idx=[0], img_wh=torch.tensor([[8, 8]]))
+    val = dict(t_rand=torch.rand(n, 33, generator=g).to(gpu), jitter=synth.resample_jitter((n, 33), 43).to(gpu))
+    draws = {k: v.to(gpu) for k, v in draws_for(n, 32, 47).items()}
+    tr.model.pfeat_mask = None
+    tr.model.ret_pfeat = True
+    before = tr.model.render_rays(batch["rays"][0], ray_id=torch.ones(n, dtype=torch.long), validation=True, **val)
+    losses = [float(tr.training_step(batch, i, **draws)["loss"]) for i in range(4)]
+    print("losses of four steps:", losses)
+    assert losses[-1] < losses[0] and all(torch.isfinite(torch.tensor(losses)))
+    metrics = tr.validation_step(batch, **val)
+    assert float(metrics["rgb_fine_psnr"]) > 0 and "loss" in metrics
+    after = tr.model.render_rays(batch["rays"][0], ray_id=torch.ones(n, dtype=torch.long), validation=True, **val)
+    tr.save_checkpoint(tmp_path / "scene.ckpt")
+    fresh = load_nerf_render_from_ckpt(tmp_path / "scene.ckpt", gpu)
+    fresh.ret_pfeat = True
+    want = fresh.render_rays(batch["rays"][0], ray_id=torch.ones(n, dtype=torch.long), validation=True, **val)
+    for k in ("rgb_fine", "feat_fine", "pts_fine", "rgb_coarse"):
+        assert torch.equal(after[k], want[k]), k
+        assert not torch.equal(after[k], before[k]), k
+    mask = torch.zeros(n, dtype=torch.bool)
+    mask[3::8] = True
+    tr.model.pfeat_mask = mask.reshape(1, 8, 8, 1)
+    masked = tr.model.render_rays(batch["rays"][0], ray_id=torch.ones(n, dtype=torch.long), validation=True, **val)
+    assert torch.equal(masked["feat_fine"], after["feat_fine"][mask.to(gpu)]) and torch.equal(masked["rgb_fine"], after["rgb_fine"])
+    tr.model.pfeat_mask = torch.ones(n + 1, dtype=torch.bool)
+    with pytest.raises(ValueError, match="pfeat_mask"):
+        tr.model.render_rays(batch["rays"][0], ray_id=torch.ones(n, dtype=torch.long), validation=True, **val)
+    tr.model.pfeat_mask = None
+    tr.fit([batch], max_epochs=1)
+    assert tr.global_step == 5 and tr.current_epoch == 1
