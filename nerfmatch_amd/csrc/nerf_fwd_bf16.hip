@@ -20,8 +20,8 @@
 //     neuron (r&3)+8*(r>>2)+4*half) maps 8 consecutive registers of a lane onto the 8 K-slots of one 32x32x16 step, so
 //     re-packing into (hi, lo) bf16 B operands is lane-local (bias, relu, cvt, subtract, cvt);
 //   * cross-layer software pipeline: a finished layer is moved out of the accumulators (AGPRs -> 128 VGPR scalars) and
-//     re-packed one K-step "unit" at a time INSIDE the K-loop of the layer that consumes it, 3-4 VALU instructions
-//     behind each MFMA of the second half slot (pinned with sched_barriers and opaque asm, see UnitWork), so that only
+//     re-packed one K-step "unit" at a time INSIDE the K-loop of the layer that consumes it, at most 5 VALU instructions
+//     behind an MFMA (pinned with sched_barriers and opaque asm; which gap carries what: the table at UnitWork), so that only
 //     the 128 accumulator reads and unit 0 are exposed per layer;
 //   * weights are pre-split and pre-ordered on the host into 16 KiB "slots" = one K-step for all 8 output blocks,
 //     streamed by all 4 wavefronts with global_load_lds (LDS DMA, no VGPRs) into a 4-slot LDS ring: two slots in use, two
@@ -314,7 +314,7 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     // ---- 8 pts layers + views layer (feature_linear folded in at pack time), software pipelined across layers ----------
     // The finished layer is moved out of the accumulators (finish_layer: AGPRs -> cx.hv, plus unit 0) and re-packed one
     // K-step unit at a time INSIDE the K-loop of the layer that consumes it: unit u+1 (bias, relu, hi/lo split = ~40 VALU
-    // instructions) is computed in the shadow of the second-half MFMAs of K-step u (UnitWork, slot_step8).
+    // instructions) is computed in the shadow of the MFMAs of K-step u (UnitWork and its per-gap schedule, slot_step8).
     Ctx cx;
     cx.blob_slots = blob_slots; cx.ring = ring; cx.sm_small = sm_small;
     cx.tapw = reinterpret_cast<f32x4*>(a.ws) + ((size_t)blockIdx.x * 4 + wave) * 32 * 64 + lane;

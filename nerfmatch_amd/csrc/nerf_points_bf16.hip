@@ -179,7 +179,7 @@ __device__ __forceinline__ void points_fwd_body(const PointsArgs& a) {
 
 // ---- backward -----------------------------------------------------------------------------------------------------------
 // Unit u of the gradient held in cx.hv (registers 8m .. 8m+7 of block u >> 1), multiplied by its ReLU gate (GATED: byte u & 3 of
-// gw[u >> 2], gate_byte's bit order) and split into bf16 hi / lo -- same 12 pieces as UnitWork, same placement rules.
+// gw[u >> 2], gate_byte's bit order) and split into bf16 hi / lo -- the operations of UnitWork (no bias), placed by the same tables.
 template <bool GATED>
 struct UnitWorkB {
   Ctx& cx;
@@ -188,48 +188,52 @@ struct UnitWorkB {
   u32x4 gw;
   float v8[8];
   float f0, f1;
-  __device__ __forceinline__ void prefetch() {}
-  __device__ __forceinline__ void operator()(int j) {
-    const int ob = u >> 1, m = u & 1;
-    if (j < 4) {  // elements j and 4 + j
-      float a0 = cx.hv[ob * 16 + 8 * m + j], a1 = cx.hv[ob * 16 + 8 * m + 4 + j];
-      if constexpr (GATED) {
-        const unsigned w = gw[u >> 2];
-        const int base = 8 * (u & 3);
-        // element e: bit e / 2 (e even) or 4 + e / 2 (e odd)
-        const int e0 = j, e1 = 4 + j;
-        const int b0 = base + ((e0 & 1) ? 4 + (e0 >> 1) : (e0 >> 1)), b1 = base + ((e1 & 1) ? 4 + (e1 >> 1) : (e1 >> 1));
-        a0 = __int_as_float(__float_as_int(a0) & __builtin_amdgcn_sbfe((int)w, b0, 1));
-        a1 = __int_as_float(__float_as_int(a1) & __builtin_amdgcn_sbfe((int)w, b1, 1));
-      }
-      v8[j] = a0; v8[4 + j] = a1;
-      pin(v8[j]); pin(v8[4 + j]);
-    } else if (!(j & 1)) {
-      const int p = (j - 4) >> 1;
-      unsigned hp = pack_bf16(v8[2 * p], v8[2 * p + 1]);
-      f0 = __uint_as_float(hp << 16);
-      f1 = __uint_as_float(hp & 0xffff0000u);
-      pin(hp); pin(f0); pin(f1);
-      out.h[p] = hp;
-    } else {
-      const int p = (j - 5) >> 1;
-      float r0 = v8[2 * p] - f0, r1 = v8[2 * p + 1] - f1;
-      pin(r0); pin(r1);
-      unsigned lp = pack_bf16(r0, r1);
-      pin(lp);
-      out.l[p] = lp;
+  float r0[4], r1[4];
+  __device__ __forceinline__ float gated(int e) const {
+    float a = cx.hv[(u >> 1) * 16 + 8 * (u & 1) + e];
+    if constexpr (GATED) {  // element e: bit e / 2 (e even) or 4 + e / 2 (e odd)
+      const int b = 8 * (u & 3) + ((e & 1) ? 4 + (e >> 1) : (e >> 1));
+      a = __int_as_float(__float_as_int(a) & __builtin_amdgcn_sbfe((int)gw[u >> 2], b, 1));
     }
+    return a;
   }
+  __device__ __forceinline__ void bias() {}
+  __device__ __forceinline__ void ra(int j) { v8[j] = gated(j); pin(v8[j]); }
+  __device__ __forceinline__ void rb(int j) { v8[4 + j] = gated(4 + j); pin(v8[4 + j]); }
+  __device__ __forceinline__ void relu(int j) { ra(j); rb(j); }
+  __device__ __forceinline__ void hi(int p) {
+    unsigned hp = pack_bf16(v8[2 * p], v8[2 * p + 1]);
+    f0 = __uint_as_float(hp << 16);
+    f1 = __uint_as_float(hp & 0xffff0000u);
+    pin(hp); pin(f0); pin(f1);
+    out.h[p] = hp;
+  }
+  __device__ __forceinline__ void rem(int p) {
+    r0[p] = v8[2 * p] - f0; r1[p] = v8[2 * p + 1] - f1;
+    pin(r0[p]); pin(r1[p]);
+  }
+  __device__ __forceinline__ void lo(int p) {
+    unsigned lp = pack_bf16(r0[p], r1[p]);
+    pin(lp);
+    out.l[p] = lp;
+  }
+  __device__ __forceinline__ void gates() {}
+  __device__ __forceinline__ void seq(int c) { unit_seq<true>(*this, c); }
+  template <bool EVEN> __device__ __forceinline__ void step8(int t) { unit_step8<EVEN, true>(*this, t); }
 };
 template <bool GATED>
 __device__ __forceinline__ UnitWorkB<GATED> unit_work_b(int u, Ctx& cx, Unit& out, const u32x4& gw) {
-  return UnitWorkB<GATED>{cx, out, u, gw, {}, 0.f, 0.f};
+  return UnitWorkB<GATED>{cx, out, u, gw, {}, 0.f, 0.f, {}, {}};
 }
 template <bool GATED>
 __device__ __forceinline__ void make_unit0_b(Ctx& cx, const u32x4& gw) {
   UnitWorkB<GATED> w = unit_work_b<GATED>(0, cx, cx.xn, gw);
 #pragma unroll
-  for (int j = 0; j < 12; ++j) w(j);
+  for (int j = 0; j < 4; ++j) w.relu(j);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) { w.hi(p); w.rem(p); }
+#pragma unroll
+  for (int p = 0; p < 4; ++p) w.lo(p);
 }
 // one product of the backward chain: NKS K-steps x NOB output blocks on the units of cx.hv (unit 0 is in cx.xn)
 template <int NOB, int NKS, bool GATED>

@@ -186,6 +186,7 @@ struct Ctx {
   unsigned dma_lds;   //   the LDS byte address of its wavefront's quarter of ring position 0 (uniform: an SGPR); set by ring_open_wait
   OpHalf opA;       // A operands of the next half slot, fetched one half slot ahead
   OpHalf opB;       // fp16x1: blocks 4-7 of the next slot (the whole slot is fetched one K-step ahead there)
+  f32x4 hb0, hb1;   // split modes: biases of unit 0 of the layer being finished, read by its last K-step (AccTake) for finish_layer
   Unit xn;          // B operands of the next hidden K-step
   float sig_part;   // this lane's partial dot product of the density head
   float sc;         // fp16x3: s_l of the finished layer in cx.hv (OFF_SCALE), wavefront-uniform -> lives in an SGPR: the re-packing fma
@@ -259,92 +260,192 @@ __device__ __forceinline__ unsigned gate_byte(const u32x4& h) {
 
 // Unit u of the finished layer lo held in cx.hv: registers 8m .. 8m+7 (m = u & 1) of output block u >> 1, i.e. neurons
 // 32 (u>>1) + 16 m + 4 half + {0..3, 8..11}  ->  + bias, relu, hi/lo split.
-// Cut into pieces of <= 6 VALU instructions; slot_step8/4 issue one piece behind each MFMA of a half slot, pinned with
-// sched_barriers, so the re-packing runs in the shadow of the matrix pipe.  Branch free on purpose: the pieces must stay
-// inside the MFMAs' basic block.
+// Cut into operations of 1..5 VALU instructions which the K-steps place in the gaps behind their MFMAs by the tables below
+// ("Per-gap schedule"), pinned with sched_barriers, so that the re-packing runs in the shadow of the matrix pipe.  Branch free on
+// purpose: the operations must stay inside the MFMAs' basic block.  The operations of a unit (split modes; element pairs p = 0..3):
+//   bias()          the two bias reads (LDS), >= 2 gaps in front of the first ra / rb / relu
+//   ra(j), rb(j)    element j / element 4 + j: bias, relu (fp16x3: input scale, clamp; rb also folds both into the running maximum);
+//   relu(j)         = both in one gap
+//   hi(p)           packed hi halves of elements 2p, 2p+1 (bf16 modes: + their fp32 values f0, f1 -- ONE pair of registers, so rem(p) comes
+//                   before hi(p + 1))
+//   rem(p), lo(p)   the two remainders v - hi, and their packed rounding.  The compiler pads one wait state between an inline-asm result and
+//                   its first reader (it assumes a partial-register write), so hi -> rem -> lo of a pair sit in three DIFFERENT gaps: the MFMA
+//                   between them is the wait state (in one gap they cost two s_nop, 8 cycles of issue, per pair)
+//   gates()         P = 4: the unit's gate byte from its four hi words
+// ---- Per-gap schedule ---------------------------------------------------------------------------------------------------------------
+// One wavefront per SIMD: an MFMA holds vector issue for 8 of its 32 cycles, so what sits in the gap behind it hides while its issue costs
+// stay within 24 cycles (VALU / s_nop 4 each, two ds_read_b128 <= 3, an LDS-DMA piece 31-60).  Every gap is therefore one of
+//   (a) one DMA piece and nothing else   (b) <= 2 ds_read_b128 + <= 3 VALU   (c) <= 5 VALU (an s_nop counts as one);
+// scripts/kstep_gaps.py prints what the compiler made of it (profiles/r8_kstep_gaps_*.log).  8-block K-step (slot_step8), gap k = behind
+// MFMA k of the half; B = operands of blocks 4-7 of this slot, A' = operands of blocks 0-3 of the next slot:
+//   gap        | odd K-step, fp16x3       | odd, bf16 modes    | even K-step, fp16x3      | even, bf16 modes
+//   first  0-3 | 2 B reads each           | the same           | 2 B reads each           | the same
+//   first  4   | bias                     | bias               | DMA piece 0              | the same
+//   first  5   | -                        | -                  | DMA piece 1              |
+//   first  6-9 | relu(0) .. relu(3)       | the same           | DMA pieces 2-5           |
+//   first  10  | hi(0..3)                 | hi(0)              | DMA piece 6              |
+//   first  11  | rem(0) rem(1)            | rem(0)             | DMA piece 7              |
+//   (odd: s_waitcnt vmcnt(0) lgkmcnt(0), s_barrier)
+//   second 0   | lo(0) lo(1) rem(2)       | hi(1)              | bias                     | bias
+//   second 1   | 2 A' reads, rem(3)       | 2 A', rem(1)       | 2 A' reads               | 2 A'
+//   second 2   | 2 A' reads, lo(2)        | 2 A', lo(0) lo(1)  | 2 A' reads, ra(0)        | the same
+//   second 3   | 2 A' reads, lo(3)        | 2 A'               | 2 A' reads, rb(0)        | the same
+//   second 4   | 2 A' reads               | 2 A'               | 2 A' reads, ra(1)        | the same
+//   second 5   | -                        | hi(2)              | rb(1) ra(2)              | the same
+//   second 6   | -                        | rem(2)             | rb(2) ra(3)              | the same
+//   second 7   | -                        | hi(3) lo(2)        | rb(3) hi(0)              | the same
+//   second 8   | -                        | rem(3)             | hi(1) hi(2) hi(3) rem(0) | rem(0) hi(1)
+//   second 9   | -                        | lo(3)              | lo(0) rem(1) rem(2)      | rem(1) hi(2)
+//   second 10  | -                        | (P = 4: gates)     | lo(1) lo(2) rem(3)       | rem(2) hi(3)
+//   second 11  | -                        | -                  | lo(3)                    | rem(3) lo(0..3) (P = 4: + gates)
+// The last B read has 8 MFMAs in front of the second half, the last A' read 7 in front of the next K-step; the A' reads of an odd K-step
+// stay behind its barrier.  The second half of an even K-step is the "compact sequence" seq(0..11) (unit_seq), which the views layer's
+// forms use as well.  Gaps that stay over the budget, and why:
+//   * bf16 modes, even K-steps, second half 7-11 (6 VALU each; P = 4: + the ~10 of the gate byte in the last): hi is four instructions
+//     there (no mixed-precision FMA reads the packed half: two conversions, a shift and a mask), and 44 VALU do not fit into the 45 issue
+//     slots behind the bias reads in whole operations.  P = 4, odd K-steps: the gate byte is one operation of ~10 in an otherwise empty gap.
+//   * the IPE K-steps of layer 0, DMA gaps 4 and 8: two v_readlane each -- the slot address comes back from an SGPR spilled to a VGPR lane.
+//   * a layer's last K-step (AccTake): nothing; the 17 accumulator reads that do not fit go to the head of finish_layer, where they run
+//     while the K-loop's last MFMAs drain.
+//   * views layer, even positions (slot_step4x2 / slot_step4): two units per 24 MFMAs (72 VALU, 20 ds_read) and 8 DMA pieces are more than
+//     24 gaps hold under (a)-(c) -- the DMA pieces share gaps 4..11 of the first half with seq(); five such K-steps per tile.
+template <bool BF, class W> __device__ __forceinline__ void unit_seq(W& w, int c);
+template <bool EVEN, bool BF, class W> __device__ __forceinline__ void unit_step8(W& w, int t);
 template <int P>
 struct UnitWork {
   Ctx& cx;
   Unit& out;
-  int u, lo;
+  int u, lo_;
   float floor_v;
   f32x4 b0, b1;
   float sc;  // fp16x3: s_lo (OFF_SCALE)
   float v8[8];
-  float f0, f1;
-  unsigned hpk;  // fp16x3: the packed hi pair of the current pair of values
-  // bias loads; issued ahead of the MFMAs that shadow the pieces (and ahead of the next A-operand fetch, so that the
-  // counted LDS wait in front of piece 0 covers these two reads only)
-  __device__ __forceinline__ void prefetch() {
+  float f0, f1;              // bf16 modes: fp32 values of the current pair's hi halves
+  float r0[4], r1[4];        // remainders of pair p, rem(p) -> lo(p)
+  __device__ __forceinline__ void bias() {
     const int ob = u >> 1, m = u & 1;
-    const float* bl = cx.sm_small + OFF_BIAS + lo * 256 + ob * 32 + 16 * m + 4 * cx.hi;
+    const float* bl = cx.sm_small + OFF_BIAS + lo_ * 256 + ob * 32 + 16 * m + 4 * cx.hi;
     b0 = *reinterpret_cast<const f32x4*>(bl); b1 = *reinterpret_cast<const f32x4*>(bl + 8);
   }
+  // element e = j or 4 + j of the unit: accumulator + bias (fp16x3: accumulator x next layer's input scale + bias, exact), relu
+  __device__ __forceinline__ float act(int e, float b) const {
+    const float h = cx.hv[(u >> 1) * 16 + 8 * (u & 1) + e];
+    if constexpr (is_bf16<P>()) return __builtin_fmaxf(h + b, floor_v);
+    else if constexpr (P == 1) return __builtin_amdgcn_fmed3f(h + b, floor_v, F16_MAX);  // fp16 operands: the same instruction count with
+                                     // v_med3_f32 -- an activation beyond the fp16 range saturates instead of turning into infinity
+    else return __builtin_amdgcn_fmed3f(__builtin_fmaf(h, sc, b), floor_v, F16_MAX);
+  }
+  // fp16x3: the running maximum of what is about to become fp16 is kept: a value AT the limit raises the saturation flag at the end of
+  // the kernel (status[0]) -- never a silent clamp
+  __device__ __forceinline__ void range(int j) {
+    if constexpr (P == 2) asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(cx.vmax) : "v"(v8[j]), "v"(v8[4 + j]));
+  }
+  __device__ __forceinline__ void ra(int j) { v8[j] = act(j, b0[j]); pin(v8[j]); }
+  __device__ __forceinline__ void rb(int j) { v8[4 + j] = act(4 + j, b1[j]); range(j); pin(v8[4 + j]); }
+  __device__ __forceinline__ void relu(int j) {  // (the maximum reads both values before either is pinned: no wait state)
+    v8[j] = act(j, b0[j]); v8[4 + j] = act(4 + j, b1[j]);
+    range(j);
+    pin(v8[j]); pin(v8[4 + j]);
+  }
+  __device__ __forceinline__ void hi(int p) {
+    unsigned hp;
+    if constexpr (is_bf16<P>()) {
+      hp = pack_bf16(v8[2 * p], v8[2 * p + 1]);
+      f0 = __uint_as_float(hp << 16);
+      f1 = __uint_as_float(hp & 0xffff0000u);
+    } else {
+      // fp16 parts: lo = v - hi comes straight from the PACKED hi register with v_fma_mix_f32 (an fp16 half as a source of an fp32 FMA:
+      // hi * -1 + v, exact) in rem(p) -- no fp32 copy of hi is made -- and needs 12 bits at most, rounded to nearest by
+      // v_cvt_pk_f16_f32: 22 significant bits (below 2^-14, where fp16 is subnormal, the absolute quantum 2^-24 bounds the error).
+      hp = pack_f16(v8[2 * p], v8[2 * p + 1]);  // (round to nearest: |lo| <= 2^-12 |v|; the remainder is exact for either rounding)
+    }
+    pin(hp);
+    if constexpr (is_bf16<P>()) { pin(f0); pin(f1); }
+    out.h[p] = hp;
+  }
+  __device__ __forceinline__ void rem(int p) {
+    if constexpr (is_bf16<P>()) {
+      r0[p] = v8[2 * p] - f0; r1[p] = v8[2 * p + 1] - f1;
+      pin(r0[p]); pin(r1[p]);
+    } else {  // (volatile instead of a pin behind them: a pin would read an inline-asm result in the same gap -- one s_nop each)
+      asm volatile("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0[p]) : "v"(out.h[p]), "v"(v8[2 * p]));
+      asm volatile("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1[p]) : "v"(out.h[p]), "v"(v8[2 * p + 1]));
+    }
+  }
+  __device__ __forceinline__ void lo(int p) {
+    unsigned lp = is_bf16<P>() ? pack_bf16(r0[p], r1[p]) : pack_f16(r0[p], r1[p]);
+    pin(lp);
+    out.l[p] = lp;
+  }
+  __device__ __forceinline__ void gates() {
+    if constexpr (has_gates<P>()) {  // all four hi words of the unit exist: value > 0 <=> its bf16 hi half is non-zero (after the ReLU nothing is negative)
+      const unsigned t = gate_byte(out.h);
+      cx.gbits[u >> 2] |= t << (8 * (u & 3));
+    }
+  }
+  __device__ __forceinline__ void seq(int c) { unit_seq<is_bf16<P>()>(*this, c); }
+  template <bool EVEN> __device__ __forceinline__ void step8(int t) { unit_step8<EVEN, is_bf16<P>()>(*this, t); }
+  // fp16x1 (slot_step8_one / slot_step4_one) and finish_layer: the unit in 12 pieces, in order
+  __device__ __forceinline__ void prefetch() { bias(); }
   __device__ __forceinline__ void operator()(int j) {
-    const int ob = u >> 1, m = u & 1;
-    if (j < 4) {               // elements j and 4 + j: bias, relu
-      if constexpr (is_bf16<P>()) {
-        v8[j] = __builtin_fmaxf(cx.hv[ob * 16 + 8 * m + j] + b0[j], floor_v);
-        v8[4 + j] = __builtin_fmaxf(cx.hv[ob * 16 + 8 * m + 4 + j] + b1[j], floor_v);
-      } else if constexpr (P == 1) {  // fp16 operands: the same instruction count with v_med3_f32 -- an activation beyond the fp16
-                                      // range saturates instead of turning into infinity (and the pass into NaNs)
-        v8[j] = __builtin_amdgcn_fmed3f(cx.hv[ob * 16 + 8 * m + j] + b0[j], floor_v, F16_MAX);
-        v8[4 + j] = __builtin_amdgcn_fmed3f(cx.hv[ob * 16 + 8 * m + 4 + j] + b1[j], floor_v, F16_MAX);
-      } else {  // fp16x3: the accumulator goes to the next layer's input scale inside the bias add (one v_fma instead of one v_add;
-                // exact), and the running maximum of what is about to become fp16 is kept: a value AT the limit raises the
-                // saturation flag at the end of the kernel (status[0]) -- never a silent clamp
-        v8[j] = __builtin_amdgcn_fmed3f(__builtin_fmaf(cx.hv[ob * 16 + 8 * m + j], sc, b0[j]), floor_v, F16_MAX);
-        v8[4 + j] = __builtin_amdgcn_fmed3f(__builtin_fmaf(cx.hv[ob * 16 + 8 * m + 4 + j], sc, b1[j]), floor_v, F16_MAX);
-        asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(cx.vmax) : "v"(v8[j]), "v"(v8[4 + j]));
-      }
-      pin(v8[j]); pin(v8[4 + j]);
-    } else if constexpr (P == 1) {  // pieces 4..7: pair p = j - 4 rounded to fp16 and packed (pieces 8..11: nothing)
+    if (j < 4) relu(j);
+    else if constexpr (P == 1) {  // pieces 4..7: pair p = j - 4 rounded to fp16 and packed (pieces 8..11: nothing)
       if (j < 8) {
         unsigned hp = pack_f16(v8[2 * (j - 4)], v8[2 * (j - 4) + 1]);
         pin(hp);
         out.h[j - 4] = hp;
       }
-    } else if (!(j & 1)) {     // pair p = (2p, 2p+1): hi halves and their fp32 values
-      const int p = (j - 4) >> 1;
-      unsigned hp;
-      if constexpr (is_bf16<P>()) {
-        hp = pack_bf16(v8[2 * p], v8[2 * p + 1]);
-        f0 = __uint_as_float(hp << 16);
-        f1 = __uint_as_float(hp & 0xffff0000u);
-      } else {
-        // fp16 parts: hi = the value truncated to 11 significant bits by v_cvt_pkrtz_f16_f32 (round toward zero, two values per
-        // instruction); lo = v - hi comes straight from the PACKED hi register with v_fma_mix_f32 (an fp16 half as a source of
-        // an fp32 FMA: hi * -1 + v, exact) in piece j+1 -- no fp32 copy of hi is made -- and needs 12 bits at most, rounded to
-        // nearest by v_cvt_pk_f16_f32: 22 significant bits like the round-to-nearest split (below 2^-14, where fp16 is
-        // subnormal, the absolute quantum 2^-24 bounds the error).
-        hp = pack_f16(v8[2 * p], v8[2 * p + 1]);  // (round to nearest: |lo| <= 2^-12 |v|; the remainder below is exact for either rounding)
-        hpk = hp;
-      }
-      pin(hp);
-      if constexpr (is_bf16<P>()) { pin(f0); pin(f1); }
-      out.h[p] = hp;
-    } else {                   // lo halves = rounded remainders
-      const int p = (j - 5) >> 1;
-      float r0, r1;
-      if constexpr (is_bf16<P>()) {
-        r0 = v8[2 * p] - f0; r1 = v8[2 * p + 1] - f1;
-      } else {
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hpk), "v"(v8[2 * p]));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hpk), "v"(v8[2 * p + 1]));
-      }
-      pin(r0); pin(r1);
-      unsigned lp = is_bf16<P>() ? pack_bf16(r0, r1) : pack_f16(r0, r1);
-      pin(lp);
-      out.l[p] = lp;
-      if constexpr (has_gates<P>()) {
-        if (j == 11) {  // all four hi words of the unit exist: value > 0 <=> its bf16 hi half is non-zero (after the ReLU nothing is negative)
-          const unsigned t = gate_byte(out.h);
-          cx.gbits[u >> 2] |= t << (8 * (u & 3));
-        }
-      }
+    } else if (!(j & 1)) hi((j - 4) >> 1);
+    else {
+      rem((j - 5) >> 1); lo((j - 5) >> 1);
+      if (j == 11) gates();
     }
   }
 };
+// The compact sequence: a whole unit in 12 consecutive gaps of which gaps 1..4 also carry two operand reads each (<= 3 VALU there).
+// BF: the bf16 forms (hi = 3 instructions, one f0 / f1 pair).
+template <bool BF, class W>
+__device__ __forceinline__ void unit_seq(W& w, int c) {
+  switch (c) {  // (a compile-time constant after unrolling)
+    case 0: w.bias(); break;
+    case 2: w.ra(0); break;
+    case 3: w.rb(0); break;
+    case 4: w.ra(1); break;
+    case 5: w.rb(1); w.ra(2); break;
+    case 6: w.rb(2); w.ra(3); break;
+    case 7: w.rb(3); w.hi(0); break;
+    case 8: if constexpr (BF) { w.rem(0); w.hi(1); } else { w.hi(1); w.hi(2); w.hi(3); w.rem(0); } break;
+    case 9: if constexpr (BF) { w.rem(1); w.hi(2); } else { w.lo(0); w.rem(1); w.rem(2); } break;
+    case 10: if constexpr (BF) { w.rem(2); w.hi(3); } else { w.lo(1); w.lo(2); w.rem(3); } break;
+    case 11: if constexpr (BF) { w.rem(3); w.lo(0); w.lo(1); w.lo(2); w.lo(3); w.gates(); } else { w.lo(3); } break;
+    default: break;
+  }
+}
+// Gap t of an 8-block K-step (0..11: first half, 12..23: second half): the table above
+template <bool EVEN, bool BF, class W>
+__device__ __forceinline__ void unit_step8(W& w, int t) {
+  if constexpr (EVEN) {
+    if (t >= 12) unit_seq<BF>(w, t - 12);
+  } else {
+    switch (t) {
+      case 4: w.bias(); break;
+      case 6: case 7: case 8: case 9: w.relu(t - 6); break;
+      case 10: if constexpr (BF) { w.hi(0); } else { w.hi(0); w.hi(1); w.hi(2); w.hi(3); } break;
+      case 11: if constexpr (BF) { w.rem(0); } else { w.rem(0); w.rem(1); } break;
+      case 12: if constexpr (BF) { w.hi(1); } else { w.lo(0); w.lo(1); w.rem(2); } break;
+      case 13: w.rem(BF ? 1 : 3); break;
+      case 14: if constexpr (BF) { w.lo(0); w.lo(1); } else { w.lo(2); } break;
+      case 15: if constexpr (!BF) { w.lo(3); } break;
+      case 17: if constexpr (BF) { w.hi(2); } break;
+      case 18: if constexpr (BF) { w.rem(2); } break;
+      case 19: if constexpr (BF) { w.hi(3); w.lo(2); } break;
+      case 20: if constexpr (BF) { w.rem(3); } break;
+      case 21: if constexpr (BF) { w.lo(3); } break;
+      case 22: if constexpr (BF) { w.gates(); } break;
+      default: break;
+    }
+  }
+}
 // fp16x3: the consumer of layer `slot`'s output has made all its units -- fold the running maximum into this thread's LDS cell
 // (ds_max_u32 without return: fire and forget; the values are >= 0, so the bit patterns order like the floats)
 template <int P>
@@ -361,33 +462,63 @@ __device__ __forceinline__ void fold_range(Ctx& cx, int slot) {
 struct NoWork {
   __device__ __forceinline__ void prefetch() {}
   __device__ __forceinline__ void operator()(int) {}
+  __device__ __forceinline__ void seq(int) {}
+  template <bool EVEN> __device__ __forceinline__ void step8(int) {}
 };
-// The work of a layer's LAST K-step (which re-packs nothing: all 16 units of the previous layer exist, cx.hv is dead): blocks 0..3 of the
-// layer being finished are final once that K-step's first half is through, so their 64 accumulator reads (v_accvgpr_read, finish_layer's
-// first half) go behind the MFMAs of its second half instead of in front of the next layer.
+// The work of the LAST K-step of layer l (which re-packs nothing: all 16 units of the previous layer exist, cx.hv is dead): blocks 0..3 of the
+// layer being finished are final once that K-step's first half is through, so their accumulator reads (v_accvgpr_read) go behind the MFMAs
+// of its second half instead of in front of the next layer.  Split modes: as many per gap as the per-gap schedule allows (take_n; gap 0 one less: the compiler pads the first read behind the MFMAs with an s_nop), 47 of the
+// 64 -- the rest opens finish_layer, where it runs while the last MFMAs drain -- and in second-half gap 10 the two bias reads of the next
+// layer's unit 0, which finish_layer would otherwise wait for with nothing to cover their LDS latency.
+constexpr int take_n(int s) { return s == 0 ? 4 : s == 1 ? 2 : s <= 4 ? 3 : s == 10 ? 2 : 5; }  // (gaps 1..4: + operand reads; 10: + bias reads and their address)
+constexpr int take_before(int s) {
+  int n = 0;
+  for (int k = 0; k < s; ++k) n += take_n(k);
+  return n;
+}
+constexpr int TAKE_HIDDEN = take_before(12);
+__device__ __forceinline__ const float* unit0_bias(const Ctx& cx, int l) { return cx.sm_small + OFF_BIAS + l * 256 + 4 * cx.hi; }
 template <int P>
 struct AccTake {
   const f32x16 (&acc)[8];
   Ctx& cx;
+  int l;
   __device__ __forceinline__ void prefetch() {}
-  __device__ __forceinline__ void operator()(int j) {
-    constexpr int per = is_split<P>() ? 6 : 8;  // 12 pieces of 6 (split modes) / 8 pieces of 8 (fp16x1)
+  __device__ __forceinline__ void operator()(int j) {  // fp16x1: 8 pieces of 8
 #pragma unroll
-    for (int k = 0; k < per; ++k) {
-      const int i = per * j + k;
+    for (int k = 0; k < 8; ++k) {
+      const int i = 8 * j + k;
       if (i < 64) cx.hv[i] = acc_read(acc[i >> 4][i & 15]);
+    }
+  }
+  __device__ __forceinline__ void seq(int) {}
+  template <bool EVEN> __device__ __forceinline__ void step8(int t) {
+    if (t < 12) return;
+    const int s = t - 12;
+#pragma unroll
+    for (int k = 0; k < take_n(s); ++k) {
+      const int i = take_before(s) + k;
+      cx.hv[i] = acc_read(acc[i >> 4][i & 15]);
+    }
+    if (s == 10) {
+      const float* bl = unit0_bias(cx, l);
+      cx.hb0 = *reinterpret_cast<const f32x4*>(bl); cx.hb1 = *reinterpret_cast<const f32x4*>(bl + 8);
     }
   }
 };
 template <int P>
 __device__ __forceinline__ UnitWork<P> unit_work(int u, int lo, Ctx& cx, Unit& out) {
-  return UnitWork<P>{cx, out, u, lo, lo < 8 ? 0.f : (!is_bf16<P>() ? -F16_MAX : -__builtin_inff()), {}, {}, cx.sc, {}, 0.f, 0.f, 0u};
+  return UnitWork<P>{cx, out, u, lo, lo < 8 ? 0.f : (!is_bf16<P>() ? -F16_MAX : -__builtin_inff()), {}, {}, cx.sc, {}, 0.f, 0.f, {}, {}};
 }
 
-// End of layer l: move the accumulators out of the AGPRs (the next layer starts from C = 0 in the same registers) and
-// make unit 0.  The only part of the re-packing that is not hidden behind MFMAs (128 + ~40 VALU instructions).
+// End of layer l: move the rest of the accumulators out of the AGPRs (the next layer starts from C = 0 in the same registers) and
+// make unit 0.  The only part of the re-packing that is not hidden behind MFMAs (~80 + ~40 VALU instructions).
 template <int P>
 __device__ __forceinline__ void finish_layer(const f32x16 (&acc)[8], int l, Ctx& cx) {
+  if constexpr (is_split<P>()) {
+#pragma unroll
+    for (int i = TAKE_HIDDEN; i < 64; ++i) cx.hv[i] = acc_read(acc[i >> 4][i & 15]);  // (what AccTake left of blocks 0..3)
+  }
 #pragma unroll
   for (int ob = 4; ob < 8; ++ob)  // (blocks 0..3: AccTake, in the shadow of the layer's last K-step)
 #pragma unroll
@@ -395,9 +526,27 @@ __device__ __forceinline__ void finish_layer(const f32x16 (&acc)[8], int l, Ctx&
   if constexpr (P == 2)
     cx.sc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, cx.sm_small[OFF_SCALE + l])));
   UnitWork<P> w = unit_work<P>(0, l, cx, cx.xn);
-  w.prefetch();
+  if constexpr (is_split<P>()) {  // (hi, rem and lo of a pair apart: see UnitWork)
+    w.b0 = cx.hb0; w.b1 = cx.hb1;  // (read by AccTake)
 #pragma unroll
-  for (int j = 0; j < 12; ++j) w(j);
+    for (int j = 0; j < 4; ++j) w.relu(j);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      w.hi(p);
+      if constexpr (is_bf16<P>()) w.rem(p);  // (one f0 / f1 pair)
+    }
+    if constexpr (!is_bf16<P>()) {
+#pragma unroll
+      for (int p = 0; p < 4; ++p) w.rem(p);
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) w.lo(p);
+    w.gates();
+  } else {
+    w.prefetch();
+#pragma unroll
+    for (int j = 0; j < 12; ++j) w(j);
+  }
 }
 
 // Density head on the finished layer 7: sigma partial = relu(h7) . w_alpha over this lane's 128 neurons.  Once per tile,
@@ -444,21 +593,6 @@ __device__ __forceinline__ void dump_tap(int lo, Ctx& cx) {
   }
 }
 
-// acc[4p .. 4p+3] (+)= W_half . (xh + xl)  as  w_hi*x_hi + w_hi*x_lo + w_lo*x_hi; FIRST starts from C = 0
-template <int P, bool FIRST, int NOB>
-__device__ __forceinline__ void mfma_head(f32x16 (&acc)[NOB], int p, const OpHalf& a, const bf16x8& xh) {
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int o = 0; o < 4; ++o) acc[4 * p + o] = mfma_p<P>(a.h[o], xh, FIRST ? zero : acc[4 * p + o]);
-}
-template <int P, int NOB>
-__device__ __forceinline__ void mfma_tail(f32x16 (&acc)[NOB], int p, const OpHalf& a, const bf16x8& xh, const bf16x8& xl) {
-#pragma unroll
-  for (int o = 0; o < 4; ++o) acc[4 * p + o] = mfma_p<P>(a.h[o], xl, acc[4 * p + o]);
-#pragma unroll
-  for (int o = 0; o < 4; ++o) acc[4 * p + o] = mfma_p<P>(a.l[o], xh, acc[4 * p + o]);
-}
-
 // fp16x1 form of the K-step: 8 MFMAs whose A operands (all 8 blocks of slot g) were fetched during the PREVIOUS K-step, so
 // no MFMA waits for LDS, and everything else a K-step has to issue -- the ring barrier of slot g+1 with the DMA of a later
 // slot, the 8 operand reads of slot g+1, the bias reads and the 8 pieces of re-packing work -- sits BETWEEN the MFMAs, a
@@ -495,65 +629,63 @@ __device__ __forceinline__ void slot_step8_one(f32x16 (&acc)[8], Ctx& cx, const 
   cx.g = g + 1;
 }
 
-// One K-step (slot cx.g) of an 8-block layer, software pipelined over half slots with a "consume first" order: every
-// batch of LDS reads is issued right AFTER four MFMAs that use the previously fetched operands:
-//   head(blocks 0-3, A) | fetch B = blocks 4-7 of slot g | tail(blocks 0-3, A) [even position: + the DMA pieces of slots g+2, g+3]
-//   odd position: ring barrier of slots g+1, g+2
-//   head(blocks 4-7, B) | fetch A = blocks 0-3 of slot g+1 | tail(blocks 4-7, B)
-// work(j), j = 0..11, is VALU work independent of this slot's second half (re-packing of a later K-step's B operands);
-// piece j is issued right behind the j-th MFMA of the second half.
+// One operand pair (hi, lo) of output block 4 p + o of a slot: the two ds_read_b128 a gap carries
+template <int P>
+__device__ __forceinline__ void load_pair(OpHalf& d, const float* slot, int lane, int p, int o) {
+  const u32x4* s4 = reinterpret_cast<const u32x4*>(slot) + lane;
+  d.h[o] = __builtin_bit_cast(bf16x8, s4[((4 * p + o) * 2 + 0) * 64]);
+  d.l[o] = __builtin_bit_cast(bf16x8, s4[((4 * p + o) * 2 + 1) * 64]);
+}
+// MFMA k = 0..11 of a half slot on four blocks: w_hi*x_hi (FIRST: from C = 0), w_hi*x_lo, w_lo*x_hi -- four blocks each
+template <int P, bool FIRST>
+__device__ __forceinline__ f32x16 mfma_k(int k, const OpHalf& a, const bf16x8& xh, const bf16x8& xl, const f32x16& c) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (k < 4) return mfma_p<P>(a.h[k], xh, FIRST ? zero : c);
+  if (k < 8) return mfma_p<P>(a.h[k & 3], xl, c);
+  return mfma_p<P>(a.l[k & 3], xh, c);
+}
+
+// One K-step (slot cx.g) of an 8-block layer, software pipelined over half slots: 12 MFMAs on blocks 0-3 with the A operands fetched
+// during the previous K-step, 12 on blocks 4-7 with the B operands fetched during the first half; odd position: the ring barrier of slots
+// g+1, g+2 between the halves.  What else a K-step issues -- 16 operand reads, the 8 DMA pieces of an even position's weight request and
+// `work`, VALU work independent of this slot (the re-packing of the next K-step's B operands, or AccTake) -- sits in the 24 gaps behind the
+// MFMAs by the per-gap schedule (table at UnitWork): operand reads two per gap, B in gaps 0-3 of the first half, the next slot's A in gaps
+// 1-4 of the second; the DMA pieces alone in gaps 4-11 of the first half; work.step8<EVEN>(t) says what the work does in gap t.
 // (EVEN: the K-step's position in the weight stream is even -- every layer holds an even number of K-steps, so the callers know)
+// (the next slot's operands are read unconditionally: past the last slot they are stale ring contents nobody uses)
 template <int P, bool FIRST, bool EVEN, class Work>
 __device__ __forceinline__ void slot_step8(f32x16 (&acc)[8], Ctx& cx, const bf16x8& xh, const bf16x8& xl, Work work) {
   if constexpr (P == 1) {
     slot_step8_one<FIRST, EVEN>(acc, cx, xh, work);
     return;
   }
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const int g = cx.g;
+  const OpHalf A = cx.opA;
   OpHalf B;
-  mfma_head<P, FIRST, 8>(acc, 0, cx.opA, xh);
-  __builtin_amdgcn_sched_barrier(0);
-  load_half<P>(B, cx.ring + (g & (NRING - 1)) * SLOT_FLOATS, cx.lane, 1);
-  work.prefetch();
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (EVEN) {  // mfma_tail with this K-step's weight request in its gaps
+  const float* cur = cx.ring + (g & (NRING - 1)) * SLOT_FLOATS;
+  const float* nxt = cx.ring + ((g + 1) & (NRING - 1)) * SLOT_FLOATS;
 #pragma unroll
-    for (int o = 0; o < 8; ++o) {
-      acc[o & 3] = mfma_p<P>(o < 4 ? cx.opA.h[o & 3] : cx.opA.l[o & 3], o < 4 ? xl : xh, acc[o & 3]);
-      ring_request<P>(cx, g, o);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else {
-    mfma_tail<P, 8>(acc, 0, cx.opA, xh, xl);
+  for (int k = 0; k < 12; ++k) {
+    acc[k & 3] = mfma_k<P, FIRST>(k, A, xh, xl, acc[k & 3]);
     __builtin_amdgcn_sched_barrier(0);
+    if (k < 4) load_pair<P>(B, cur, cx.lane, 1, k);
+    if constexpr (EVEN) {
+      if (k >= 4) ring_request<P>(cx, g, k - 4);
+    }
+    work.template step8<EVEN>(k);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if constexpr (!EVEN) {
     ring_acquire_two();
     __builtin_amdgcn_sched_barrier(0);  // (the second half's first MFMA stays behind the barrier)
   }
-  // from here to the end of the K-step: ONE basic block (the work pieces must not be separated from their MFMAs)
+  // from here to the end of the K-step: ONE basic block (the work must not be separated from its MFMAs)
 #pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    acc[4 + o] = mfma_p<P>(B.h[o], xh, FIRST ? zero : acc[4 + o]);
+  for (int k = 0; k < 12; ++k) {
+    acc[4 + (k & 3)] = mfma_k<P, FIRST>(k, B, xh, xl, acc[4 + (k & 3)]);
     __builtin_amdgcn_sched_barrier(0);
-    work(o);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  // the next slot's first operands, behind four MFMAs ("consume first"); unconditional: past the last slot they are
-  // stale ring contents nobody uses
-  load_half<P>(cx.opA, cx.ring + ((g + 1) & (NRING - 1)) * SLOT_FLOATS, cx.lane, 0);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    acc[4 + o] = mfma_p<P>(B.h[o], xl, acc[4 + o]);
-    __builtin_amdgcn_sched_barrier(0);
-    work(4 + o);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    acc[4 + o] = mfma_p<P>(B.l[o], xh, acc[4 + o]);
-    __builtin_amdgcn_sched_barrier(0);
-    work(8 + o);
+    if (k >= 1 && k <= 4) load_pair<P>(cx.opA, nxt, cx.lane, 0, k - 1);
+    work.template step8<EVEN>(12 + k);
     __builtin_amdgcn_sched_barrier(0);
   }
   cx.g = g + 1;
@@ -580,41 +712,27 @@ __device__ __forceinline__ void slot_step4_one(f32x16 (&acc)[4], Ctx& cx, const 
   cx.g = g + 1;
 }
 
+// Split modes: 12 MFMAs, the work as the compact sequence (seq(k) in gap k), the next slot's operands two per gap in gaps 1-4, an even
+// position's DMA pieces in gaps 4-11 next to the work (over the per-gap budget: see the table at UnitWork).
 template <int P, bool FIRST, bool EVEN, class Work>
 __device__ __forceinline__ void slot_step4(f32x16 (&acc)[4], Ctx& cx, const bf16x8& xh, const bf16x8& xl, Work work) {
   if constexpr (P == 1) {
     slot_step4_one<FIRST, EVEN>(acc, cx, xh, work);
     return;
   }
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const int g = cx.g;
   const OpHalf C = cx.opA;
-  work.prefetch();
+  const float* nxt = cx.ring + ((g + 1) & (NRING - 1)) * SLOT_FLOATS;
   if constexpr (!EVEN) ring_acquire_two();
-  // (an even position's weight request rides in gaps 4..11, behind the operand fetch)
 #pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    acc[o] = mfma_p<P>(C.h[o], xh, FIRST ? zero : acc[o]);
+  for (int k = 0; k < 12; ++k) {
+    acc[k & 3] = mfma_k<P, FIRST>(k, C, xh, xl, acc[k & 3]);
     __builtin_amdgcn_sched_barrier(0);
-    work(o);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  load_half<P>(cx.opA, cx.ring + ((g + 1) & (NRING - 1)) * SLOT_FLOATS, cx.lane, 0);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    acc[o] = mfma_p<P>(C.h[o], xl, acc[o]);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (EVEN) ring_request<P>(cx, g, o);
-    work(4 + o);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    acc[o] = mfma_p<P>(C.l[o], xh, acc[o]);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (EVEN) ring_request<P>(cx, g, 4 + o);
-    work(8 + o);
+    if (k >= 1 && k <= 4) load_pair<P>(cx.opA, nxt, cx.lane, 0, k - 1);
+    if constexpr (EVEN) {
+      if (k >= 4) ring_request<P>(cx, g, k - 4);
+    }
+    work.seq(k);
     __builtin_amdgcn_sched_barrier(0);
   }
   cx.g = g + 1;
@@ -625,36 +743,26 @@ __device__ __forceinline__ void slot_step4(f32x16 (&acc)[4], Ctx& cx, const bf16
 // FULL slot and one counted wait per 24 MFMAs instead of per 12 (a single 4-block K-step runs at 67 cycles per MFMA against the 8-block
 // layers' 46: its fixed cost does not hide behind 12 MFMAs).  w0 makes the unit the SECOND half consumes (u1, ready behind this slot's
 // 12th MFMA), w1 the first unit of the next slot (cx.xn).
+// Each half is a compact sequence, seq(k) in gap k, with its operand reads (first half: this slot's second K-step, second half: the next
+// slot) two per gap in gaps 1-4; u1 is complete in gap 11 of the first half.  Even positions: the DMA pieces in gaps 4-11 of the first half,
+// next to w0 (over the per-gap budget: see the table at UnitWork; they stay in gaps that carry VALU work only but for the first, where a
+// piece was measured cheapest).
 template <int P, bool FIRST, bool EVEN, class W0, class W1>
 __device__ __forceinline__ void slot_step4x2(f32x16 (&av)[4], Ctx& cx, const bf16x8& x0h, const bf16x8& x0l, Unit& u1, W0 w0, W1 w1) {
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const int g = cx.g;
   const OpHalf A = cx.opA;
   OpHalf B;
-  w0.prefetch();
+  const float* cur = cx.ring + (g & (NRING - 1)) * SLOT_FLOATS;
+  const float* nxt = cx.ring + ((g + 1) & (NRING - 1)) * SLOT_FLOATS;
 #pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    av[o] = mfma_p<P>(A.h[o], x0h, FIRST ? zero : av[o]);
+  for (int k = 0; k < 12; ++k) {
+    av[k & 3] = mfma_k<P, FIRST>(k, A, x0h, x0l, av[k & 3]);
     __builtin_amdgcn_sched_barrier(0);
-    w0(o);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  load_half<P>(B, cx.ring + (g & (NRING - 1)) * SLOT_FLOATS, cx.lane, 1);  // the second K-step's operands, behind four MFMAs
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    av[o] = mfma_p<P>(A.h[o], x0l, av[o]);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (EVEN) ring_request<P>(cx, g, o);
-    w0(4 + o);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    av[o] = mfma_p<P>(A.l[o], x0h, av[o]);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (EVEN) ring_request<P>(cx, g, 4 + o);
-    w0(8 + o);
+    if (k >= 1 && k <= 4) load_pair<P>(B, cur, cx.lane, 1, k - 1);  // the second K-step's operands
+    if constexpr (EVEN) {
+      if (k >= 4) ring_request<P>(cx, g, k - 4);
+    }
+    w0.seq(k);
     __builtin_amdgcn_sched_barrier(0);
   }
   // (all reads of this slot are issued: the barrier below frees its ring position for the K-step after next)
@@ -663,28 +771,12 @@ __device__ __forceinline__ void slot_step4x2(f32x16 (&av)[4], Ctx& cx, const bf1
     __builtin_amdgcn_sched_barrier(0);
   }
   const bf16x8 x1h = __builtin_bit_cast(bf16x8, u1.h), x1l = __builtin_bit_cast(bf16x8, u1.l);
-  w1.prefetch();
 #pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    av[o] = mfma_p<P>(B.h[o], x1h, av[o]);
+  for (int k = 0; k < 12; ++k) {
+    av[k & 3] = mfma_k<P, false>(k, B, x1h, x1l, av[k & 3]);
     __builtin_amdgcn_sched_barrier(0);
-    w1(o);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  load_half<P>(cx.opA, cx.ring + ((g + 1) & (NRING - 1)) * SLOT_FLOATS, cx.lane, 0);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    av[o] = mfma_p<P>(B.h[o], x1l, av[o]);
-    __builtin_amdgcn_sched_barrier(0);
-    w1(4 + o);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    av[o] = mfma_p<P>(B.l[o], x1h, av[o]);
-    __builtin_amdgcn_sched_barrier(0);
-    w1(8 + o);
+    if (k >= 1 && k <= 4) load_pair<P>(cx.opA, nxt, cx.lane, 0, k - 1);
+    w1.seq(k);
     __builtin_amdgcn_sched_barrier(0);
   }
   cx.g = g + 1;
@@ -739,8 +831,9 @@ __device__ __forceinline__ void views_extras(f32x16 (&av)[4], Ctx& cx, const bf1
 }
 
 // IPE K-steps of layers 0 (FIRST: they open the layer) and 5 (skip connection, after the hidden K-steps)
+// (l: the layer they close, 0 or 5)
 template <int P, bool FIRST>
-__device__ __forceinline__ void ipe_steps(f32x16 (&acc)[8], Ctx& cx, const float* ipe_src) {
+__device__ __forceinline__ void ipe_steps(f32x16 (&acc)[8], Ctx& cx, const float* ipe_src, int l = FIRST ? 0 : 5) {
   auto operand = [&](int m, bf16x8& ph, bf16x8& pl) {
     // (fp16x1: one operand per K-step, at [m][64 lanes][4 floats] of the same LDS region)
     ph = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ipe_src + (is_split<P>() ? (m * 2 + 0) : m) * 256));
@@ -754,7 +847,7 @@ __device__ __forceinline__ void ipe_steps(f32x16 (&acc)[8], Ctx& cx, const float
     if (m == 0) slot_step8<P, FIRST, true>(acc, cx, ph, pl, NoWork{});
     else slot_step8<P, false, true>(acc, cx, ph, pl, NoWork{});
     operand(m + 1, ph, pl);
-    if (m + 2 == XS) slot_step8<P, false, false>(acc, cx, ph, pl, AccTake<P>{acc, cx});  // (the IPE steps close layers 0 and 5)
+    if (m + 2 == XS) slot_step8<P, false, false>(acc, cx, ph, pl, AccTake<P>{acc, cx, l});  // (the IPE steps close layers 0 and 5)
     else slot_step8<P, false, false>(acc, cx, ph, pl, NoWork{});
   }
 }
@@ -790,7 +883,7 @@ __device__ __forceinline__ void layer_pass(f32x16 (&acc)[8], int l, Ctx& cx, con
       if (ks + 2 < HS) slot_step8<P, false, false>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 2, l - 1, cx, cx.xn));
       // (every layer, no branch in the MFMA stream: in layer 5 the skip connection's IPE steps still follow, what is taken here is
       //  overwritten by their own AccTake)
-      else slot_step8<P, false, false>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), AccTake<P>{acc, cx});
+      else slot_step8<P, false, false>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), AccTake<P>{acc, cx, l});
     }
   }
   fold_range<P>(cx, l - 1);  // (all 16 units of layer l-1's output exist now)
