@@ -484,6 +484,23 @@ int nm_dual_softmax_match_fused(const float* im, const float* pt, int P, int M, 
                                 const uint8_t* pt_mask, float threshold, int mutual, int64_t* out_i, int64_t* out_j,
                                 float* out_conf, int* counts, void* workspace, size_t workspace_bytes, nmStream_t stream);
 
+/* Cosine mutual nearest neighbours of two descriptor sets (csrc/match_fused.hip): the reference's mutual_nn_matching
+ * (nerfmatch/utils/geometry.py:160-180), which the two-view pose metrics of a NeRF validation step call on the rendered point features.
+ *   desc1 [N1,C], desc2 [N2,C] fp32; d = desc / (|desc| + eps) per row, sim = d1 d2^T (split-bf16 matrix cores, only in registers).
+ *   nn12[i] = argmax_j sim[i,j], nn21[j] = argmax_i sim[i,j]; where the kernel's own values are exactly equal the LOWEST index wins.
+ *   Row i is a match iff nn21[nn12[i]] == i, with score sim[i, nn12[i]]; use_threshold != 0 keeps only score > threshold (strictly).
+ *   An all-zero row normalises to zero: its similarities are exactly 0 and take part like any other value.  Non-finite inputs are
+ *   outside the contract (the indices stay inside the arrays).
+ * Outputs (device): matches [N1,2] int64 (i, nn12[i]) in ascending i and scores [N1] fp32 -- valid prefix: count[0] entries, the rest is
+ *   not written; count [1] int32; nn12 [N1] / nn21 [N2] int32, or NULL.  Deterministic: the same inputs give the same bytes.
+ * C in {64,128,256,512}, 1 <= N1, N2 <= 2^20 -- otherwise NM_ERR_UNSUPPORTED; N1 or N2 < 1, a negative / non-finite eps or a NaN
+ * threshold: NM_ERR_ARG.  workspace: nm_feature_mutual_nn_workspace_bytes(N1,N2,C) bytes (0 for an unsupported shape), else
+ * NM_ERR_WORKSPACE.  Every check is made before anything is enqueued. */
+size_t nm_feature_mutual_nn_workspace_bytes(int N1, int N2, int C);
+int nm_feature_mutual_nn(const float* desc1, const float* desc2, int N1, int N2, int C, float eps, float threshold, int use_threshold,
+                         int64_t* matches, float* scores, int* count, int* nn12, int* nn21, void* workspace, size_t workspace_bytes,
+                         nmStream_t stream);
+
 /* Dual-softmax matching + (mutual) nearest-neighbour selection for ONE image/point-set pair.
  * Replaces coarse_matching (nerfmatch/nerfmatch_c2f_trainer.py:289-300) + extract_mutual_matches inference branch
  * (nerfmatch/modules/extract_matches.py:21-36).

@@ -109,6 +109,8 @@ SIGNATURES = {
     "nm_dual_softmax_match": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "nm_match_fused_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "nm_dual_softmax_match_fused": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, f32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "nm_feature_mutual_nn_workspace_bytes": (sz, [i32, i32, i32]),
+    "nm_feature_mutual_nn": (i32, [vp, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "nm_fine_windows": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
     "nm_fine_windows_batch": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp]),
     "nm_assemble_matches": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp]),

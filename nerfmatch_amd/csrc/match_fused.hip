@@ -19,6 +19,8 @@
 //   compact    ordered compaction per pair
 // Every conf value comes out of the same inlined expression on bit-identical accumulators (the tile code is one function), so
 // the equality tests compare equal bits exactly like the reference's `conf == conf.max()`.
+// The same packer and tile K-loop also serve nm_feature_mutual_nn at the end of this file: cosine mutual nearest neighbours of two
+// descriptor sets (the reference's mutual_nn_matching) in ONE tile pass.
 #include "bf16x3.h"
 #include <limits.h>
 
@@ -159,15 +161,16 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_read(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
 }
-template <bool MAX>
+template <int MAX>  // 0: sum, 1: maximum of values >= +0 (on the bit patterns), 2: maximum of any finite values / -inf (v_max_f32)
 __device__ __forceinline__ float red2(float x, float y) {
   // the maximum is taken on the bit patterns: the values are confidences >= +0 (or NaN in columns outside the matrix, which are
   // dropped whole), for which the integer order is the float order, and v_max_i32 folds into the DPP instruction where v_max_f32 on
   // a value of unknown origin would first be canonicalised (one more instruction per value)
+  if (MAX == 2) return __builtin_fmaxf(x, y);
   if (MAX) return __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), __builtin_bit_cast(int, y)));
   return x + y;
 }
-template <bool MAX, int CTRL, int NOUT>
+template <int MAX, int CTRL, int NOUT>
 __device__ __forceinline__ void halve(const float* in, float* out, bool bit) {
 #pragma unroll
   for (int j = 0; j < NOUT; ++j) {
@@ -176,7 +179,7 @@ __device__ __forceinline__ void halve(const float* in, float* out, bool bit) {
     out[j] = red2<MAX>(keep, dpp_read<CTRL>(send));
   }
 }
-template <bool MAX>
+template <int MAX>
 __device__ __forceinline__ void column_reduce(const f32x16 (&acc)[4], int lane, float (&out)[2]) {
   float v[64], w1[32], w2[16], w3[8], w4[4];
 #pragma unroll
@@ -460,7 +463,8 @@ __global__ void __launch_bounds__(256, 3) match_tie_kernel(FArgs a) {
   if (mine && first != INT_MAX) atomicMin(a.sel_j + (size_t)p * a.M + m, first);
 }
 
-// Rows -> ready-made MFMA operands: f / (|f| + 1e-6) (the summation order of match.hip's l2norm_kernel: one wavefront per row,
+// Rows -> ready-made MFMA operands: f / (|f| + eps), eps = 1e-6 for the matcher and the caller's for nm_feature_mutual_nn (the
+// summation order of match.hip's l2norm_kernel: one wavefront per row,
 // lane l sums channels l, l + 64, ..., then the xor tree), split into bf16 hi / lo, written as [K-step][hi, lo][lane' = (row & 31) +
 // 32 half][8 values k = 16 ks + 8 half + i].  One workgroup per group of 32 rows, so that every 1 KiB (K-step, hi / lo) piece
 // leaves as ONE coalesced store of 64 x 16 bytes (a first version, one wavefront per row writing 2-byte elements, ran at a third
@@ -469,7 +473,7 @@ __global__ void __launch_bounds__(256, 3) match_tie_kernel(FArgs a) {
 //   point side (POINTS = true):  slot (chunk = group / 4, ks) of 8 KiB, piece ((group & 3) 2 + hl) KiB          -- A-operand slots
 // grid (groups, P), C = 64 PER
 template <int PER, bool POINTS>
-__device__ __forceinline__ void norm_pack32_body(const float* __restrict__ x, int rows, int groups, int nks, char* __restrict__ blob, int g, float* s_inv) {
+__device__ __forceinline__ void norm_pack32_body(const float* __restrict__ x, int rows, int groups, int nks, char* __restrict__ blob, int g, float* s_inv, float eps) {
   const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* xg = x + ((size_t)p * rows + (size_t)g * 32) * 64 * PER;
 #pragma unroll 1
@@ -485,7 +489,7 @@ __device__ __forceinline__ void norm_pack32_body(const float* __restrict__ x, in
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    if (lane == 0) s_inv[r] = sqrtf(q) + 1e-6f;
+    if (lane == 0) s_inv[r] = sqrtf(q) + eps;
   }
   __syncthreads();
   const int r = lane & 31, half = lane >> 5;
@@ -521,20 +525,22 @@ __device__ __forceinline__ void norm_pack32_body(const float* __restrict__ x, in
 // [gi, gi + gp) the point rows
 template <int PER>
 __global__ void __launch_bounds__(256) norm_pack32_kernel(const float* __restrict__ im, int M, int gi, const float* __restrict__ pt, int N, int gp, int nks,
-                                                          char* __restrict__ imb, char* __restrict__ blob) {
+                                                          char* __restrict__ imb, char* __restrict__ blob, float eps) {
   __shared__ float s_inv[32];
-  if ((int)blockIdx.x < gi) norm_pack32_body<PER, false>(im, M, gi, nks, imb, blockIdx.x, s_inv);
-  else norm_pack32_body<PER, true>(pt, N, gp, nks, blob, blockIdx.x - gi, s_inv);
+  if ((int)blockIdx.x < gi) norm_pack32_body<PER, false>(im, M, gi, nks, imb, blockIdx.x, s_inv, eps);
+  else norm_pack32_body<PER, true>(pt, N, gp, nks, blob, blockIdx.x - gi, s_inv, eps);
 }
 
-// ordered compaction, one workgroup per pair (cf. compact_kernel in match.hip)
+// ordered compaction, one workgroup per pair (cf. compact_kernel in match.hip).  PAIRS (nm_feature_mutual_nn): out_i is one (K, 2) list of
+// (i, j), out_j unused, and the slots behind the count are left alone
+template <bool PAIRS>
 __global__ void __launch_bounds__(1024) match_compact_kernel(const int* __restrict__ sel_j, const float* __restrict__ sel_v, int M,
                                                               int64_t* __restrict__ out_i, int64_t* __restrict__ out_j,
                                                               float* __restrict__ out_conf, int* __restrict__ count) {
   __shared__ int s_wave[16];
   __shared__ int s_base;
   const int p = blockIdx.x;
-  sel_j += (size_t)p * M; sel_v += (size_t)p * M; out_i += (size_t)p * M; out_j += (size_t)p * M; out_conf += (size_t)p * M;
+  sel_j += (size_t)p * M; sel_v += (size_t)p * M; out_i += (size_t)p * M * (PAIRS ? 2 : 1); out_j += (size_t)p * M; out_conf += (size_t)p * M;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) s_base = 0;
   __syncthreads();
@@ -553,8 +559,13 @@ __global__ void __launch_bounds__(1024) match_compact_kernel(const int* __restri
     const int base = s_base;
     if (has) {
       const int o = base + woff + prefix;
-      out_i[o] = i;
-      out_j[o] = sj;
+      if constexpr (PAIRS) {
+        out_i[2 * (size_t)o] = i;
+        out_i[2 * (size_t)o + 1] = sj;
+      } else {
+        out_i[o] = i;
+        out_j[o] = sj;
+      }
       out_conf[o] = sel_v[i];
     }
     __syncthreads();
@@ -563,7 +574,8 @@ __global__ void __launch_bounds__(1024) match_compact_kernel(const int* __restri
   }
   // the slots behind the count: index 0 / confidence 0 (round 5: the single-pair path's speculative fine stage reads the first `cap` slots as
   // indices before the count is known -- this used to be a fill launch of the caller's)
-  for (int i = s_base + tid; i < M; i += 1024) { out_i[i] = 0; out_j[i] = 0; out_conf[i] = 0.f; }
+  if constexpr (!PAIRS)
+    for (int i = s_base + tid; i < M; i += 1024) { out_i[i] = 0; out_j[i] = 0; out_conf[i] = 0.f; }
   if (tid == 0) count[p] = s_base;
 }
 
@@ -602,7 +614,206 @@ FWork carve(void* base, int P, int M, int N, int C) {
   return w;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Cosine mutual nearest neighbours of two descriptor sets (nm_feature_mutual_nn; the reference's mutual_nn_matching,
+// nerfmatch/utils/geometry.py:160-180): sim = d1 d2^T of the rows normalised as f / (|f| + eps), nn12 = row argmax, nn21 = column
+// argmax, row i matches iff nn21[nn12[i]] == i.  ONE pass of the tiles above (desc1 rows on the image side, desc2 rows on the point
+// side), the similarity only in accumulator registers:
+//   norm_pack32  both sides -> MFMA operands, with the caller's eps
+//   nn_tile      sim_tile; per row of the tile its maximum + first column, per column its maximum + first row -> partial arrays
+//   nn_select    per row: the partial results of its tiles_n tiles in ascending order (strict >: the first tile holding the maximum
+//                wins, so the lowest column), the same for the column it points to, the mutual test on the indices, the threshold
+//   compact      match_compact_kernel<true>: ordered compaction into (K, 2) / (K,)
+// What differs from the matcher's epilogue: the values have any sign, so every maximum is a float maximum from -inf; entries outside
+// the matrix (zero-padded operands: sim = 0, above every negative true value) are set to -inf BEFORE either argmax; and "first index"
+// is kept at every level -- inside a lane (descending overwrite), across the two lane halves and the tiles (smaller index on equality /
+// strict >), and in the column direction, where the 32 rows of a column sit in 32 lanes of 4 wavefronts, by a minimum over the rows
+// whose value equals the tile's column maximum (LDS atomicMin: order-independent, hence deterministic).
+struct NArgs {
+  float* rbest;   // [tiles_n][N1] per-tile row maximum
+  int* ridx;      // [tiles_n][N1] its first column (global)
+  float* cbest;   // [tiles_m][N2] per-tile column maximum
+  int* cidx;      // [tiles_m][N2] its first row (global)
+  int* sel_j;     // [N1] matched column or -1
+  float* sel_v;   // [N1] row maximum
+  int* nn12;      // [N1] or NULL
+  int* nn21;      // [N2] or NULL
+  float thr;
+  int use_thr;
+};
+
+__global__ void __launch_bounds__(256, 4) nn_tile_kernel(FArgs a, NArgs n) {
+  __shared__ __attribute__((aligned(16))) float ring[F_RING * F_SLOT_FLOATS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hi = lane >> 5;
+  const int rpx = (a.tiles_m + 7) >> 3, j = blockIdx.x >> 3;  // the XCD-aware mapping of match_tile_kernel
+  const int chunk = j / rpx, row_tile = (blockIdx.x & 7) * rpx + j % rpx;
+  if (row_tile >= a.tiles_m) return;
+  f32x16 acc[4];
+  sim_tile(a, 0, row_tile, chunk, ring, acc);
+  const int m = row_tile * FT + wave * 32 + r;
+  const float NINF = -__builtin_inff();
+  // ragged tiles only (workgroup-uniform): columns >= N2 and rows >= N1 leave both argmaxes
+  if ((chunk + 1) * FT > a.N) {
+#pragma unroll
+    for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[ob][i] = chunk * FT + 32 * ob + nrow(i, hi) < a.N ? acc[ob][i] : NINF;
+  }
+  if ((row_tile + 1) * FT > a.M) {
+#pragma unroll
+    for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[ob][i] = m < a.M ? acc[ob][i] : NINF;
+  }
+  // rows: maximum of the lane's 64 values, its first column (ascending (ob, i) is ascending column: descending overwrite), then the
+  // other half's -- its columns interleave with this half's in groups of four, so on equality the smaller index
+  float best = NINF;
+#pragma unroll
+  for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) best = __builtin_fmaxf(best, acc[ob][i]);
+  int bl = 0;
+#pragma unroll
+  for (int ob = 3; ob >= 0; --ob)
+#pragma unroll
+    for (int i = 15; i >= 0; --i) bl = acc[ob][i] == best ? 16 * ob + i : bl;
+  int bidx = chunk * FT + 32 * (bl >> 4) + nrow(bl & 15, hi);
+  {
+    const float ov = nm_shfl_xor32(best);
+    const int oi = __shfl_xor(bidx, 32, 64);
+    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+  }
+  if (hi == 0 && m < a.M) {
+    n.rbest[(size_t)chunk * a.M + m] = best;
+    n.ridx[(size_t)chunk * a.M + m] = bidx;
+  }
+  // columns: float maximum over the 32 rows of each half (column_reduce), over the 4 wavefronts in LDS, then the first row
+  float* scr = ring;  // [4][FT] per-wavefront maxima | [FT] the tile's column maxima | [FT] first rows (int)
+  int* first = reinterpret_cast<int*>(scr + 5 * FT);
+  {
+    float cm[2];
+    column_reduce<2>(acc, lane, cm);
+    scr[wave * FT + reduced_column(lane, 0)] = cm[0];
+    scr[wave * FT + reduced_column(lane, 1)] = cm[1];
+  }
+  __syncthreads();
+  if (tid < FT) {
+    scr[4 * FT + tid] = __builtin_fmaxf(__builtin_fmaxf(scr[tid], scr[FT + tid]), __builtin_fmaxf(scr[2 * FT + tid], scr[3 * FT + tid]));
+    first[tid] = FT - 1;  // (never left standing for a column of the matrix: some row of the tile holds its maximum)
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4 cmx = *reinterpret_cast<const f32x4*>(scr + 4 * FT + 32 * ob + 8 * q + 4 * hi);
+#pragma unroll
+      for (int e4 = 0; e4 < 4; ++e4)
+        if (acc[ob][4 * q + e4] == cmx[e4]) atomicMin(first + 32 * ob + 8 * q + 4 * hi + e4, wave * 32 + r);
+    }
+  __syncthreads();
+  if (tid < FT) {
+    const int col = chunk * FT + tid;
+    if (col < a.N) {
+      n.cbest[(size_t)row_tile * a.N + col] = scr[4 * FT + tid];
+      n.cidx[(size_t)row_tile * a.N + col] = row_tile * FT + first[tid];
+    }
+  }
+}
+
+// maximum and first index of entry `i` over `tiles` partial arrays of stride `stride`, in ascending tile order
+__device__ __forceinline__ int nn_combine(const float* best, const int* idx, int tiles, int stride, int i, int limit, float& v) {
+  v = -__builtin_inff();
+  int k = 0;
+  for (int t = 0; t < tiles; ++t) {
+    const float b = best[(size_t)t * stride + i];
+    if (b > v) { v = b; k = idx[(size_t)t * stride + i]; }
+  }
+  return min(max(k, 0), limit - 1);  // (inside the arrays whatever the inputs were: non-finite descriptors are outside the contract)
+}
+
+// grid (ceil(max(N1, N2) / 256), 2): y = 0 rows (selection), y = 1 columns (only nn21, when it is wanted)
+__global__ void __launch_bounds__(256) nn_select_kernel(FArgs a, NArgs n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  float v, cv;
+  if (blockIdx.y == 0) {
+    if (i >= a.M) return;
+    const int jj = nn_combine(n.rbest, n.ridx, a.tiles_n, a.M, i, a.N, v);
+    const int back = nn_combine(n.cbest, n.cidx, a.tiles_m, a.N, jj, a.M, cv);
+    const bool keep = back == i && (!n.use_thr || v > n.thr);
+    n.sel_j[i] = keep ? jj : -1;
+    n.sel_v[i] = v;
+    if (n.nn12) n.nn12[i] = jj;
+  } else {
+    if (i >= a.N || !n.nn21) return;
+    n.nn21[i] = nn_combine(n.cbest, n.cidx, a.tiles_m, a.N, i, a.M, cv);
+  }
+}
+
+struct NWork {
+  char *imb, *blob;
+  float *rbest, *cbest, *sel_v;
+  int *ridx, *cidx, *sel_j;
+  size_t bytes;
+};
+NWork nn_carve(void* base, int M, int N, int C) {
+  NWork w{};
+  size_t off = 0;
+  auto take = [&](size_t n) {
+    void* q = base ? (char*)base + off : nullptr;
+    off += al256(n);
+    return q;
+  };
+  const size_t tm = ((size_t)M + FT - 1) / FT, tn = ((size_t)N + FT - 1) / FT, nks = C / 16;
+  w.imb = (char*)take((((size_t)M + 31) / 32) * nks * 2048);
+  w.blob = (char*)take(tn * nks * F_SLOT_BYTES);
+  w.rbest = (float*)take(tn * M * 4);
+  w.ridx = (int*)take(tn * M * 4);
+  w.cbest = (float*)take(tm * N * 4);
+  w.cidx = (int*)take(tm * N * 4);
+  w.sel_j = (int*)take((size_t)M * 4);
+  w.sel_v = (float*)take((size_t)M * 4);
+  w.bytes = off;
+  return w;
+}
+constexpr int NN_MAX_ROWS = 1 << 20;  // per side: the tile grid (8 ceil(tiles_m / 8) tiles_n workgroups) stays far inside 2^31
+
 }  // namespace
+
+extern "C" size_t nm_feature_mutual_nn_workspace_bytes(int N1, int N2, int C) {
+  if (N1 <= 0 || N2 <= 0 || N1 > NN_MAX_ROWS || N2 > NN_MAX_ROWS || (C != 64 && C != 128 && C != 256 && C != 512)) return 0;
+  return nn_carve(nullptr, N1, N2, C).bytes;
+}
+
+extern "C" int nm_feature_mutual_nn(const float* desc1, const float* desc2, int N1, int N2, int C, float eps, float threshold, int use_threshold,
+                                    int64_t* matches, float* scores, int* count, int* nn12, int* nn21, void* workspace, size_t workspace_bytes,
+                                    nmStream_t stream) {
+  NM_CHECK_ARG(desc1 && desc2 && matches && scores && count && workspace && N1 > 0 && N2 > 0 && eps >= 0.f && eps < __builtin_inff());
+  if ((C != 64 && C != 128 && C != 256 && C != 512) || N1 > NN_MAX_ROWS || N2 > NN_MAX_ROWS) return NM_ERR_UNSUPPORTED;
+  if (use_threshold && !(threshold == threshold)) return NM_ERR_ARG;
+  NWork w = nn_carve(workspace, N1, N2, C);
+  if (workspace_bytes < w.bytes) return NM_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  FArgs a{};
+  a.imb = w.imb; a.blob = w.blob;
+  a.M = N1; a.N = N2; a.C = C; a.nks = C / 16; a.tiles_m = (N1 + FT - 1) / FT; a.tiles_n = (N2 + FT - 1) / FT;
+  NArgs n{};
+  n.rbest = w.rbest; n.ridx = w.ridx; n.cbest = w.cbest; n.cidx = w.cidx; n.sel_j = w.sel_j; n.sel_v = w.sel_v;
+  n.nn12 = nn12; n.nn21 = nn21; n.thr = threshold; n.use_thr = use_threshold != 0;
+  const int gi = (N1 + 31) / 32, gp = a.tiles_n * 4;
+  const dim3 gn(gi + gp, 1);
+  switch (C) {
+    case 64: norm_pack32_kernel<1><<<gn, 256, 0, s>>>(desc1, N1, gi, desc2, N2, gp, a.nks, w.imb, w.blob, eps); break;
+    case 128: norm_pack32_kernel<2><<<gn, 256, 0, s>>>(desc1, N1, gi, desc2, N2, gp, a.nks, w.imb, w.blob, eps); break;
+    case 256: norm_pack32_kernel<4><<<gn, 256, 0, s>>>(desc1, N1, gi, desc2, N2, gp, a.nks, w.imb, w.blob, eps); break;
+    default: norm_pack32_kernel<8><<<gn, 256, 0, s>>>(desc1, N1, gi, desc2, N2, gp, a.nks, w.imb, w.blob, eps); break;
+  }
+  nn_tile_kernel<<<dim3((unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n)), 256, 0, s>>>(a, n);
+  const int mx = N1 > N2 ? N1 : N2;
+  nn_select_kernel<<<dim3((mx + 255) / 256, nn21 ? 2 : 1), 256, 0, s>>>(a, n);
+  match_compact_kernel<true><<<1, 1024, 0, s>>>(w.sel_j, w.sel_v, N1, matches, nullptr, scores, count);
+  return nm_launch_status();
+}
 
 extern "C" size_t nm_match_fused_workspace_bytes(int P, int M, int N, int C) {
   if (P <= 0 || M <= 0 || N <= 0 || C <= 0) return 0;
@@ -629,10 +840,10 @@ extern "C" int nm_dual_softmax_match_fused(const float* im, const float* pt, int
   const int gi = (M + 31) / 32, gp = a.tiles_n * 4;  // groups of 32 rows (the point side is padded to whole 128-row chunks)
   const dim3 gn(gi + gp, P);
   switch (C) {
-    case 64: norm_pack32_kernel<1><<<gn, 256, 0, s>>>(im, M, gi, pt, N, gp, a.nks, w.imb, w.blob); break;
-    case 128: norm_pack32_kernel<2><<<gn, 256, 0, s>>>(im, M, gi, pt, N, gp, a.nks, w.imb, w.blob); break;
-    case 256: norm_pack32_kernel<4><<<gn, 256, 0, s>>>(im, M, gi, pt, N, gp, a.nks, w.imb, w.blob); break;
-    default: norm_pack32_kernel<8><<<gn, 256, 0, s>>>(im, M, gi, pt, N, gp, a.nks, w.imb, w.blob); break;
+    case 64: norm_pack32_kernel<1><<<gn, 256, 0, s>>>(im, M, gi, pt, N, gp, a.nks, w.imb, w.blob, 1e-6f); break;
+    case 128: norm_pack32_kernel<2><<<gn, 256, 0, s>>>(im, M, gi, pt, N, gp, a.nks, w.imb, w.blob, 1e-6f); break;
+    case 256: norm_pack32_kernel<4><<<gn, 256, 0, s>>>(im, M, gi, pt, N, gp, a.nks, w.imb, w.blob, 1e-6f); break;
+    default: norm_pack32_kernel<8><<<gn, 256, 0, s>>>(im, M, gi, pt, N, gp, a.nks, w.imb, w.blob, 1e-6f); break;
   }
   const dim3 gt((unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n), P);
   match_tile_kernel<1><<<gt, 256, 0, s>>>(a);
@@ -641,6 +852,6 @@ extern "C" int nm_dual_softmax_match_fused(const float* im, const float* pt, int
   match_tile_kernel<2><<<gt, 256, 0, s>>>(a);
   match_select_kernel<<<dim3((M + 63) / 64, P), 256, 0, s>>>(a);
   match_tie_kernel<<<dim3(a.tiles_m, P), 256, 0, s>>>(a);
-  match_compact_kernel<<<P, 1024, 0, s>>>(w.sel_j, w.sel_v, M, out_i, out_j, out_conf, counts);
+  match_compact_kernel<false><<<P, 1024, 0, s>>>(w.sel_j, w.sel_v, M, out_i, out_j, out_conf, counts);
   return nm_launch_status();
 }

@@ -4,8 +4,10 @@ torch.autograd.Function, the optimiser and schedule table is trainer._TrainerBas
 is one process per GPU with dist.GradBuckets as in the matcher trainers.
 
 Batches carry the reference's keys: `rays` (1,R,12), `rgbs` (1,R,3), `ts` (1,R) appearance ids, `mask` (R,1) (read when
-loss.use_sem_mask), `seq_ind`, `img_idx`, `img_wh`.  Not built: the two-view pose metrics of log_step (compute_nerf_pose_metrics, :125-136)
-and image logging; validation_step returns the scalar metrics."""
+loss.use_sem_mask), `seq_ind`, `img_idx`, `img_wh`; a two-view validation batch (the pair dataset's) also `c2w` (1,8,4), `K` (1,6,3) and
+`unnorm_scene` (1,4,4).  validation_step returns the scalar metrics and, for a two-view batch, the pose metrics of log_step
+(utils.metrics.compute_nerf_pose_metrics, :125-133): cosine mutual-NN matching of the two views' point features and four PnP problems, on
+the GPU.  Not built: image logging."""
 import torch
 
 from . import dist as nmdist
@@ -13,7 +15,7 @@ from .nerf.renderer import NerfRenderer
 from .nerf.train_render import training_metrics
 from .nerf_evaluator import save_nerf_ckpt
 from .trainer import _TrainerBase
-from .utils.metrics import compute_nerf_metrics
+from .utils.metrics import compute_nerf_metrics, compute_nerf_pose_metrics
 
 
 def init_pfeat_mask(img_wh, ds=8, sample_num=1):
@@ -67,7 +69,8 @@ class NerfTrainer(_TrainerBase):
         return {k: v.detach() for k, v in metrics.items()}
 
     def validation_step(self, data, batch_idx=0, **render_kw):
-        """Validation render (ret_pfeat=True, pfeat_mask honoured) and its scalar metrics (reference :160-180)."""
+        """Validation render (ret_pfeat=True, pfeat_mask honoured) and its scalar metrics (reference :160-180); a batch of more than one
+        view (len(data["img_idx"]) > 1) adds R_err_depth, t_err_depth, R_err_match, t_err_match, match_score and num_matches (:125-133)."""
         m = self.model
         m.ret_pfeat = True
         m.set_training_mode(False)
@@ -79,6 +82,8 @@ class NerfTrainer(_TrainerBase):
             preds = m.forward(rays.to(dev), ray_id=ray_id, validation=True, **render_kw)
             mask = data["mask"].to(dev) if self.mask_loss else None
             metrics = compute_nerf_metrics(preds, self._rows(data["rgbs"], 3).to(dev), mask_loss=mask, validation_mode=True, cnfg_loss=self.cnfg_loss)
+            if len(data["img_idx"]) > 1:
+                metrics.update(compute_nerf_pose_metrics(preds["pts_fine"], m.pfeat_mask[0, ..., 0], preds["feat_fine"], data))
         return metrics
 
     def fit(self, loader, max_epochs=1, log=None):

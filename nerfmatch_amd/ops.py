@@ -755,6 +755,43 @@ def dual_softmax_match_batch(im, pt, scale, im_mask=None, pt_mask=None, threshol
     return dict(i_ids=oi, j_ids=oj, mconf=oc, count=cnt, conf=conf, im_norm=imn, pt_norm=ptn)
 
 
+_feature_nn_ws = {}
+
+
+def feature_mutual_nn(desc1, desc2, threshold=None, eps=1e-9, want_nn=False):
+    """nm_feature_mutual_nn: cosine mutual nearest neighbours of desc1 (N1,C) and desc2 (N2,C) -> (matches (K,2) int64, scores (K,) fp32),
+    and with want_nn=True also (nn12 (N1,) int32, nn21 (N2,) int32).  Rows are normalised as f / (|f| + eps); equal similarities go to
+    the lowest index; a truthy `threshold` keeps score > threshold, None / 0 keeps every mutual pair.  K is read back from the device
+    (one 4-byte copy, like dual_softmax_match).  An empty side returns empty lists without a launch (nn: -1)."""
+    if desc1.dim() != 2 or desc2.dim() != 2 or desc1.shape[1] != desc2.shape[1]:
+        raise _lib.NerfmatchAmdError(f"feature_mutual_nn: descriptor sets of shapes {tuple(desc1.shape)} and {tuple(desc2.shape)}")
+    N1, Cc = desc1.shape
+    N2 = desc2.shape[0]
+    dev = desc1.device
+    if N1 == 0 or N2 == 0:
+        out = (torch.empty(0, 2, device=dev, dtype=torch.int64), torch.empty(0, device=dev, dtype=torch.float32))
+        if want_nn:
+            out += (torch.full((N1,), -1, device=dev, dtype=torch.int32), torch.full((N2,), -1, device=dev, dtype=torch.int32))
+        return out
+    L = lib()
+    need = L.nm_feature_mutual_nn_workspace_bytes(N1, N2, Cc)
+    ws = _scratch(_feature_nn_ws, dev, need)
+    matches = torch.empty(N1, 2, device=dev, dtype=torch.int64)
+    scores = torch.empty(N1, device=dev, dtype=torch.float32)
+    cnt = torch.empty(1, device=dev, dtype=torch.int32)
+    nn12 = torch.empty(N1, device=dev, dtype=torch.int32) if want_nn else None
+    nn21 = torch.empty(N2, device=dev, dtype=torch.int32) if want_nn else None
+    use_thr = bool(threshold)  # the reference's `if threshold:`
+    with _probe("nm_feature_mutual_nn", 2.0 * N1 * N2 * Cc):
+        rc = L.nm_feature_mutual_nn(dptr(desc1), dptr(desc2), N1, N2, Cc, float(eps), float(threshold) if use_thr else 0.0, int(use_thr),
+                                    dptr(matches, torch.int64), dptr(scores), dptr(cnt, torch.int32), dptr(nn12, torch.int32),
+                                    dptr(nn21, torch.int32), dptr(ws, torch.uint8), C.c_size_t(need), stream())
+    check(rc, "nm_feature_mutual_nn")
+    k = int(cnt.item())
+    out = (matches[:k], scores[:k])
+    return out + (nn12, nn21) if want_nn else out
+
+
 def fine_windows(ffeat_chw, i_ids, count, win=5, stride=4):
     """ffeat (C,Hf,Wf), i_ids (K,) int64 -> (K, win*win, C)."""
     Cc, Hf, Wf = ffeat_chw.shape
