@@ -341,6 +341,37 @@ int nm_nerf_photo_loss(const float* rgb_c, const float* rgb_f, const float* gt, 
 int nm_nerf_app_grad(const float* g_xd_a, const float* g_xd_b, const long long* ray_id, int R, int S, int V, float* g_ray, float* g_table,
                      nmStream_t stream);
 
+/* ---- Training ray batches from device-resident frames (csrc/ray_bank.hip) ---------------------------------------------------
+ * Replaces the pre-expanded host ray table of NerfBaseDataset (load_sample + process_train_data, nerfmatch/datasets/nerfbase.py:255-321,
+ * :351-385; get_ray_dirs / get_rays_c2w / prepare_rays_data, nerfmatch/nerf/render_utils.py:23-41, :81-104) and the shuffling DataLoader
+ * over it.  The bank: images [F,H,W,3] uint8, masks [F,H,W] uint8 or NULL, cams [F,21] = row-major Kinv (9) | rows 0..2 of the normalised
+ * camera-to-world (12), flags [F] int32, ts_table [F] int64 (the frame's appearance id) -- all on the device.  Pixel g = (f H + y) W + x.
+ * The per-pixel expressions are nm_raygen's: rows of pixels outside the last image row, norm_ray_dir != 0, equal nm_raygen's at ds = 1
+ * bit for bit.  The last row's radius is the reference's (the value of row H-3, `dx[-2:-1]`, render_utils.py:94-95), which nm_raygen's is
+ * not; hence H >= 3. */
+
+/* flags[f] = 1 iff some pixel of frame f has a unit-sphere discriminant that is not >= 0: every ray of that frame gets far = 1
+ * (the try / except around rays_intersect_sphere, nerfbase.py:287-293).  Once per bank. */
+int nm_raybank_frame_flags(const float* cams, int F, int H, int W, int* flags, nmStream_t stream);
+
+/* n rays, one thread each.  Ray i's index j comes from ids[i] (int64, device) or, ids == NULL, from the epoch permutation
+ * j = perm(pos0 + i * pos_stride); its pixel is g = valid[j] (valid: int64 [n_src], device) or, valid == NULL, g = j.
+ *   n_src: the size of the index space of j (the length of `valid`; F*H*W without it).
+ *   perm: a keyed bijection of [0, n_src): a balanced 4-round Feistel network on 2 * perm_half_bits bits (the smallest even number with
+ *     2^bits >= n_src; <= 40), halves (l, r) -> (r, l ^ (mix(r + key_k) & (2^half_bits - 1))) with nm_pnp_ransac's 32-bit mix, re-applied
+ *     while the value is >= n_src (cycle walking).  perm_keys_host: the 4 round keys (host; derived from (seed, epoch) by the caller).
+ *     Every position must lie in [0, n_src) (NM_ERR_ARG otherwise).  nerfmatch_amd.nerf.ray_bank.epoch_ids states it in torch.
+ * Outputs (device): rays [n,12] = o(3) d(3) near far viewdir(3) radius (16-byte aligned) with d = viewdir (norm_ray_dir != 0) or the
+ *   unnormalised dirs . R^T, whose row neighbours then give the radius (nerfbase.py:284); far = (sqrt(disc) - o.v) / v.v from the unit
+ *   directions, or 1 where flags[f]; rgbs [n,3] = uint8 / 255 (true division); ts [n] int64 = ts_table[f]; mask [n] (may be NULL; needs
+ *   masks) = 1 - round(m / 255) (mask_transient, nerfbase.py:225-228).
+ * An index outside its table (ids[i] or valid[j]) is clamped into it and counted in *bad (device int, add-only; zeroed by the caller):
+ *   no id can make the kernel leave the tables. */
+int nm_raybank_gather(const uint8_t* images, const uint8_t* masks, const float* cams, const int* flags, const long long* ts_table, int F, int H,
+                      int W, const long long* ids, const long long* valid, long long n_src, const uint32_t* perm_keys_host, int perm_half_bits,
+                      long long pos0, long long pos_stride, int n, int norm_ray_dir, float near_plane, float* rays, float* rgbs, long long* ts,
+                      float* mask, int* bad, nmStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Matcher half
  * ---------------------------------------------------------------------------------------------- */

@@ -82,6 +82,10 @@ SIGNATURES = {
     "nm_nerf_distortion_bwd": (i32, [vp, vp, i32, i32, f32, vp, vp]),
     "nm_nerf_photo_loss": (i32, [vp, vp, vp, vp, f32, i32, vp, vp, vp, vp]),
     "nm_nerf_app_grad": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    # training ray batches from device-resident frames (ray_bank.hip)
+    "nm_raybank_frame_flags": (i32, [vp, i32, i32, i32, vp, vp]),
+    "nm_raybank_gather": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, C.c_longlong, C.POINTER(C.c_uint32), i32, C.c_longlong, C.c_longlong,
+                                i32, i32, f32, vp, vp, vp, vp, vp, vp]),
     "nm_linear": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "nm_linear_blob_bytes_bf16x3": (sz, [i32, i32]),
     "nm_linear_qkv_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -92,6 +92,17 @@ __device__ __forceinline__ void nm_sincosf(float x, float& sn, float& cs) {
 }
 __device__ __forceinline__ float nm_cosf(float x) { return nm_sincos_sel(x, 1); }
 
+// 32-bit integer mix (a bijection of uint32): the hash of the PnP sampler (pnp.hip, whose header comment states it) and the round function
+// of the ray bank's epoch permutation (ray_bank.hip)
+__device__ __forceinline__ uint32_t nm_mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 15;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+
 __device__ __forceinline__ float nm_shfl_xor32(float v) { return __shfl_xor(v, 32, 64); }
 
 // sum over the 64 lanes of a wavefront (xor butterfly: every lane ends up with the total)

@@ -32,19 +32,11 @@ constexpr int PNP_GN_ITERS = 5;
 constexpr double PNP_AREA_FLOOR = 1e-8;  // sin^2 of the angle at x1 of the sample triangle below which there is no hypothesis
 constexpr double PNP_LAMBDA0 = 1e-3, PNP_LAMBDA_MIN = 1e-9, PNP_LAMBDA_MAX = 1e9;
 
-__device__ __forceinline__ uint32_t pnp_mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ uint32_t pnp_hash4(uint32_t seed, uint32_t h, uint32_t slot, uint32_t attempt) {
-  uint32_t v = pnp_mix32(seed ^ 0x9E3779B9u);
-  v = pnp_mix32(v + h);
-  v = pnp_mix32(v + slot);
-  return pnp_mix32(v + attempt);
+__device__ __forceinline__ uint32_t pnp_hash4(uint32_t seed, uint32_t h, uint32_t slot, uint32_t attempt) {  // nm_mix32: common.h
+  uint32_t v = nm_mix32(seed ^ 0x9E3779B9u);
+  v = nm_mix32(v + h);
+  v = nm_mix32(v + slot);
+  return nm_mix32(v + attempt);
 }
 
 // the range of query q in the match arrays, clamped to [0, K]: whatever `offsets` holds, no access leaves the arrays

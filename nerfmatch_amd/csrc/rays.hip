@@ -3,6 +3,7 @@
 // row-major writes.  They exist so that a localisation step never leaves the device; the reference
 // builds the full-resolution ray grid on the CPU and copies 1/64 of it (render_utils.py:56-78).
 #include "common.h"
+#include "ray_pixel.h"  // view_dir, ray_sphere, ray_far_plane, cone_radius: shared with ray_bank.hip
 #include <cstdlib>
 
 namespace {
@@ -14,24 +15,6 @@ struct RayGenArgs {
   float near_plane;
   float poses[RAYGEN_MAXQ][12];  // rows 0..2 of the normalised camera-to-world matrices
 };
-struct RayGenPose {  // kinv + the pose of the query this workgroup row (blockIdx.y) belongs to
-  float kinv[9];
-  float c2w[12];
-};
-
-__device__ __forceinline__ void view_dir(const RayGenPose& a, int px, int py, float (&v)[3]) {
-  const float x = (float)px, y = (float)py;
-  float cam[3], wd[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) cam[j] = NM_FMA(1.0f, a.kinv[3 * j + 2], NM_FMA(y, a.kinv[3 * j + 1], x * a.kinv[3 * j]));
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-    wd[j] = NM_FMA(cam[2], a.c2w[4 * j + 2], NM_FMA(cam[1], a.c2w[4 * j + 1], cam[0] * a.c2w[4 * j]));
-  const float n = sqrtf(wd[0] * wd[0] + wd[1] * wd[1] + wd[2] * wd[2]);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) v[j] = wd[j] / n;
-}
-
 // grid: one thread per sub-sampled ray.  Besides its own pixel every thread evaluates the direction of the
 // pixel one image row below (cone radius = distance between unit directions of row neighbours) and every
 // thread of the FULL image contributes to the far-plane validity flag: the reference checks the discriminant
@@ -60,10 +43,7 @@ __global__ void raygen_kernel(RayGenArgs a, float* __restrict__ rays, int* __res
     for (int xx = x0; xx < x1; ++xx) {
       float v[3];
       view_dir(pz, xx, yy, v);
-      const float od = o[0] * v[0] + o[1] * v[1] + o[2] * v[2];
-      const float dd = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-      const float disc = od * od + (1.0f - oo) * dd;
-      bad |= !(disc >= 0.0f);
+      bad |= !(ray_sphere(o, oo, v).disc >= 0.0f);
     }
   if (bad) atomicOr(fallback, 1);
 
@@ -74,13 +54,8 @@ __global__ void raygen_kernel(RayGenArgs a, float* __restrict__ rays, int* __res
     view_dir(pz, px, py + 1, vn);
   else
     view_dir(pz, px, py - 1, vn);
-  const float e0 = v[0] - vn[0], e1 = v[1] - vn[1], e2 = v[2] - vn[2];
-  const float step = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
-  const float radius = step * 2.0f / 3.4641016151377544f;
-  const float od = o[0] * v[0] + o[1] * v[1] + o[2] * v[2];
-  const float dd = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-  const float disc = od * od + (1.0f - oo) * dd;
-  const float far_plane = (sqrtf(disc) - od) / dd;
+  const float radius = cone_radius(v, vn);
+  const float far_plane = ray_far_plane(ray_sphere(o, oo, v));
   float* r = rays + (size_t)idx * 12;
   r[0] = o[0]; r[1] = o[1]; r[2] = o[2];
   r[3] = v[0]; r[4] = v[1]; r[5] = v[2];
@@ -106,10 +81,8 @@ __global__ void __launch_bounds__(256) raygen_pixels_kernel(RayGenArgs a, float*
   const float oo = o[0] * o[0] + o[1] * o[1] + o[2] * o[2];
   float v[3];
   view_dir(pz, xx, yy, v);
-  const float od = o[0] * v[0] + o[1] * v[1] + o[2] * v[2];
-  const float dd = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-  const float disc = od * od + (1.0f - oo) * dd;
-  const bool bad = inside && !(disc >= 0.0f);
+  const RaySphere sp = ray_sphere(o, oo, v);
+  const bool bad = inside && !(sp.disc >= 0.0f);
   if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(fallback + q, 1);
   const int h = a.ds / 2;
   if (!inside || xx % a.ds != h || yy % a.ds != h) return;
@@ -121,10 +94,8 @@ __global__ void __launch_bounds__(256) raygen_pixels_kernel(RayGenArgs a, float*
     view_dir(pz, xx, yy + 1, vn);
   else
     view_dir(pz, xx, yy - 1, vn);
-  const float e0 = v[0] - vn[0], e1 = v[1] - vn[1], e2 = v[2] - vn[2];
-  const float step = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
-  const float radius = step * 2.0f / 3.4641016151377544f;
-  const float far_plane = (sqrtf(disc) - od) / dd;
+  const float radius = cone_radius(v, vn);
+  const float far_plane = ray_far_plane(sp);
   float* r = rays + ((size_t)q * a.nx * a.ny + (size_t)iy * a.nx + ix) * 12;
   r[0] = o[0]; r[1] = o[1]; r[2] = o[2];
   r[3] = v[0]; r[4] = v[1]; r[5] = v[2];

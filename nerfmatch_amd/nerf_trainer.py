@@ -7,7 +7,8 @@ Batches carry the reference's keys: `rays` (1,R,12), `rgbs` (1,R,3), `ts` (1,R) 
 loss.use_sem_mask), `seq_ind`, `img_idx`, `img_wh`; a two-view validation batch (the pair dataset's) also `c2w` (1,8,4), `K` (1,6,3) and
 `unnorm_scene` (1,4,4).  validation_step returns the scalar metrics and, for a two-view batch, the pose metrics of log_step
 (utils.metrics.compute_nerf_pose_metrics, :125-133): cosine mutual-NN matching of the two views' point features and four PnP problems, on
-the GPU.  Not built: image logging."""
+the GPU.  nerf.ray_bank.RayBank produces all three kinds of batch from frames held on the GPU: `fit(bank)` trains a scene.  Not built: image
+logging."""
 import torch
 
 from . import dist as nmdist
@@ -90,6 +91,8 @@ class NerfTrainer(_TrainerBase):
         from ._lib import steady_gc
 
         for _ in range(max_epochs):
+            if hasattr(loader, "set_epoch"):  # (nerf.ray_bank.RayBank: the epoch keys its permutation, like DistributedSampler.set_epoch)
+                loader.set_epoch(self.current_epoch)
             with steady_gc():
                 for i, batch in enumerate(loader):
                     metrics = self.training_step(batch, i)

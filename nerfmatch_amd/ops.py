@@ -294,6 +294,38 @@ def unnormalize_points(pts, unnorm):
     return out
 
 
+def raybank_frame_flags(cams, H, W):
+    """cams (F,21) on the device (Kinv | c2w rows 0..2 per frame) -> flags (F,) int32: 1 = some pixel of the frame misses the unit sphere."""
+    F = cams.shape[0]
+    assert cams.shape == (F, 21)
+    flags = torch.empty(F, device=cams.device, dtype=torch.int32)
+    check(lib().nm_raybank_frame_flags(dptr(cams), F, int(H), int(W), dptr(flags, torch.int32), stream()), "nm_raybank_frame_flags")
+    return flags
+
+
+def raybank_gather(images, cams, flags, ts_table, bad, n, ids=None, perm=None, pos0=0, pos_stride=1, valid=None, masks=None, norm_ray_dir=True,
+                   near=NEAR_PLANE):
+    """n training rays of a ray bank (images (F,H,W,3) uint8, cams (F,21), flags (F,) int32, ts_table (F,) int64, masks (F,H,W) uint8 or None)
+    -> rays (n,12), rgbs (n,3), ts (n,) int64, mask (n,1) or None.  ids: (n,) int64 device indices; or perm = (keys, half_bits) of the epoch
+    permutation applied to positions pos0 + i * pos_stride.  valid: int64 table the indices go through.  bad: device int32[1] counter of
+    clamped indices (add-only).  No host synchronisation."""
+    F, H, W, _ = images.shape
+    assert images.shape == (F, H, W, 3) and cams.shape == (F, 21) and (ids is None) != (perm is None)
+    assert ids is None or ids.shape == (n,)
+    n_src = F * H * W if valid is None else valid.numel()
+    dev = images.device
+    rays = torch.empty(n, 12, device=dev, dtype=torch.float32)
+    rgbs = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    ts = torch.empty(n, device=dev, dtype=torch.int64)
+    mask = None if masks is None else torch.empty(n, 1, device=dev, dtype=torch.float32)
+    keys, half_bits = (None, 0) if perm is None else ((C.c_uint32 * 4)(*perm[0]), int(perm[1]))
+    check(lib().nm_raybank_gather(dptr(images, torch.uint8), dptr(masks, torch.uint8), dptr(cams), dptr(flags, torch.int32),
+                                  dptr(ts_table, torch.int64), F, H, W, dptr(ids, torch.int64), dptr(valid, torch.int64), n_src, keys, half_bits,
+                                  int(pos0), int(pos_stride), int(n), int(bool(norm_ray_dir)), float(near), dptr(rays), dptr(rgbs),
+                                  dptr(ts, torch.int64), dptr(mask), dptr(bad, torch.int32), stream()), "nm_raybank_gather")
+    return rays, rgbs, ts, mask
+
+
 # ----------------------------------------------------------------------------- matcher half
 # Arithmetic of the nn.Linear layers: "fp32" (v_mfma_f32_32x32x2_f32, nm_linear) or "bf16x3" (bf16 MFMA on hi/lo-split
 # operands, fp32-accurate, nm_linear_bf16x3).  Module-level switch like ATTENTION_PRECISION.
