@@ -35,7 +35,7 @@ enum {
 };
 
 /* Bumped on every removed or re-signed symbol; nm_abi_version() of a loaded library must equal the binding's own number. */
-#define NM_ABI_VERSION 2
+#define NM_ABI_VERSION 3
 int nm_abi_version(void);
 const char* nm_error_string(int code);
 
@@ -290,17 +290,25 @@ int nm_inerf_composite(const float* logit_rgb, const float* sigma_raw, int ld, c
 int nm_inerf_composite_bwd(const float* logit_rgb, const float* sigma_raw, int ld, const float* z, const float* rays,
                            const float* g_rgb_map, const float* g_weights, int R, int S, int S_act, float* g_logit,
                            float* g_sigma, float* g_d, nmStream_t stream);
-/* The same two passes on the fused fine field's own output (round 6): out4 [n, 4] = rgb logits | raw sigma per sample, as nm_nerf_points_fwd*_bf16x3
- * writes them; g_out4 [n, 4] = d loss / d (logits, sigma), what nm_nerf_points_bwd*_bf16x3 reads.  One wavefront per ray (prefix product / suffix
- * sum over lanes), 16-byte accesses; weights / g_weights as above (may be NULL).  S_act <= 1024. */
-int nm_inerf_composite4(const float* out4, const float* z, const float* rays, int R, int S, int S_act, float* rgb_map, float* weights,
-                        nmStream_t stream);
-int nm_inerf_composite4_bwd(const float* out4, const float* z, const float* rays, const float* g_rgb_map, const float* g_weights, int R, int S,
-                            int S_act, float* g_out4, float* g_d, nmStream_t stream);
 int nm_inerf_ray_sums(const float* weights, const float* feats, int C, const float* rays, const float* z, int R, int S, int S_act,
                       float* pt_feat, float* pts, nmStream_t stream);
 int nm_inerf_ray_sums_bwd(const float* weights, const float* feats, int C, const float* rays, const float* z, const float* g_pt_feat,
                           const float* g_pts, int R, int S, int S_act, float* g_feats, float* g_weights, nmStream_t stream);
+
+/* ---- Compositing along a ray and its backward, one wavefront per ray (csrc/nerf_composite.hip) -------------------------------
+ * volume_render_radiance_field (render_utils.py:176-230) on the MLP's own output rows, for the refinement's fused fine pass and for scene
+ * training: out4 [R*S_act, 4] = rgb logits | raw sigma per sample (what nm_nerf_points_fwd*_bf16x3 and the GEMM chain write), t [R, S+1]
+ * fence posts, delta = dz * |rays[:, 3:6]|; only the first S_act <= S samples of a ray exist (see above).  density = relu(raw sigma +
+ * noise [R, S_act] * noise_std) (noise NULL: none), white_bg either way, the +1e-10 in the transmittance product
+ *   -> rgb [R,3], depth [R], acc [R], weights [R, S_act] (the last three may be NULL).
+ * _bwd: g_rgb [R,3], g_weights [R, S_act] (NULL = none) -> g_out4 [R*S_act, 4] = d loss / d (logits, sigma), what
+ * nm_nerf_points_bwd*_bf16x3 reads (the density gate is raw sigma + noise * noise_std > 0), and g_d [R,3] = d loss / d rays[:, 3:6]
+ * through |d| (NULL: not wanted).  Prefix product / suffix sum over lanes, 16-byte accesses.  1 <= S_act <= S; S_act > 1024 is
+ * NM_ERR_UNSUPPORTED from both. */
+int nm_nerf_composite4(const float* out4, const float* t, const float* rays, const float* noise, float noise_std, int white_bg, int R, int S,
+                       int S_act, float* rgb, float* depth, float* acc, float* weights, nmStream_t stream);
+int nm_nerf_composite4_bwd(const float* out4, const float* t, const float* rays, const float* noise, float noise_std, int white_bg,
+                           const float* g_rgb, const float* g_weights, int R, int S, int S_act, float* g_out4, float* g_d, nmStream_t stream);
 
 /* ---- NeRF scene training (csrc/nerf_train.hip) ---------------------------------------------------------------------------
  * The per-ray kernels of one training step of NerfRenderer.render_rays(validation=False) (nerfmatch/nerf/renderer.py:182-295) and
@@ -314,14 +322,6 @@ int nm_inerf_ray_sums_bwd(const float* weights, const float* feats, int C, const
  * device such an id is clamped into the table and counted in *status (int, device, may be NULL; add-only). */
 int nm_nerf_train_encode(const float* rays, const float* t, int R, int S, const long long* ray_id, const long long* ray_id_host,
                          const float* table, int V, float var_scale, float* xi, float* xd, int* status, nmStream_t stream);
-/* volume_render_radiance_field in training mode (render_utils.py:176-230): out4[R*S,4] = rgb logits | raw sigma,
- * density = relu(raw sigma + noise[R,S] * noise_std) (noise NULL: none), white_bg either way, the +1e-10 in the transmittance product
- * -> rgb[R,3], depth[R], acc[R], weights[R,S] (the last three may be NULL).  One wavefront per ray, S <= 1024.
- * _bwd: g_rgb[R,3], g_weights[R,S] (NULL = none) -> g_out4[R*S,4]; the density gate is raw sigma + noise * noise_std > 0. */
-int nm_nerf_train_composite(const float* out4, const float* t, const float* rays, const float* noise, float noise_std, int white_bg, int R,
-                            int S, float* rgb, float* depth, float* acc, float* weights, nmStream_t stream);
-int nm_nerf_train_composite_bwd(const float* out4, const float* t, const float* rays, const float* noise, float noise_std, int white_bg,
-                                const float* g_rgb, const float* g_weights, int R, int S, float* g_out4, nmStream_t stream);
 /* s[R,S+1] = t_to_s(t, min t, max t) (render_utils.py:618-636; minimum and maximum over the WHOLE batch, reduced on the device; g's
  * in-place eps as the reference applies it) and, with weights[R,S], lossfun_distortion (metrics.py:453-465) per ray -> loss_ray[R] and
  * its mean -> loss_mean[1] (may be NULL).  t_is_s != 0: `t` already holds s (s and workspace may then be NULL).

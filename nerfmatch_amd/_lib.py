@@ -14,7 +14,7 @@ import os
 
 LIB_PATH = Path(os.environ.get("NERFMATCH_AMD_LIB", PKG / "lib" / "libnerfmatch_amd.so"))  # env override: kernel A/B builds
 
-ABI_VERSION = 2  # NM_ABI_VERSION of include/nerfmatch_amd.h; lib() refuses a library that reports another one
+ABI_VERSION = 3  # NM_ABI_VERSION of include/nerfmatch_amd.h; lib() refuses a library that reports another one
 
 _lib = None
 
@@ -64,8 +64,6 @@ SIGNATURES = {
     "nm_nerf_fwd_fp16x1": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "nm_unnormalize_points": (i32, [vp, vp, i32, vp, vp]),
     "nm_inerf_encode": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
-    "nm_inerf_composite4": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
-    "nm_inerf_composite4_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "nm_inerf_encode_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "nm_inerf_encode_bwd2": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "nm_inerf_pose_grad": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
@@ -73,10 +71,11 @@ SIGNATURES = {
     "nm_inerf_composite_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "nm_inerf_ray_sums": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
     "nm_inerf_ray_sums_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    # compositing along a ray, one wavefront per ray (nerf_composite.hip)
+    "nm_nerf_composite4": (i32, [vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "nm_nerf_composite4_bwd": (i32, [vp, vp, vp, vp, f32, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
     # NeRF scene training (nerf_train.hip)
     "nm_nerf_train_encode": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, f32, vp, vp, vp, vp]),
-    "nm_nerf_train_composite": (i32, [vp, vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]),
-    "nm_nerf_train_composite_bwd": (i32, [vp, vp, vp, vp, f32, i32, vp, vp, i32, i32, vp, vp]),
     "nm_nerf_distortion_workspace_bytes": (sz, []),
     "nm_nerf_distortion": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
     "nm_nerf_distortion_bwd": (i32, [vp, vp, i32, i32, f32, vp, vp]),

@@ -6,7 +6,8 @@
 //   x_pts = IPE(o + t_mean * v, var)          -> nm_inerf_encode      / nm_inerf_encode_bwd
 //   x_dir = PE(v), appearance row                (same kernels)
 //   8x256 MLP + heads                          -> nm_linear / nm_linear_bf16x3, forward and (transposed) backward
-//   white-background compositing, delta * |d|  -> nm_inerf_composite  / nm_inerf_composite_bwd
+//   white-background compositing, delta * |d|  -> nm_inerf_composite  / nm_inerf_composite_bwd (one thread per ray, [n, ld] columns: the fp32
+//                                                 route; the fused route composites its [n, 4] rows with nm_nerf_composite4, nerf_composite.hip)
 // Samples s >= S_act are not evaluated: with the reference's randomized resampler the intervals s > S/2 have zero
 // width, i.e. weight 0 and -- because d(alpha)/d(sigma) = delta exp(-sigma delta) = 0 and delta = dz |d| with dz = 0 --
 // gradient exactly 0 (cf. NM_NERF_ZERO_TAIL).  S_act = S evaluates everything.
@@ -14,11 +15,8 @@
 
 namespace {
 // the sample math the render and points kernels inline too (nerf_sample.h)
-using nmsample::HALF_PI_F32, nmsample::frustum, nmsample::ray_consts, nmsample::ray_norm, nmsample::lift_var, nmsample::ipe_exact, nmsample::ipe_damp_exact;
-using nmsample::view_row_value, nmsample::attenuation, nmsample::alpha_of, nmsample::trans_factor, nmsample::sigmoid;
-
-constexpr int XI = 96;   // IPE columns (90 used)
-constexpr int XD = 48;   // view-direction PE (27) | appearance row (16) | padding
+using nmsample::HALF_PI_F32, nmsample::frustum, nmsample::ray_consts, nmsample::ray_norm, nmsample::lift_var, nmsample::ipe_damp_exact;
+using nmsample::XI, nmsample::XD, nmsample::write_sample_rows, nmsample::attenuation, nmsample::alpha_of, nmsample::trans_factor, nmsample::sigmoid;
 
 struct Gauss {
   float t_mean, var[3];
@@ -34,31 +32,16 @@ __device__ __forceinline__ Gauss gauss_of(float t0, float t1, const float* d, fl
   return g;
 }
 
-// 16 threads per sample (round 4; was one thread per output element, each recomputing the sample's Gaussian): thread i < 15 writes the
-// six IPE columns of frequency 2^i (3 axes x {sin, sin(. + pi/2)}), thread 15 the view-direction row xd and the padding of xi
+// 16 threads per sample, write_sample_rows' roles (round 4; was one thread per output element, each recomputing the sample's Gaussian)
 __global__ void inerf_encode_kernel(const float* __restrict__ rays, const float* __restrict__ z, int R, int S, int Sa,
                                     const float* __restrict__ app_row, float* __restrict__ xi, float* __restrict__ xd) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t n = idx >> 4;
-  const int i = (int)(idx & 15);
   if (n >= (size_t)R * Sa) return;
   const int r = (int)(n / Sa), s = (int)(n % Sa);
   const float* rp = rays + (size_t)r * 12;
-  if (i < 15) {
-    const Gauss g = gauss_of(z[(size_t)r * (S + 1) + s], z[(size_t)r * (S + 1) + s + 1], rp + 3, rp[11]);
-    const float sc = (float)(1 << i);
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-      const float mean = rp[ax] + g.t_mean * rp[8 + ax];
-      const float xe = mean * sc;
-      xi[n * XI + i * 3 + ax] = ipe_exact(xe, g.var[ax], sc);
-      xi[n * XI + 45 + i * 3 + ax] = ipe_exact(xe + HALF_PI_F32, g.var[ax], sc);
-    }
-  } else {
-#pragma unroll
-    for (int f = 90; f < XI; ++f) xi[n * XI + f] = 0.f;
-    for (int c = 0; c < XD; ++c) xd[n * XD + c] = view_row_value(c, rp[8 + c % 3], app_row);
-  }
+  const float* zr = z + (size_t)r * (S + 1) + s;
+  write_sample_rows(rp, rp + 8, zr[0], zr[1], 0.f, app_row, (int)(idx & 15), xi + n * XI, xd + n * XD);
 }
 
 // g_o[r], g_v[r] = d loss / d origin, d loss / d view direction of ray r.  One workgroup (256 threads) per ray.
@@ -230,152 +213,6 @@ __global__ void inerf_composite_bwd_kernel(const float* __restrict__ logit, cons
   g_d[(size_t)r * 3 + 2] = gnorm * rp[5] * inv;
 }
 
-// Round 6: the same two passes on the FUSED fine field's own output rows (out4 [n, 4] = rgb logits | raw sigma, what nm_nerf_points_fwd*
-// writes), one WAVEFRONT per ray instead of one thread: a lane takes the samples lane, lane + 64, ..., the transmittance is a prefix product
-// over lanes (six shuffle steps per 64 samples, carry between chunks), the backward's B_s = sum_{j > s} q_j w_j a suffix sum the same way; one
-// 16-byte load and one 16-byte store per sample.  The one-thread-per-ray kernels above walk 128 dependent iterations on 75 wavefronts of a
-// 1024-SIMD chip (58 + 66 us per step at 4800 rays) and need sigma copied out of / back into column 3 around them (two strided torch copies).
-// The products / sums associate differently from the sequential loops (a scan tree): results agree to rounding.
-constexpr int CMP_MAX_CHUNKS = 16;  // 64 samples each
-__device__ __forceinline__ float shfl_up_f(float v, int d) { return __shfl_up(v, d, 64); }
-__device__ __forceinline__ float shfl_down_f(float v, int d) { return __shfl_down(v, d, 64); }
-
-struct CmpSample {
-  float raw, sg, dz, delta, ex, alpha, u;
-  f32x4 o;
-};
-__device__ __forceinline__ CmpSample cmp_sample(const float* __restrict__ out4, const float* __restrict__ zr, size_t n, int sidx, bool valid, float dn) {
-  CmpSample c;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  c.o = valid ? *reinterpret_cast<const f32x4*>(out4 + n * 4) : zero4;
-  c.raw = c.o[3];
-  c.sg = fmaxf(c.raw, 0.f);
-  c.dz = valid ? zr[sidx + 1] - zr[sidx] : 0.f;
-  c.delta = c.dz * dn;
-  c.ex = attenuation(c.raw, c.delta);
-  c.alpha = valid ? 1.0f - c.ex : 0.f;  // (alpha_of's expression, from the ex the backward needs anyway)
-  c.u = trans_factor(c.alpha);
-  return c;
-}
-// inclusive prefix product over the lanes; returns it, *excl = the exclusive one (1 in lane 0)
-__device__ __forceinline__ float prefix_prod(float u, int lane, float* excl) {
-  float p = u;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float t = shfl_up_f(p, d);
-    if (lane >= d) p *= t;
-  }
-  const float e = shfl_up_f(p, 1);
-  *excl = lane == 0 ? 1.0f : e;
-  return p;
-}
-
-__global__ void __launch_bounds__(256) inerf_composite4_kernel(const float* __restrict__ out4, const float* __restrict__ z,
-                                                                const float* __restrict__ rays, int R, int S, int Sa, float* __restrict__ rgb_map,
-                                                                float* __restrict__ w_out) {
-  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
-  const float* rp = rays + (size_t)r * 12;
-  const float* zr = z + (size_t)r * (S + 1);
-  const float dn = ray_norm(rp + 3);
-  float T0 = 1.f, acc = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
-  for (int base = 0; base < Sa; base += 64) {
-    const int sidx = base + lane;
-    const bool valid = sidx < Sa;
-    const size_t n = (size_t)r * Sa + sidx;
-    const CmpSample c = cmp_sample(out4, zr, n, sidx, valid, dn);
-    float excl;
-    const float p = prefix_prod(c.u, lane, &excl);
-    const float w = c.alpha * (T0 * excl);
-    if (w_out && valid) w_out[n] = w;
-    c0 += w * sigmoid(c.o[0]); c1 += w * sigmoid(c.o[1]); c2 += w * sigmoid(c.o[2]);
-    acc += w;
-    T0 *= __shfl(p, 63, 64);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    acc += __shfl_xor(acc, o, 64); c0 += __shfl_xor(c0, o, 64); c1 += __shfl_xor(c1, o, 64); c2 += __shfl_xor(c2, o, 64);
-  }
-  if (lane == 0) {
-    rgb_map[(size_t)r * 3] = c0 + (1.0f - acc);
-    rgb_map[(size_t)r * 3 + 1] = c1 + (1.0f - acc);
-    rgb_map[(size_t)r * 3 + 2] = c2 + (1.0f - acc);
-  }
-}
-
-__global__ void __launch_bounds__(256) inerf_composite4_bwd_kernel(const float* __restrict__ out4, const float* __restrict__ z,
-                                                                    const float* __restrict__ rays, const float* __restrict__ G,
-                                                                    const float* __restrict__ g_w, int R, int S, int Sa, float* __restrict__ g4,
-                                                                    float* __restrict__ g_d) {
-  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
-  const float* rp = rays + (size_t)r * 12;
-  const float* zr = z + (size_t)r * (S + 1);
-  const float dn = ray_norm(rp + 3);
-  const float G0 = G[(size_t)r * 3], G1 = G[(size_t)r * 3 + 1], G2 = G[(size_t)r * 3 + 2];
-  // forward sweep: the transmittance at the start of every chunk
-  float carry[CMP_MAX_CHUNKS];
-  const int nchunk = (Sa + 63) / 64;
-  {
-    float T0 = 1.f;
-#pragma unroll
-    for (int k = 0; k < CMP_MAX_CHUNKS; ++k) {
-      carry[k] = T0;
-      if (k < nchunk) {
-        const int sidx = k * 64 + lane;
-        const CmpSample c = cmp_sample(out4, zr, (size_t)r * Sa + sidx, sidx, sidx < Sa, dn);
-        float excl;
-        T0 *= __shfl(prefix_prod(c.u, lane, &excl), 63, 64);
-      }
-    }
-  }
-  // backward sweep: rgb_map = 1 + sum_s w_s (c_s - 1), w_s = alpha_s T_s, T_s = prod_{j<s} u_j, u = 1 - alpha + 1e-10
-  float Bc = 0.f, gnorm = 0.f;  // Bc = sum of q w over the chunks behind this one
-#pragma unroll
-  for (int k = CMP_MAX_CHUNKS - 1; k >= 0; --k) {
-    if (k >= nchunk) continue;
-    const int sidx = k * 64 + lane;
-    const bool valid = sidx < Sa;
-    const size_t n = (size_t)r * Sa + sidx;
-    const CmpSample c = cmp_sample(out4, zr, n, sidx, valid, dn);
-    float excl;
-    prefix_prod(c.u, lane, &excl);
-    const float Ts = carry[k] * excl;
-    const float w = c.alpha * Ts;
-    const float s0 = sigmoid(c.o[0]), s1 = sigmoid(c.o[1]), s2 = sigmoid(c.o[2]);
-    float q = (G0 * (s0 - 1.0f) + G1 * (s1 - 1.0f)) + G2 * (s2 - 1.0f);  // d loss / d w_s
-    if (g_w && valid) q += g_w[n];
-    const float qw = valid ? q * w : 0.f;
-    float sfx = qw;  // inclusive suffix sum over the lanes
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const float t = shfl_down_f(sfx, d);
-      if (lane + d < 64) sfx += t;
-    }
-    const float nxt = shfl_down_f(sfx, 1);
-    const float B = Bc + (lane == 63 ? 0.f : nxt);
-    const float g_alpha = q * Ts - B / c.u;
-    if (valid) {
-      f32x4 g;
-      g[0] = G0 * w * (s0 * (1.0f - s0));
-      g[1] = G1 * w * (s1 * (1.0f - s1));
-      g[2] = G2 * w * (s2 * (1.0f - s2));
-      g[3] = c.raw > 0.f ? g_alpha * (c.delta * c.ex) : 0.f;
-      *reinterpret_cast<f32x4*>(g4 + n * 4) = g;
-      gnorm += g_alpha * (c.sg * c.ex) * c.dz;
-    }
-    Bc += __shfl(sfx, 0, 64);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) gnorm += __shfl_xor(gnorm, o, 64);
-  if (lane == 0) {
-    const float inv = dn > 0.f ? 1.0f / dn : 0.f;
-    g_d[(size_t)r * 3] = gnorm * rp[3] * inv;
-    g_d[(size_t)r * 3 + 1] = gnorm * rp[4] * inv;
-    g_d[(size_t)r * 3 + 2] = gnorm * rp[5] * inv;
-  }
-}
-
 // Matching term of the refinement (nerfmatch_evaluator.py:420-428): per ray, pt_feat = sum_s w_s feats_s and
 // pts = sum_s w_s mean_s, the Gaussian means o + t_mean d being those of the sampler, i.e. constants.
 // One workgroup per ray, thread = feature channel (C <= blockDim); threads 0..2 also do the three coordinates.
@@ -523,21 +360,6 @@ extern "C" int nm_inerf_composite(const float* logit_rgb, const float* sigma_raw
                                   int S_act, float* rgb_map, float* weights, nmStream_t stream) {
   NM_CHECK_ARG(logit_rgb && sigma_raw && z && rays && rgb_map && R > 0 && S > 0 && S_act > 0 && S_act <= S && ld >= 3);
   inerf_composite_kernel<<<(R + 63) / 64, 64, 0, (hipStream_t)stream>>>(logit_rgb, sigma_raw, ld, z, rays, R, S, S_act, rgb_map, weights);
-  return nm_launch_status();
-}
-
-extern "C" int nm_inerf_composite4(const float* out4, const float* z, const float* rays, int R, int S, int S_act, float* rgb_map, float* weights,
-                                   nmStream_t stream) {
-  NM_CHECK_ARG(out4 && z && rays && rgb_map && R > 0 && S > 0 && S_act > 0 && S_act <= S);
-  inerf_composite4_kernel<<<(R + 3) / 4, 256, 0, (hipStream_t)stream>>>(out4, z, rays, R, S, S_act, rgb_map, weights);
-  return nm_launch_status();
-}
-
-extern "C" int nm_inerf_composite4_bwd(const float* out4, const float* z, const float* rays, const float* g_rgb_map, const float* g_weights, int R,
-                                       int S, int S_act, float* g_out4, float* g_d, nmStream_t stream) {
-  NM_CHECK_ARG(out4 && z && rays && g_rgb_map && g_out4 && g_d && R > 0 && S > 0 && S_act > 0 && S_act <= S);
-  if (S_act > 64 * CMP_MAX_CHUNKS) return NM_ERR_UNSUPPORTED;
-  inerf_composite4_bwd_kernel<<<(R + 3) / 4, 256, 0, (hipStream_t)stream>>>(out4, z, rays, g_rgb_map, g_weights, R, S, S_act, g_out4, g_d);
   return nm_launch_status();
 }
 

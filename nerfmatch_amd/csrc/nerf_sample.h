@@ -1,7 +1,8 @@
 // The mip-NeRF sample math, defined ONCE for every NeRF-side kernel: the conical-frustum Gaussian, its lift to a diagonal 3-D covariance,
 // the integrated positional encoding, the view-direction row, the alpha / transmittance step and the compositing scan along a ray.
 // Callers: nerf_fwd.hip (fp32 MFMA render), nerf_fwd_bf16.hip (split render), nerf_points_bf16.hip (pointwise forward "from rays"),
-// inerf.hip (nm_inerf_encode / composite pairs), encode.hip (the constant).  Several tests require these kernels to agree BIT FOR BIT
+// inerf.hip (nm_inerf_encode and its backward, the per-ray compositing loops, the ray sums), nerf_train.hip (nm_nerf_train_encode),
+// nerf_composite.hip (the wavefront-per-ray compositing pair), encode.hip (the constant).  Several tests require these kernels to agree BIT FOR BIT
 // (tests/test_nerf_sample_math_gpu.py, test_tapped_points_kernels_vs_gemm_chain, test_wavefront_compositing_vs_per_ray_loops): they do
 // because they inline the same expression trees from here -- the build uses -ffp-contract=off, so operand order and association below
 // ARE the result bits.  Change a formula here and every kernel changes with it; do not re-type one at a call site.
@@ -97,17 +98,47 @@ __device__ __forceinline__ float ipe_fast(float arg, float var, float sc) { retu
 // ---- views-layer row ------------------------------------------------------------------------------------------------------------
 // Column f of the 48-wide [direction PE | appearance] row: f = 0..11 sin(2^k v), 12..23 sin(2^k v + pi/2) (k = (f % 12) / 3), 24..26 raw v,
 // 27..42 the appearance row (zeros without one), 43..47 padding.  v_ax = component f % 3 of the view direction rays[8:11].
+constexpr int XI = 96;            // columns of an IPE row (90 used)
+constexpr int XD = 48;            // columns of a views-layer row
+constexpr int APP0 = 27, APP = 16;  // the appearance row's first column and width in it
 __device__ __forceinline__ float view_row_value(int f, float v_ax, const float* app_row) {
   float v = 0.f;
   if (f < 24) {
     const float xe = v_ax * (float)(1 << ((f % 12) / 3));
     v = nm_sinf(f < 12 ? xe : xe + HALF_PI_F32);
-  } else if (f < 27) {
+  } else if (f < APP0) {
     v = v_ax;
-  } else if (f < 43) {
-    v = app_row ? app_row[f - 27] : 0.f;
+  } else if (f < APP0 + APP) {
+    v = app_row ? app_row[f - APP0] : 0.f;
   }
   return v;
+}
+
+// ---- the GEMM chains' input rows of one sample ----------------------------------------------------------------------------------------------
+// xi [XI] = IPE (exact flavour) of the Gaussian of interval [t0, t1] of ray rp (rays row, 12 floats) with mean dir * t_mean + o | zero padding,
+// xd [XD] = view_row_value.  16 threads per sample: thread i < 15 writes the six IPE columns of frequency 2^i (3 axes x {sin, sin(. + pi/2)}),
+// thread 15 the view row and the padding of xi.  `dir` is the direction the MEAN reads (lift_var's comment: rays[3:6] for the training
+// render, rays[8:11] for the refinement); the covariance is always that of rays[3:6].
+__device__ __forceinline__ void write_sample_rows(const float* rp, const float* dir, float t0, float t1, float var_scale, const float* app_row, int i,
+                                                  float* __restrict__ xi, float* __restrict__ xd) {
+  if (i < 15) {
+    float t_mean, t_var, r_var, dsq[3], nul[3], dnorm, var[3];
+    frustum(t0, t1, rp[11], t_mean, t_var, r_var);
+    ray_consts(rp + 3, dsq, nul, dnorm);
+    lift_var(t_var, r_var, dsq, nul, var_scale, var);
+    const float sc = (float)(1 << i);
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+      const float mean = dir[ax] * t_mean + rp[ax];
+      const float xe = mean * sc;
+      xi[i * 3 + ax] = ipe_exact(xe, var[ax], sc);
+      xi[45 + i * 3 + ax] = ipe_exact(xe + HALF_PI_F32, var[ax], sc);
+    }
+  } else {
+#pragma unroll
+    for (int f = 90; f < XI; ++f) xi[f] = 0.f;
+    for (int c = 0; c < XD; ++c) xd[c] = view_row_value(c, rp[8 + c % 3], app_row);
+  }
 }
 
 // ---- alpha compositing ----------------------------------------------------------------------------------------------------------

@@ -2,8 +2,8 @@
 // volume_render_radiance_field, nerf/render_utils.py:176-230; t_to_s / g, render_utils.py:618-636; compute_nerf_metrics and
 // lossfun_distortion, nerfmatch/utils/metrics.py:59-96, :448-465): the per-ray kernels of a training step.  The two MLPs run on the GEMM
 // kernels (nm_linear*, nm_linear_wgrad*); what is here sits in front of, between and behind those chains:
-//   nm_nerf_train_encode          rays, fence posts, per-ray appearance id -> the chains' input rows xi | xd (layout of nm_inerf_encode)
-//   nm_nerf_train_composite(_bwd) the chains' output rows -> rgb, depth, acc, weights with the training-time density noise, and back
+//   nm_nerf_train_encode          rays, fence posts, per-ray appearance id -> the chains' input rows xi | xd (nerf_sample.h's write_sample_rows)
+//   (nm_nerf_composite4(_bwd), nerf_composite.hip: the chains' output rows -> rgb, depth, acc, weights with the density noise, and back)
 //   nm_nerf_distortion(_bwd)      s = t_to_s(t) with the batch-wide near / far, the mip-NeRF-360 distortion loss of (s, weights), and back
 //   nm_nerf_photo_loss            the two masked MSE terms and their gradients
 //   nm_nerf_app_grad              d loss / d appearance table from the chains' d loss / d xd, summed in a fixed order
@@ -12,17 +12,13 @@
 #include "nerf_sample.h"
 
 namespace {
-using nmsample::HALF_PI_F32, nmsample::frustum, nmsample::ray_consts, nmsample::ray_norm, nmsample::lift_var, nmsample::ipe_exact;
-using nmsample::view_row_value, nmsample::attenuation, nmsample::trans_factor, nmsample::sigmoid;
+using nmsample::XI, nmsample::XD, nmsample::APP0, nmsample::APP, nmsample::write_sample_rows;
 
-constexpr int XI = 96;   // IPE columns (90 used)
-constexpr int XD = 48;   // view-direction PE (27) | appearance row (16) | padding
-constexpr int APP0 = 27, APP = 16;
-constexpr int MAX_S = 1024;  // samples per ray of the one-wavefront-per-ray kernels
+constexpr int MAX_S = 1024;  // samples per ray of nm_nerf_distortion(_bwd): a workgroup's four rays keep u and w in LDS
 
 __device__ __forceinline__ int clamp_id(long long id, int V) { return id < 0 ? 0 : (id >= V ? V - 1 : (int)id); }
 
-// 16 threads per sample as in nm_inerf_encode: thread i < 15 writes the six IPE columns of frequency 2^i, thread 15 the view row and the padding
+// 16 threads per sample, write_sample_rows' roles; thread 15 also looks up the ray's appearance row
 __global__ void train_encode_kernel(const float* __restrict__ rays, const float* __restrict__ t, int R, int S, const long long* __restrict__ ray_id,
                                     const float* __restrict__ table, int V, float var_scale, float* __restrict__ xi, float* __restrict__ xd,
                                     int* __restrict__ status) {
@@ -32,163 +28,14 @@ __global__ void train_encode_kernel(const float* __restrict__ rays, const float*
   if (n >= (size_t)R * S) return;
   const int r = (int)(n / S), s = (int)(n % S);
   const float* rp = rays + (size_t)r * 12;
-  if (i < 15) {
-    float t_mean, t_var, r_var, dsq[3], nul[3], dnorm, var[3];
-    frustum(t[(size_t)r * (S + 1) + s], t[(size_t)r * (S + 1) + s + 1], rp[11], t_mean, t_var, r_var);
-    ray_consts(rp + 3, dsq, nul, dnorm);
-    lift_var(t_var, r_var, dsq, nul, var_scale, var);
-    const float sc = (float)(1 << i);
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-      const float mean = rp[3 + ax] * t_mean + rp[ax];  // cast_rays: d * t_mean + o with d = rays[3:6] (the forward render kernels' mean)
-      const float xe = mean * sc;
-      xi[n * XI + i * 3 + ax] = ipe_exact(xe, var[ax], sc);
-      xi[n * XI + 45 + i * 3 + ax] = ipe_exact(xe + HALF_PI_F32, var[ax], sc);
-    }
-  } else {
-    const float* app_row = nullptr;
-    if (table) {
-      const long long id = ray_id ? ray_id[r] : 1;  // (no ids: the reference's default id 1, renderer.py:298-299)
-      if ((id < 0 || id >= V) && s == 0 && status) atomicAdd(status, 1);
-      app_row = table + (size_t)clamp_id(id, V) * APP;
-    }
-#pragma unroll
-    for (int f = 90; f < XI; ++f) xi[n * XI + f] = 0.f;
-    for (int c = 0; c < XD; ++c) xd[n * XD + c] = view_row_value(c, rp[8 + c % 3], app_row);
+  const float* tr = t + (size_t)r * (S + 1) + s;
+  const float* app_row = nullptr;
+  if (table && i == 15) {
+    const long long id = ray_id ? ray_id[r] : 1;  // (no ids: the reference's default id 1, renderer.py:298-299)
+    if ((id < 0 || id >= V) && s == 0 && status) atomicAdd(status, 1);
+    app_row = table + (size_t)clamp_id(id, V) * APP;
   }
-}
-
-// ---- compositing: one wavefront per ray, prefix product / suffix sum over lanes (the scheme of nm_inerf_composite4) ---------------------
-struct TrSample {
-  float raw, dz, delta, ex, alpha, u;
-  f32x4 o;
-};
-// raw = raw sigma + noise * noise_std (render_utils.py:189-194: the noise is formed first, then added); its sign is the density gate
-__device__ __forceinline__ TrSample tr_sample(const float* __restrict__ out4, const float* __restrict__ tr, const float* __restrict__ nz,
-                                              float noise_std, size_t n, int sidx, bool valid, float dn) {
-  TrSample c;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  c.o = valid ? *reinterpret_cast<const f32x4*>(out4 + n * 4) : zero4;
-  c.raw = c.o[3];
-  if (nz && valid) c.raw = c.raw + nz[sidx] * noise_std;
-  c.dz = valid ? tr[sidx + 1] - tr[sidx] : 0.f;
-  c.delta = c.dz * dn;
-  c.ex = attenuation(c.raw, c.delta);
-  c.alpha = valid ? 1.0f - c.ex : 0.f;
-  c.u = trans_factor(c.alpha);
-  return c;
-}
-__device__ __forceinline__ float prefix_prod(float u, int lane, float* excl) {
-  float p = u;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float up = __shfl_up(p, d, 64);
-    if (lane >= d) p *= up;
-  }
-  const float e = __shfl_up(p, 1, 64);
-  *excl = lane == 0 ? 1.0f : e;
-  return p;
-}
-
-__global__ void __launch_bounds__(256) train_composite_kernel(const float* __restrict__ out4, const float* __restrict__ t, const float* __restrict__ rays,
-                                                               const float* __restrict__ noise, float noise_std, int white_bg, int R, int S,
-                                                               float* __restrict__ rgb, float* __restrict__ depth, float* __restrict__ acc_out,
-                                                               float* __restrict__ w_out) {
-  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
-  const float* tr = t + (size_t)r * (S + 1);
-  const float* nz = noise ? noise + (size_t)r * S : nullptr;
-  const float dn = ray_norm(rays + (size_t)r * 12 + 3);
-  float T0 = 1.f, acc = 0.f, dep = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
-  for (int base = 0; base < S; base += 64) {
-    const int sidx = base + lane;
-    const bool valid = sidx < S;
-    const size_t n = (size_t)r * S + sidx;
-    const TrSample c = tr_sample(out4, tr, nz, noise_std, n, sidx, valid, dn);
-    float excl;
-    const float p = prefix_prod(c.u, lane, &excl);
-    const float w = c.alpha * (T0 * excl);
-    if (valid) {
-      if (w_out) w_out[n] = w;
-      dep += w * (0.5f * (tr[sidx] + tr[sidx + 1]));
-    }
-    c0 += w * sigmoid(c.o[0]); c1 += w * sigmoid(c.o[1]); c2 += w * sigmoid(c.o[2]);
-    acc += w;
-    T0 *= __shfl(p, 63, 64);
-  }
-  acc = wave_sum(acc); dep = wave_sum(dep); c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2);
-  if (lane == 0) {
-    const float bg = white_bg ? 1.0f - acc : 0.f;
-    rgb[(size_t)r * 3] = c0 + bg;
-    rgb[(size_t)r * 3 + 1] = c1 + bg;
-    rgb[(size_t)r * 3 + 2] = c2 + bg;
-    if (depth) depth[r] = dep;
-    if (acc_out) acc_out[r] = acc;
-  }
-}
-
-// rgb = sum_s w_s (c_s - bg) + bg, w_s = alpha_s T_s, T_s = prod_{j<s} u_j, u = 1 - alpha + 1e-10:  g_out4 = d loss / d (rgb logits, raw sigma)
-__global__ void __launch_bounds__(256) train_composite_bwd_kernel(const float* __restrict__ out4, const float* __restrict__ t,
-                                                                   const float* __restrict__ rays, const float* __restrict__ noise, float noise_std,
-                                                                   int white_bg, const float* __restrict__ G, const float* __restrict__ g_w, int R,
-                                                                   int S, float* __restrict__ g4) {
-  constexpr int CHUNKS = MAX_S / 64;
-  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
-  const float* tr = t + (size_t)r * (S + 1);
-  const float* nz = noise ? noise + (size_t)r * S : nullptr;
-  const float dn = ray_norm(rays + (size_t)r * 12 + 3);
-  const float G0 = G[(size_t)r * 3], G1 = G[(size_t)r * 3 + 1], G2 = G[(size_t)r * 3 + 2];
-  const float bg = white_bg ? 1.0f : 0.f;
-  float carry[CHUNKS];  // the transmittance at the start of every chunk of 64 samples
-  const int nchunk = (S + 63) / 64;
-  {
-    float T0 = 1.f;
-#pragma unroll
-    for (int k = 0; k < CHUNKS; ++k) {
-      carry[k] = T0;
-      if (k < nchunk) {
-        const int sidx = k * 64 + lane;
-        const TrSample c = tr_sample(out4, tr, nz, noise_std, (size_t)r * S + sidx, sidx, sidx < S, dn);
-        float excl;
-        T0 *= __shfl(prefix_prod(c.u, lane, &excl), 63, 64);
-      }
-    }
-  }
-  float Bc = 0.f;  // sum of q w over the chunks behind this one
-#pragma unroll
-  for (int k = CHUNKS - 1; k >= 0; --k) {
-    if (k >= nchunk) continue;
-    const int sidx = k * 64 + lane;
-    const bool valid = sidx < S;
-    const size_t n = (size_t)r * S + sidx;
-    const TrSample c = tr_sample(out4, tr, nz, noise_std, n, sidx, valid, dn);
-    float excl;
-    prefix_prod(c.u, lane, &excl);
-    const float Ts = carry[k] * excl;
-    const float w = c.alpha * Ts;
-    const float s0 = sigmoid(c.o[0]), s1 = sigmoid(c.o[1]), s2 = sigmoid(c.o[2]);
-    float q = (G0 * (s0 - bg) + G1 * (s1 - bg)) + G2 * (s2 - bg);  // d loss / d w_s
-    if (g_w && valid) q += g_w[n];
-    float sfx = valid ? q * w : 0.f;  // inclusive suffix sum over the lanes
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const float dnv = __shfl_down(sfx, d, 64);
-      if (lane + d < 64) sfx += dnv;
-    }
-    const float nxt = __shfl_down(sfx, 1, 64);
-    const float B = Bc + (lane == 63 ? 0.f : nxt);
-    const float g_alpha = q * Ts - B / c.u;
-    if (valid) {
-      f32x4 g;
-      g[0] = G0 * w * (s0 * (1.0f - s0));
-      g[1] = G1 * w * (s1 * (1.0f - s1));
-      g[2] = G2 * w * (s2 * (1.0f - s2));
-      g[3] = c.raw > 0.f ? g_alpha * (c.delta * c.ex) : 0.f;
-      *reinterpret_cast<f32x4*>(g4 + n * 4) = g;
-    }
-    Bc += __shfl(sfx, 0, 64);
-  }
+  write_sample_rows(rp, rp + 3, tr[0], tr[1], var_scale, app_row, i, xi + n * XI, xd + n * XD);  // (cast_rays: d * t_mean + o with d = rays[3:6])
 }
 
 // ---- s = t_to_s(t, min t, max t) and the distortion loss ----------------------------------------------------------------------------------
@@ -359,22 +206,6 @@ extern "C" int nm_nerf_train_encode(const float* rays, const float* t, int R, in
     for (int r = 0; r < R; ++r) NM_CHECK_ARG(ray_id_host[r] >= 0 && ray_id_host[r] < V);
   const size_t total = (size_t)R * S * 16;
   train_encode_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(rays, t, R, S, ray_id, table, V, var_scale, xi, xd, status);
-  return nm_launch_status();
-}
-
-extern "C" int nm_nerf_train_composite(const float* out4, const float* t, const float* rays, const float* noise, float noise_std, int white_bg, int R,
-                                       int S, float* rgb, float* depth, float* acc, float* weights, nmStream_t stream) {
-  NM_CHECK_ARG(out4 && t && rays && rgb && R > 0 && S > 0);
-  if (S > MAX_S) return NM_ERR_UNSUPPORTED;
-  train_composite_kernel<<<(R + 3) / 4, 256, 0, (hipStream_t)stream>>>(out4, t, rays, noise, noise_std, white_bg, R, S, rgb, depth, acc, weights);
-  return nm_launch_status();
-}
-
-extern "C" int nm_nerf_train_composite_bwd(const float* out4, const float* t, const float* rays, const float* noise, float noise_std, int white_bg,
-                                           const float* g_rgb, const float* g_weights, int R, int S, float* g_out4, nmStream_t stream) {
-  NM_CHECK_ARG(out4 && t && rays && g_rgb && g_out4 && R > 0 && S > 0);
-  if (S > MAX_S) return NM_ERR_UNSUPPORTED;
-  train_composite_bwd_kernel<<<(R + 3) / 4, 256, 0, (hipStream_t)stream>>>(out4, t, rays, noise, noise_std, white_bg, g_rgb, g_weights, R, S, g_out4);
   return nm_launch_status();
 }
 

@@ -6,8 +6,9 @@ backward:
   rays              nm_raygen (values) -- only o and viewdir carry gradient; d(o, viewdir)/d(pose) is a 16-parameter torch
                     autograd expression over the sub-sampled pixel grid (plumbing-sized)
   sampling, coarse  nm_sample_coarse, fused nm_nerf_fwd (weights only, no grad), nm_resample -- as in render_rays
-  fine pass         nm_inerf_encode -> nm_linear(_bf16x3) x 12 -> nm_inerf_composite, and the mirrored backward
-                    nm_inerf_composite_bwd -> nm_linear(_bf16x3) with transposed weights -> nm_inerf_encode_bwd
+  fine pass         nm_inerf_encode -> nm_linear(_bf16x3) x 12 (nerf/gemm_field.py's FineField) -> nm_inerf_composite, and the mirrored
+                    backward nm_inerf_composite_bwd -> nm_linear(_bf16x3) with transposed weights -> nm_inerf_encode_bwd; under the
+                    split arithmetic the two fused pointwise kernels (FusedField) and nm_nerf_composite4(_bwd) on their (n, 4) rows
   optimiser         torch.optim.Adam on the 4x4 pose (as the reference)
   matching term     (`use_match_loss`, :420-441) nm_inerf_composite (weights) -> nm_inerf_ray_sums (pt_feat, points) ->
                     matcher.match_loss (the training kernels of the matcher under torch.autograd.Function, parameters frozen:
@@ -26,79 +27,10 @@ import torch
 
 from . import ops
 from ._lib import check, dptr, lib, steady_gc, stream
+from .nerf.gemm_field import XD, XI, FineField, _new, composite, composite_bwd
 
 NUM_PTS = 128  # hard-coded by the reference (:354, :360)
-XI, XD = 96, 48
 F32_EPS = float(torch.finfo(torch.float32).eps)
-
-
-def _new(*shape, dev):
-    return torch.empty(*shape, device=dev, dtype=torch.float32)
-
-
-class FineField:
-    """nerf_fine as padded GEMM operands: forward weights and their transposes (for the backward GEMMs), cached per
-    renderer.  Layers with a concatenated input are split into two GEMMs joined through the `pre` addend of nm_linear:
-    layer 5 = relu(xi . W5x^T + h4 . W5h^T + b), views = relu(feature . Wvf^T + xd . Wvd^T + b); xi has 96 columns
-    (90 IPE + padding), xd 48 (27 dir PE + 16 appearance + padding); the density / rgb heads are padded to 8 outputs.
-    The ReLU derivatives of the backward pass are the `gate` of the same epilogue (no elementwise passes)."""
-
-    def __init__(self, nerf_fine, dev):
-        sd = {k: v.detach().to(dev, torch.float32) for k, v in nerf_fine.state_dict().items()}
-        z = lambda *s: torch.zeros(*s, device=dev)
-
-        def padded(w, cols):
-            out = z(w.shape[0], cols)
-            out[:, : w.shape[1]] = w
-            return out.contiguous()
-
-        W = [sd[f"pts_linears.{l}.weight"].contiguous() for l in range(8)]
-        self.b = [sd[f"pts_linears.{l}.bias"].contiguous() for l in range(8)]
-        self.W5x, W[5] = padded(W[5][:, :90], XI), W[5][:, 90:].contiguous()
-        W[0] = padded(W[0], XI)
-        self.W = W
-        self.Wa, self.ba = z(8, 256), z(8)
-        self.Wa[:1] = sd["alpha_linear.weight"]
-        self.ba[:1] = sd["alpha_linear.bias"]
-        self.Wf, self.bf = sd["feature_linear.weight"].contiguous(), sd["feature_linear.bias"].contiguous()
-        wv = sd["views_linears.0.weight"]  # (128, 256 + 27 [+ 16])
-        self.Wvf, self.Wvd, self.bv = wv[:, :256].contiguous(), padded(wv[:, 256:], XD), sd["views_linears.0.bias"].contiguous()
-        self.Wr, self.br = z(8, 128), z(8)
-        self.Wr[:3] = sd["rgb_linear.weight"]
-        self.br[:3] = sd["rgb_linear.bias"]
-        t = lambda w: w.t().contiguous()
-        self.WT = [t(w) for w in W]
-        self.W5xT, self.WaT, self.WfT, self.WvfT, self.WvdT, self.WrT = t(self.W5x), t(self.Wa), t(self.Wf), t(self.Wvf), t(self.Wvd), t(self.Wr)
-
-    def forward(self, xi, xd):
-        """xi (n,96), xd (n,48) -> rgb logits (n,8), raw sigma (n,8) (columns 0..2 / 0), saved activations."""
-        lin = ops.linear
-        h = [lin(xi, self.W[0], self.b[0], act=1)]
-        for l in range(1, 8):
-            h.append(lin(h[-1], self.W[l], self.b[l], act=1, pre=lin(xi, self.W5x) if l == 5 else None))
-        sig = lin(h[7], self.Wa, self.ba)
-        feat = lin(h[7], self.Wf, self.bf)
-        hv = lin(feat, self.Wvf, self.bv, act=1, pre=lin(xd, self.Wvd))
-        logit = lin(hv, self.Wr, self.br)
-        return logit, sig, (h, hv)
-
-    def backward(self, g_logit, g_sig, saved, g_h=None):
-        """d loss / d logits, d loss / d sigma -> d loss / d xi (n,96), d loss / d xd (n,48).  g_h = (layer, d loss / d h[layer])
-        adds a gradient arriving at one layer's (post-ReLU) activations from outside the network: the tapped features."""
-        lin = ops.linear
-        h, hv = saved
-        tap, g_tap = g_h if g_h is not None else (-1, None)
-        g_hv = lin(g_logit, self.WrT, gate=hv)
-        g_xd = lin(g_hv, self.WvdT)
-        g_sig_h = lin(g_sig, self.WaT, residual=g_tap if tap == 7 else None)
-        g = lin(lin(g_hv, self.WvfT), self.WfT, residual=g_sig_h, gate=h[7])
-        g_xi_skip = None
-        for l in range(7, 0, -1):
-            if l == 5:
-                g_xi_skip = lin(g, self.W5xT)
-            g = lin(g, self.WT[l], residual=g_tap if tap == l - 1 else None, gate=h[l - 1])
-        g_xi = lin(g, self.WT[0], residual=g_xi_skip)
-        return g_xi, g_xd
 
 
 class FusedField:
@@ -198,25 +130,6 @@ def _composite_bwd(logit, sig, z, rays, S_act, G, g_w=None):
     check(lib().nm_inerf_composite_bwd(dptr(logit), dptr(sig), logit.shape[1], dptr(z), dptr(rays), dptr(G), dptr(g_w), R, S,
                                        S_act, dptr(g_logit), dptr(g_sig), dptr(g_d), stream()), "nm_inerf_composite_bwd")
     return g_logit, g_sig, g_d
-
-
-def _composite4(out4, z, rays, S_act, want_weights=False):
-    """_composite on the fused field's own output rows (n, 4) = rgb logits | raw sigma: one wavefront per ray (nm_inerf_composite4)."""
-    R, S = z.shape[0], z.shape[1] - 1
-    rgb = _new(R, 3, dev=rays.device)
-    w = _new(R, S_act, dev=rays.device) if want_weights else None
-    check(lib().nm_inerf_composite4(dptr(out4), dptr(z), dptr(rays), R, S, S_act, dptr(rgb), dptr(w), stream()), "nm_inerf_composite4")
-    return (rgb, w) if want_weights else rgb
-
-
-def _composite4_bwd(out4, z, rays, S_act, G, g_w=None):
-    """-> g4 (n, 4) = d loss / d (logits, sigma), g_d (R, 3)."""
-    R, S = z.shape[0], z.shape[1] - 1
-    g4, g_d = torch.empty_like(out4), _new(R, 3, dev=rays.device)
-    G = G.contiguous()
-    check(lib().nm_inerf_composite4_bwd(dptr(out4), dptr(z), dptr(rays), dptr(G), dptr(g_w), R, S, S_act, dptr(g4), dptr(g_d), stream()),
-          "nm_inerf_composite4_bwd")
-    return g4, g_d
 
 
 def _ray_sums(w, feats, rays, z, S_act):
@@ -321,7 +234,7 @@ def step_gradient(renderer, pose, K, H, W, img_ds, t_rand, jitter, ds=8, skip_ze
             out4, gates, feats = field.forward_rays(rays, t_f, S_act, app_row, tap)
         else:
             out4, gates = field.forward_rays(rays, t_f, S_act, app_row)
-        rgb_map, weights = _composite4(out4, t_f, rays, S_act, want_weights=True)  # (n, 4) = rgb logits | raw sigma, composited as they lie
+        rgb_map, _, _, weights = composite(out4, t_f, rays, white_bg=True, S_act=S_act, depth_acc=False)  # (n, 4) = rgb logits | raw sigma, composited as they lie
     else:
         field = fine_field(renderer, dev)
         xi, xd = _encode(rays, t_f, S_act, app_row)
@@ -342,7 +255,7 @@ def step_gradient(renderer, pose, K, H, W, img_ds, t_rand, jitter, ds=8, skip_ze
     # backward
     G = diff * (2.0 / diff.numel())
     if fused:
-        g4, g_d = _composite4_bwd(out4, t_f, rays, S_act, G, g_w)  # (n, 4) = d loss / d (logits, sigma)
+        g4, g_d = composite_bwd(out4, t_f, rays, G, g_w, white_bg=True, S_act=S_act, want_g_d=True)  # (n, 4) = d loss / d (logits, sigma)
         g_xi, g_xd = field.backward(g4, gates, g_h)
     else:
         g_logit, g_sig, g_d = _composite_bwd(logit, sig, t_f, rays, S_act, G, g_w)

@@ -220,7 +220,7 @@ class NeRF(nn.Module):
         when negative).  The render path never comes through here (it uses the fused kernel); callers that reach into the
         network directly (the reference's iNeRF loop, nerfmatch_evaluator.py:402-406) get the same numbers from a chain of
         the HIP GEMM kernels (nm_linear; the skip and view inputs enter as `pre` addends instead of concatenations)."""
-        from ...inerf import XD, XI, FineField  # GEMM-chain packing of one MLP (shared with the iNeRF refinement)
+        from ..gemm_field import XD, XI, FineField  # GEMM-chain packing of one MLP (shared with the iNeRF refinement)
 
         lead = x.shape[:-1]
         x2 = x.reshape(-1, x.shape[-1]).to(torch.float32)

@@ -6,11 +6,11 @@ One coarse -> fine render with gradients towards the parameters of both networks
   sampling    ops.sample_coarse, ops.resample on the coarse pass's (noisy) compositing weights -- as at inference, no gradient
               (render_utils.py:299-310, :581-597: randomized, under no_grad, stop_grad)
   encoding    nm_nerf_train_encode: xi (n,96) | xd (n,48) with the appearance row of every ray's own id (renderer.py:225)
-  MLP         the GEMM chain of inerf.FineField on the live parameters: forward through ops.linear (`pre` joins the skip / view inputs),
+  MLP         the GEMM chain of gemm_field.FineField on the live parameters: forward through ops.linear (`pre` joins the skip / view inputs),
               dX through ops.linear on the transposed weights with the `gate` epilogue, dW and db through ops.linear_wgrad_bias, in the
               arithmetic ops.LINEAR_PRECISION selects.  The weight gradients of the two layers with a concatenated input are two GEMMs
               written into the column blocks of the reference-shaped gradient; padded columns / head rows are dropped
-  per ray     nm_nerf_train_composite(_bwd) (density noise, either background), nm_nerf_distortion(_bwd), nm_nerf_photo_loss,
+  per ray     nm_nerf_composite4(_bwd) (gemm_field.composite: density noise, either background), nm_nerf_distortion(_bwd), nm_nerf_photo_loss,
               nm_nerf_app_grad (fixed summation order)
 Rays are processed in chunks whose saved activations stay below `chunk_bytes`; weight gradients accumulate over the chunks."""
 import ctypes as C
@@ -20,15 +20,10 @@ import torch.nn.functional as F
 
 from .. import ops
 from .._lib import check, dptr, lib, stream
-from ..inerf import FineField
+from .gemm_field import XD, XI, FineField, _new, composite, composite_bwd
 
-XI, XD = 96, 48
 SAVED_FLOATS = XI + XD + 8 * 256 + 256 + 128  # per sample: the inputs, the eight hidden layers, the feature and the views layer
 HEAD = ("alpha_linear", "feature_linear", "views_linears.0", "rgb_linear")
-
-
-def _new(*shape, dev):
-    return torch.empty(*shape, device=dev, dtype=torch.float32)
 
 
 def net_parameters(net):
@@ -54,25 +49,6 @@ def encode(rays, t, ray_id=None, table=None, var_scale=-1.0, status=None, ray_id
     check(lib().nm_nerf_train_encode(dptr(rays), dptr(t), R, S, dptr(ray_id, torch.int64), hp, dptr(table), V, float(var_scale), dptr(xi), dptr(xd),
                                      dptr(status, torch.int32), stream()), "nm_nerf_train_encode")
     return xi, xd
-
-
-def composite(out4, t, rays, noise=None, noise_std=0.0, white_bg=False):
-    """-> rgb (R,3), depth (R), acc (R), weights (R,S)."""
-    R, S, dev = t.shape[0], t.shape[1] - 1, t.device
-    rgb, depth, acc, w = _new(R, 3, dev=dev), _new(R, dev=dev), _new(R, dev=dev), _new(R, S, dev=dev)
-    check(lib().nm_nerf_train_composite(dptr(out4), dptr(t), dptr(rays), dptr(noise), float(noise_std), int(bool(white_bg)), R, S, dptr(rgb),
-                                        dptr(depth), dptr(acc), dptr(w), stream()), "nm_nerf_train_composite")
-    return rgb, depth, acc, w
-
-
-def composite_bwd(out4, t, rays, g_rgb, g_weights=None, noise=None, noise_std=0.0, white_bg=False):
-    R, S = t.shape[0], t.shape[1] - 1
-    g4 = torch.empty_like(out4)
-    g_rgb = g_rgb.contiguous()
-    g_weights = None if g_weights is None else g_weights.contiguous()
-    check(lib().nm_nerf_train_composite_bwd(dptr(out4), dptr(t), dptr(rays), dptr(noise), float(noise_std), int(bool(white_bg)), dptr(g_rgb),
-                                            dptr(g_weights), R, S, dptr(g4), stream()), "nm_nerf_train_composite_bwd")
-    return g4
 
 
 def _distortion(t, t_is_s, weights, want_mean=True):
@@ -163,7 +139,7 @@ def training_metrics(preds, rgb_gt, mask_loss=None, cnfg_loss=None):
 
 # ---- the MLP as a GEMM chain on the live parameters ----------------------------------------------------------------------------------------
 class _Params:
-    """state_dict() of one NeRF from its 24 parameter tensors (net_parameters order): what inerf.FineField packs its operands from"""
+    """state_dict() of one NeRF from its 24 parameter tensors (net_parameters order): what FineField packs its operands from"""
 
     def __init__(self, P):
         names = [f"pts_linears.{l}.{k}" for l in range(8) for k in ("weight", "bias")] + [f"{m}.{k}" for m in HEAD for k in ("weight", "bias")]
@@ -174,7 +150,7 @@ class _Params:
 
 
 class Chain(FineField):
-    """inerf.FineField (the padded GEMM operands of one NeRF and their transposes) on the CURRENT values of the network's 24 parameters
+    """FineField (the padded GEMM operands of one NeRF and their transposes) on the CURRENT values of the network's 24 parameters
     (net_parameters order, detached; built once per step), with a forward pass that also keeps the feature layer and a backward pass that
     adds the weight / bias gradients of a chunk of samples into `grads`."""
 
@@ -183,15 +159,8 @@ class Chain(FineField):
         self.app = P[20].shape[1] - 283
 
     def forward(self, xi, xd):
-        """-> out4 (n,4) = rgb logits | raw sigma, saved activations (FineField.forward's layer sequence)."""
-        lin = ops.linear
-        h = [lin(xi, self.W[0], self.b[0], act=1)]
-        for l in range(1, 8):
-            h.append(lin(h[-1], self.W[l], self.b[l], act=1, pre=lin(xi, self.W5x) if l == 5 else None))
-        sig = lin(h[7], self.Wa, self.ba)
-        feat = lin(h[7], self.Wf, self.bf)
-        hv = lin(feat, self.Wvf, self.bv, act=1, pre=lin(xd, self.Wvd))
-        logit = lin(hv, self.Wr, self.br)
+        """-> out4 (n,4) = rgb logits | raw sigma, saved activations."""
+        logit, sig, h, feat, hv = self.layers(xi, xd)
         return torch.cat([logit[:, :3], sig[:, :1]], 1), (xi, xd, h, feat, hv)
 
     @staticmethod

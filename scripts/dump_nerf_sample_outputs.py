@@ -10,7 +10,7 @@ Entry points and shapes:
     S = 64, a Cambridge-style network with its appearance row;
   nm_inerf_encode, nm_nerf_points_fwd_rays_bf16x3 / nm_nerf_points_bwd_tap_bf16x3: the cases of test_tapped_points_kernels_vs_gemm_chain;
   nm_inerf_encode_bwd / _bwd2: the shapes of test_encode_backward_vs_fp64_sums;
-  nm_inerf_composite / composite4 and their backwards: the shapes of test_wavefront_compositing_vs_per_ray_loops.
+  nm_inerf_composite / nm_nerf_composite4 and their backwards: the shapes of test_wavefront_compositing_vs_per_ray_loops.
 """
 import sys
 from pathlib import Path
@@ -105,8 +105,8 @@ def composite_outputs(dev, out):
         out4 = out4.to(dev).contiguous()
         sig = torch.zeros_like(out4)
         sig[:, 0] = out4[:, 3]
-        rgb4, w4 = inerf._composite4(out4, z, rays, Sa, want_weights=True)
-        g4, gd4 = inerf._composite4_bwd(out4, z, rays, Sa, G, g_w)
+        rgb4, _, _, w4 = inerf.composite(out4, z, rays, white_bg=True, S_act=Sa, depth_acc=False)
+        g4, gd4 = inerf.composite_bwd(out4, z, rays, G, g_w, white_bg=True, S_act=Sa, want_g_d=True)
         rgb, w = inerf._composite(out4, sig, z, rays, Sa, want_weights=True)
         g_logit, g_sig, gd = inerf._composite_bwd(out4, sig, z, rays, Sa, G, g_w)
         for k, v in dict(rgb4=rgb4, w4=w4, g4=g4, gd4=gd4, rgb=rgb, w=w, g_logit=g_logit, g_sig=g_sig, gd=gd).items():

@@ -26,7 +26,7 @@ def test_every_declared_symbol_is_exported_and_bound(built_lib):
 
 def test_host_only_entry_points(built_lib):
     h = _lib.lib()
-    assert h.nm_abi_version() == _lib.ABI_VERSION == 2  # (the literal: a bump is a conscious edit here too)
+    assert h.nm_abi_version() == _lib.ABI_VERSION == 3  # (the literal: a bump is a conscious edit here too)
     assert h.nm_error_string(0) == b"ok" and b"supported" in h.nm_error_string(2)
     assert h.nm_raygen_count(480, 640, 8) == 4800 and h.nm_raygen_count(480, 480, 8) == 3600
     assert h.nm_nerf_blob_floats() == 611856 and h.nm_nerf_blob_bytes_bf16x3() == 16384 + (143 + 4) * 16384  # 143 K-step slots (feature_linear folded into the views layer) + 4 zero slots of run-ahead padding
@@ -49,5 +49,5 @@ def test_library_of_another_abi_version_is_refused(built_lib, monkeypatch):
 
     monkeypatch.setattr(_lib, "_lib", None)  # (force a fresh load; the loaded handle comes back when the test ends)
     monkeypatch.setattr(_lib, "ABI_VERSION", _lib.ABI_VERSION + 1)
-    with pytest.raises(_lib.NerfmatchAmdError, match="ABI version 2"):
+    with pytest.raises(_lib.NerfmatchAmdError, match="ABI version 3"):
         _lib.lib()

@@ -433,7 +433,7 @@ def test_encode_backward_vs_fp64_sums(gpu, built_lib, R, S, Sa, two):
 
 @pytest.mark.parametrize("R,S,Sa,with_gw", [(50, 64, 33, False), (37, 128, 65, True), (9, 256, 129, True), (4801, 128, 128, False)])
 def test_wavefront_compositing_vs_per_ray_loops(gpu, built_lib, R, S, Sa, with_gw):
-    """nm_inerf_composite4 / _bwd (round 6: one wavefront per ray, prefix product and suffix sum over lanes, the fused field's (n, 4) rows as they
+    """nm_nerf_composite4 / _bwd as the refinement calls them (white background, S_act, g_d; round 6: one wavefront per ray, prefix product and suffix sum over lanes, the fused field's (n, 4) rows as they
     lie) against the sequential one-thread-per-ray kernels (nm_inerf_composite / _bwd, themselves pinned by the step-gradient tests against
     the oracle's autograd): same expression, different association of the products and sums."""
     g = torch.Generator().manual_seed(R + Sa)
@@ -447,8 +447,8 @@ def test_wavefront_compositing_vs_per_ray_loops(gpu, built_lib, R, S, Sa, with_g
     g_w = torch.randn(R, Sa, generator=g) if with_gw else None
     dev = lambda t: None if t is None else t.to(gpu).contiguous()
     out4_d, rays_d, z_d, G_d, gw_d = dev(out4), dev(rays), dev(z), dev(G), dev(g_w)
-    rgb4, w4 = inerf._composite4(out4_d, z_d, rays_d, Sa, want_weights=True)
-    g4, gd4 = inerf._composite4_bwd(out4_d, z_d, rays_d, Sa, G_d, gw_d)
+    rgb4, _, _, w4 = inerf.composite(out4_d, z_d, rays_d, white_bg=True, S_act=Sa, depth_acc=False)
+    g4, gd4 = inerf.composite_bwd(out4_d, z_d, rays_d, G_d, gw_d, white_bg=True, S_act=Sa, want_g_d=True)
     sig = torch.zeros_like(out4_d)
     sig[:, 0] = out4_d[:, 3]
     rgb, w = inerf._composite(out4_d, sig, z_d, rays_d, Sa, want_weights=True)

@@ -129,9 +129,13 @@ def test_argument_validation_without_gpu(built_lib):
     assert h.nm_nerf_train_encode(p, p, 4, 32, null, null, p, 0, -1.0, p, p, null, null) == 1  # a table of zero rows
     ids = torch.tensor([0, 1, 5, 2])
     assert h.nm_nerf_train_encode(p, p, 4, 32, null, C.c_void_p(ids.data_ptr()), p, 5, -1.0, p, p, null, null) == 1  # host ids outside [0, V)
-    assert h.nm_nerf_train_composite(null, null, null, null, 0.0, 0, 4, 32, null, null, null, null, null) == 1
-    assert h.nm_nerf_train_composite(p, p, p, null, 0.0, 0, 4, 2048, p, null, null, null, null) == _lib.NM_ERR_UNSUPPORTED
-    assert h.nm_nerf_train_composite_bwd(p, p, p, null, 0.0, 0, null, null, 4, 32, p, null) == 1
+    assert h.nm_nerf_composite4(null, null, null, null, 0.0, 0, 4, 32, 32, null, null, null, null, null) == 1
+    assert h.nm_nerf_composite4(p, p, p, null, 0.0, 0, 4, 2048, 2048, p, null, null, null, null) == _lib.NM_ERR_UNSUPPORTED
+    assert h.nm_nerf_composite4_bwd(p, p, p, null, 0.0, 0, null, null, 4, 32, 32, p, null, null) == 1
+    assert h.nm_nerf_composite4_bwd(p, p, p, null, 0.0, 0, p, null, 4, 2048, 2048, p, null, null) == _lib.NM_ERR_UNSUPPORTED
+    for bad in (33, 0):  # S_act outside [1, S]
+        assert h.nm_nerf_composite4(p, p, p, null, 0.0, 0, 4, 32, bad, p, null, null, null, null) == 1
+        assert h.nm_nerf_composite4_bwd(p, p, p, null, 0.0, 0, p, null, 4, 32, bad, p, null, null) == 1
     assert h.nm_nerf_distortion_workspace_bytes() >= 8
     assert h.nm_nerf_distortion(p, 0, null, 4, 32, null, p, null, null, null) == 1  # t -> s needs the workspace
     assert h.nm_nerf_distortion(p, 1, p, 4, 32, null, null, null, null, null) == 1  # weights without a place for the loss

@@ -44,7 +44,7 @@ def sorted_t(n, S, g, lo=0.05, hi=1.5):
 @pytest.mark.parametrize("S,white,noisy,with_gw", [(32, False, False, False), (32, True, True, True), (64, True, False, True),
                                                    (64, False, True, False), (128, True, True, False), (128, False, False, True)])
 def test_composite_forward_backward_vs_fp64(gpu, built_lib, S, white, noisy, with_gw):
-    """nm_nerf_train_composite / _bwd against fp64 autograd over the oracle's compositing from the SAME out4 / t / noise; |raw + noise| > 1e-3
+    """nm_nerf_composite4 / _bwd as scene training calls them (every sample, no g_d) against fp64 autograd over the oracle's compositing from the SAME out4 / t / noise; |raw + noise| > 1e-3
     keeps the density gate unambiguous.  Bar: 5e-6 of the largest entry (that of test_wavefront_compositing_vs_per_ray_loops)."""
     from nerfmatch_amd.nerf import train_render as tr
 
@@ -76,6 +76,82 @@ def test_composite_forward_backward_vs_fp64(gpu, built_lib, S, white, noisy, wit
     closed = (out4[:, 3] + (noise.reshape(-1) * std if noisy else 0)) <= 0
     assert closed.any() and not g4[:, 3].cpu()[closed].any() and not g_want[:, 3][closed].any()  # the gate is raw + noise, not raw
     assert all(v < 5e-6 for v in errs.values()), errs
+
+
+# (S, S_act, white_bg, noise, g_weights): half a wavefront, exactly one, one lane into the second chunk, one lane into the third; every option
+# both ways with S_act < S
+MERGED_CASES = [(64, 33, True, True, True), (64, 33, False, False, False), (64, 64, False, True, True), (128, 65, True, False, True),
+                (128, 65, False, True, False), (256, 129, True, True, False), (256, 129, False, False, True), (256, 129, True, False, False)]
+
+
+def _merged_case(S, Sa, white, noisy, with_gw):
+    """inputs of one case and the fp64 autograd reference on the first S_act intervals, the direction taking a gradient too"""
+    g = torch.Generator().manual_seed(1000 * S + 8 * Sa + 4 * white + 2 * noisy + with_gw)
+    out4 = torch.randn(R * Sa, 4, generator=g)
+    out4[:, 3] = out4[:, 3] * 40 + 10
+    noise = torch.randn(R, Sa, generator=g) if noisy else None
+    std = 1.0 if noisy else 0.0
+    eff = out4[:, 3].reshape(R, Sa) + (noise * std if noisy else 0)
+    out4[:, 3] = torch.where((eff.abs() <= 1e-3).reshape(-1), out4[:, 3] + 0.01, out4[:, 3])
+    rays, t = make_rays(R, 5), sorted_t(R, S, g)
+    G, g_w = torch.randn(R, 3, generator=g), (torch.randn(R, Sa, generator=g) if with_gw else None)
+    with torch.enable_grad():
+        o64, d64 = out4.double().requires_grad_(True), rays[:, 3:6].double().requires_grad_(True)
+        raw = o64.reshape(R, Sa, 4)
+        sig = raw[..., 3] + (noise.double() * std if noisy else 0)
+        want = no.composite(torch.cat([torch.sigmoid(raw[..., :3]), sig[..., None]], -1), t[:, : Sa + 1].double(), d64, white)
+        obj = (want[0] * G.double()).sum() + ((want[3] * g_w.double()).sum() if with_gw else 0)
+        g_want, gd_want = torch.autograd.grad(obj, [o64, d64])
+    return dict(out4=out4, noise=noise, std=std, rays=rays, t=t, G=G, g_w=g_w, want=[w.detach() for w in want], g_want=g_want, gd_want=gd_want)
+
+
+@pytest.fixture(scope="module")
+def g_d_bar(gpu, built_lib):
+    """The bar for g_d against fp64: nobody had measured one, so it is the larger of 5e-6 and twice the largest error of the kept
+    one-thread-per-ray nm_inerf_composite_bwd against the same fp64 on the cases it can run (white background, no noise)."""
+    from nerfmatch_amd import inerf
+
+    worst = 0.0
+    for S, Sa, white, noisy, with_gw in MERGED_CASES:
+        if not white or noisy:
+            continue
+        c = _merged_case(S, Sa, white, noisy, with_gw)
+        d = lambda x: None if x is None else x.to(gpu).contiguous()
+        out4 = d(c["out4"])
+        sig = torch.zeros_like(out4)
+        sig[:, 0] = out4[:, 3]
+        _, _, gd = inerf._composite_bwd(out4, sig, d(c["t"]), d(c["rays"]), Sa, d(c["G"]), d(c["g_w"]))
+        e = rel(gd, c["gd_want"])
+        print(f"nm_inerf_composite_bwd S={S} S_act={Sa} g_w={with_gw}: g_d {e:.1e} of the largest entry against fp64")
+        worst = max(worst, e)
+    return max(5e-6, 2 * worst)
+
+
+@pytest.mark.parametrize("S,Sa,white,noisy,with_gw", MERGED_CASES)
+def test_merged_composite_option_combinations_vs_fp64(gpu, built_lib, g_d_bar, S, Sa, white, noisy, with_gw):
+    """nm_nerf_composite4 / _bwd on the combinations neither the refinement nor scene training calls: noise or a black background with
+    S_act < S, g_d with noise and with a black background, depth / acc with S_act < S.  R = 37: nine full workgroups of four rays plus one
+    ray.  Reference: fp64 autograd over the oracle's compositing of the first S_act intervals from the SAME out4 / t / noise, |raw + noise|
+    > 1e-3.  Bars: 5e-6 of the largest entry (that of the two existing compositing tests) for everything they hold to it; g_d: g_d_bar.
+    Measured: the kept per-ray loops' g_d against fp64 1.8e-7 (S_act = 65) and 2.7e-7 (S_act = 129), so g_d_bar = 5e-6; the merged kernel's
+    g_d 1.8e-7 ... 5.4e-7 over the eight cases, everything else 0.5e-7 ... 2.8e-7."""
+    from nerfmatch_amd.nerf import gemm_field as gf
+
+    c = _merged_case(S, Sa, white, noisy, with_gw)
+    d = lambda x: None if x is None else x.to(gpu).contiguous()
+    got = gf.composite(d(c["out4"]), d(c["t"]), d(c["rays"]), d(c["noise"]), c["std"], white, S_act=Sa)
+    g4, g_d = gf.composite_bwd(d(c["out4"]), d(c["t"]), d(c["rays"]), d(c["G"]), d(c["g_w"]), d(c["noise"]), c["std"], white, S_act=Sa, want_g_d=True)
+    errs = {k: rel(a, b) for k, a, b in zip(("rgb", "depth", "acc", "weights"), got, c["want"])}
+    errs["g_logit"], errs["g_sigma"] = rel(g4[:, :3], c["g_want"][:, :3]), rel(g4[:, 3], c["g_want"][:, 3])
+    e_gd = rel(g_d, c["gd_want"])
+    print(f"merged composite S={S} S_act={Sa} white={white} noise={noisy} g_w={with_gw}: " + "  ".join(f"{k} {v:.1e}" for k, v in errs.items())
+          + f"  g_d {e_gd:.1e} (bar {g_d_bar:.1e})")
+    assert got[3].shape == (R, Sa) and g4.shape == (R * Sa, 4)
+    assert float(c["g_want"][:, 3].abs().max()) > 0 and float(c["gd_want"].abs().max()) > 0
+    closed = (c["out4"][:, 3] + (c["noise"].reshape(-1) * c["std"] if noisy else 0)) <= 0
+    assert closed.any() and not g4[:, 3].cpu()[closed].any()  # closed gates: exactly zero
+    assert all(v < 5e-6 for v in errs.values()), errs
+    assert e_gd < g_d_bar, (e_gd, g_d_bar)
 
 
 @pytest.mark.parametrize("S", SS)

@@ -122,7 +122,7 @@ def test_symbol_is_declared_exported_and_bound(built_lib):
         assert re.search(rf"\b{name}\s*\(", txt), f"{name} is not declared in the header"
         assert name in _lib.SIGNATURES and name not in h._nm_missing and getattr(h, name).argtypes == _lib.SIGNATURES[name][1]
     assert len(_lib.SIGNATURES["nm_pnp_ransac"][1]) == 20
-    assert h.nm_abi_version() == 2  # purely additive: the version stays
+    assert h.nm_abi_version() == 3  # (these two were purely additive: no bump of their own; 3 = the merged per-ray compositing pair)
 
 
 def test_recorded_bounds():
