@@ -180,8 +180,13 @@ __device__ __forceinline__ f32x4 reduce_scatter_32rows(float (&v)[128], int lane
 // ds_read of the epilogue, which would then wait for the rows tap_prefetch requests right behind this.
 #define NM_MLP_DONE_WAIT() __builtin_amdgcn_s_waitcnt(0x0070)
 #define NM_EPI_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-template <int P>
+// TAP7: the launch may composite a tap on layer 7 early (tap7_early below; decided per tile at run time).  The fp16x3 kernel exists in both
+// forms and the host picks (nerf_fwd_split): without TAP7 no tile needs its densities in front of the views layer, so the views K-loop
+// adds up the density head as it re-packs layer 7 (DENS; dens_open in nerf_split_chain.h) and alpha_head goes.  Two kernels, not two
+// K-loops behind a branch in one: with both in one kernel the register allocator spilled 148 VGPRs.
+template <int P, bool TAP7 = true>
 __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
+  constexpr bool DENS = P == 2 && !TAP7;
   __shared__ __attribute__((aligned(16))) float sm[LDS_TOTAL];
   float* const sm_small = sm + LDS_SMALL;
   float* const ring = sm + LDS_RING;
@@ -322,7 +327,7 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     cx.vmax = 0.f; cx.rng = sm_rng + tid; cx.sc = 1.f;
     // A tap on layer 7 in a regular tile with colour heads is composited at the end of layer 7, from registers (tap7_early); the
     // per-sample feature output (a debug output) and the leftover pass keep the workspace path.
-    const bool early = need_rgb && !lo_pass && tap == 7 && a.feat && !a.sfeat;
+    const bool early = TAP7 && need_rgb && !lo_pass && tap == 7 && a.feat && !a.sfeat;
     cx.tap_pref = need_tap && !lo_pass && !early; cx.rgb = need_rgb;
     cx.tap_ring = ring + wave * SLOT_FLOATS; cx.tap_ipe = sm_ipe + wave * (XS * 2 * 64 * 4);
     if constexpr (is_split<P>()) {
@@ -449,7 +454,7 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     TRACE(3);
 #pragma unroll 1
     for (int l = 1; l < 8; ++l) {
-      layer_pass<P>(acc, l, cx, ipe_src, tap7);
+      layer_pass<P, DENS>(acc, l, cx, ipe_src, tap7);
       TRACE(3 + l);
     }
     float c_r = 0.f, c_g = 0.f, c_b = 0.f;
@@ -466,7 +471,10 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
       const int hh = launder(lane) >> 5;
       const float* exr = sm_ex + launder(rl) * 48 + 8 * hh;  // K-slot (step e, half h, i) <-> extra input 16 e + 8 h + i
       f32x16 av[4];
-      views_hidden<P>(av, cx);
+      if constexpr (DENS) {
+        views_hidden<P, true>(av, cx);
+        dens_close(cx);
+      } else views_hidden<P>(av, cx);
       fold_range<P>(cx, 7);  // (layer 7's output is re-packed by the views layer's K-loop)
       bf16x8 exh[VS], exl[VS];
 #pragma unroll
@@ -716,7 +724,8 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
 
 __global__ void __launch_bounds__(256, 1) nerf_fwd_bf16x3_kernel(NerfArgs a) { nerf_fwd_body<0>(a); }
 __global__ void __launch_bounds__(256, 1) nerf_fwd_fp16x1_kernel(NerfArgs a) { nerf_fwd_body<1>(a); }
-__global__ void __launch_bounds__(256, 1) nerf_fwd_fp16x3_kernel(NerfArgs a) { nerf_fwd_body<2>(a); }
+__global__ void __launch_bounds__(256, 1) nerf_fwd_fp16x3_kernel(NerfArgs a) { nerf_fwd_body<2, false>(a); }
+__global__ void __launch_bounds__(256, 1) nerf_fwd_fp16x3_tap7_kernel(NerfArgs a) { nerf_fwd_body<2, true>(a); }
 
 }  // namespace
 
@@ -751,7 +760,12 @@ static int nerf_fwd_split(int mode, const void* blob, const float* rays, const f
   const int grid = a.ntiles < ncu ? a.ntiles : (ncu < WS_WORKGROUPS ? ncu : WS_WORKGROUPS);
   // (the two-wavefronts-per-SIMD experiment of round 2, 12 % slower, lives in scripts/variants/ now: DESIGN.md section 3.1c)
   if (mode == 1) nerf_fwd_fp16x1_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
-  else if (mode == 2) nerf_fwd_fp16x3_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  else if (mode == 2) {
+    // (the condition of `early` in nerf_fwd_body, without its per-tile part)
+    const bool tap7_early = !(flags & NM_NERF_SKIP_RGB) && (tap_layer < 0 || tap_layer == 7) && feat && !sample_feat;
+    if (tap7_early) nerf_fwd_fp16x3_tap7_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else nerf_fwd_fp16x3_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  }
   else nerf_fwd_bf16x3_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
   return nm_launch_status();
 }

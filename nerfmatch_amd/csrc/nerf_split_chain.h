@@ -138,6 +138,17 @@ __device__ __forceinline__ void ring_acquire_two() {
   __builtin_amdgcn_s_barrier();
 }
 
+// fp16x3: an LDS wait the COMPILER sees, placed where every outstanding ds_read was issued several MFMAs ago (it costs nothing there).
+// The compiler's own waits in these K-loops are all lgkmcnt(0), put in front of the first MFMA that needs a register it has not waited
+// for yet -- without this one that is an MFMA one or two gaps behind FRESH operand reads, whose whole LDS latency it then sits out
+// (hipcc -S of the parent: a wait right behind the B reads of first-half gaps 0, 1 of every odd K-step and behind the bias reads of
+// every views-layer half).  With the reads of the next K-step's A operands retired here, its waits fall in front of a half's first
+// MFMA, where everything pending is old.  (simm16: vmcnt 63, expcnt 7, lgkmcnt 0)
+template <int P>
+__device__ __forceinline__ void lds_retire() {
+  if constexpr (P == 2) __builtin_amdgcn_s_waitcnt(0xC07F);
+}
+
 // fp16x1, called in every EVEN K-step g: slots g+1 and g+2 have landed when at most the 6 DMA instructions of slots g+3..g+5
 // remain in flight; one barrier for both; then slots g+6 and g+7 are requested into the ring positions of slots g-2 and g-1
 // (every wavefront is past their MFMAs).  Halves the barriers / counted waits per MFMA of a stream whose K-step is 8 MFMAs.
@@ -189,6 +200,9 @@ struct Ctx {
   f32x4 hb0, hb1;   // split modes: biases of unit 0 of the layer being finished, read by its last K-step (AccTake) for finish_layer
   Unit xn;          // B operands of the next hidden K-step
   float sig_part;   // this lane's partial dot product of the density head
+  float dp[4];      // fp16x3, density head accumulated in the views K-loop (UnitWork<2, true>): the four partial sums of alpha_head,
+  float dv[3], dw[3];  //   and the three terms a unit hands to the next one
+  f32x4 nb0, nb1;   // fp16x3: the biases of the NEXT unit to be made, read by the unit in front of it (UnitWork::bias_next; unit 1's by finish_layer)
   float sc;         // fp16x3: s_l of the finished layer in cx.hv (OFF_SCALE), wavefront-uniform -> lives in an SGPR: the re-packing fma
                     // has two VGPR sources like the add it replaces
   float vmax;       // fp16x3: running max |re-packed value| of the layer being consumed (range telemetry / saturation flag)
@@ -227,6 +241,13 @@ __device__ __forceinline__ void ring_request(const Ctx& cx, int g, int j) {
   }
 #undef NM_DMA_PIECE
 }
+// fp16x3, 8-block layers (slot_step8<.., RQE = true>): the ring positions an even K-step g fills are free as soon as the barrier in the
+// middle of odd K-step g-1 has passed, and that K-step's second-half gaps 5-10 carry nothing in this mode.  So pieces 0..5 go there, one
+// per gap, and pieces 6, 7 into first-half gaps 4, 5 of K-step g: the youngest piece is asked for ~31 MFMAs in front of the barrier that
+// waits for it instead of 24, the oldest ~43 instead of 32.  Same pieces, same barrier.  Only for a pair (odd g-1, even g) inside one
+// K-loop: a layer's last K-step fills those gaps with AccTake, and a tile's first K-step has no predecessor -- the K-step behind either
+// keeps all eight pieces; the views layer's seq() leaves no empty gaps either.  The bf16 modes use second-half gaps 5-10 for the re-packing.
+template <int P> constexpr bool request_early() { return P == 2; }
 // Opens a tile's weight stream: the slots K-step 0 does not request itself
 template <int P>
 __device__ __forceinline__ void ring_open(const char* blob_slots, float* ring, int wave, int lane) {
@@ -298,6 +319,12 @@ __device__ __forceinline__ unsigned gate_byte(const u32x4& h) {
 //   second 9   | -                        | lo(3)              | lo(0) rem(1) rem(2)      | rem(1) hi(2)
 //   second 10  | -                        | (P = 4: gates)     | lo(1) lo(2) rem(3)       | rem(2) hi(3)
 //   second 11  | -                        | -                  | lo(3)                    | rem(3) lo(0..3) (P = 4: + gates)
+// fp16x3 reads a unit's biases one unit ahead (UnitWork::bias_next: second-half gap 11, views layer gap 11 of the half, behind lds_retire), so
+// "bias" in its columns is a register copy and gap 11 carries two reads.
+// fp16x3, K-steps 1 .. 14 of a hidden K-loop and 1 .. 4 of an IPE group (request_early): the odd K-step's second-half gaps 5-10 carry DMA
+// pieces 0-5 of the NEXT even K-step's request, whose first-half gaps 4, 5 keep pieces 6, 7 and whose gaps 6-11 are empty; an IPE K-step
+// also fetches the next one's two B operands (IpeFetch: first-half gap 6 / 4, the group's first K-step second-half gap 5).  Views layer,
+// fp16x3 without an early tap: seq() with the density head's terms (UnitWork::dens_seq) -- gap 0 holds four reads and nothing else.
 // The last B read has 8 MFMAs in front of the second half, the last A' read 7 in front of the next K-step; the A' reads of an odd K-step
 // stay behind its barrier.  The second half of an even K-step is the "compact sequence" seq(0..11) (unit_seq), which the views layer's
 // forms use as well.  Gaps that stay over the budget, and why:
@@ -311,7 +338,8 @@ __device__ __forceinline__ unsigned gate_byte(const u32x4& h) {
 //     24 gaps hold under (a)-(c) -- the DMA pieces share gaps 4..11 of the first half with seq(); five such K-steps per tile.
 template <bool BF, class W> __device__ __forceinline__ void unit_seq(W& w, int c);
 template <bool EVEN, bool BF, class W> __device__ __forceinline__ void unit_step8(W& w, int t);
-template <int P>
+// DENS (fp16x3, the views layer's units of layer 7): the unit also adds its eight terms to the density head's dot product (dens_seq)
+template <int P, bool DENS = false>
 struct UnitWork {
   Ctx& cx;
   Unit& out;
@@ -322,10 +350,53 @@ struct UnitWork {
   float v8[8];
   float f0, f1;              // bf16 modes: fp32 values of the current pair's hi halves
   float r0[4], r1[4];        // remainders of pair p, rem(p) -> lo(p)
+  f32x4 wa0, wa1;            // DENS: the density vector's entries of elements 0..3 / 4..7
+  // DENS: p_j += v8[j] w[j], then p_j += v8[4 + j] w'[j], units ascending -- alpha_head's own order of summation, so cx.sig_part keeps its
+  // bits (v8 is med3(fma(hv, s, b), 0, F16_MAX) where alpha_head takes max(.., 0): the same value unless the launch raises the saturation
+  // flag and is redone in fp32).  In the compact sequence: the two reads in gap 0; one term where a gap has an issue slot left
+  // and its input was pinned in an EARLIER gap (no wait state), no two terms of one p_j in a gap; the last three terms do not fit and are
+  // handed to the next unit's gap 1 (cx.dv, cx.dw), the last unit's to DensTail.  Volatile asm: placed where written, like rem().
+  __device__ __forceinline__ static void dens_fma(float& p, float v, float w) { asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(p) : "v"(v), "v"(w)); }
+  __device__ __forceinline__ void dens_seq(int c) {
+    if constexpr (DENS) {
+      switch (c) {
+        case 0: {
+          const float* wl = cx.sm_small + OFF_WALPHA + (u >> 1) * 32 + 16 * (u & 1) + 4 * cx.hi;
+          wa0 = *reinterpret_cast<const f32x4*>(wl); wa1 = *reinterpret_cast<const f32x4*>(wl + 8);
+        } break;
+        case 1:  // (the previous unit's last three)
+          dens_fma(cx.dp[1], cx.dv[0], cx.dw[0]); dens_fma(cx.dp[2], cx.dv[1], cx.dw[1]); dens_fma(cx.dp[3], cx.dv[2], cx.dw[2]);
+          break;
+        case 7: dens_fma(cx.dp[0], v8[0], wa0[0]); break;  // (first use of the two reads: the operand reads of gaps 1-4 are old by now)
+        case 10: dens_fma(cx.dp[0], v8[4], wa1[0]); break;
+        case 11:
+          dens_fma(cx.dp[1], v8[1], wa0[1]); dens_fma(cx.dp[2], v8[2], wa0[2]); dens_fma(cx.dp[3], v8[3], wa0[3]);
+          cx.dv[0] = v8[5]; cx.dw[0] = wa1[1]; cx.dv[1] = v8[6]; cx.dw[1] = wa1[2]; cx.dv[2] = v8[7]; cx.dw[2] = wa1[3];
+          break;
+        default: break;
+      }
+    }
+  }
   __device__ __forceinline__ void bias() {
+    if constexpr (P == 2) {  // (read a unit ahead: bias_next)
+      b0 = cx.nb0; b1 = cx.nb1;
+      return;
+    }
     const int ob = u >> 1, m = u & 1;
     const float* bl = cx.sm_small + OFF_BIAS + lo_ * 256 + ob * 32 + 16 * m + 4 * cx.hi;
     b0 = *reinterpret_cast<const f32x4*>(bl); b1 = *reinterpret_cast<const f32x4*>(bl + 8);
+  }
+  // fp16x3: the two bias reads of unit u + 1, in the LAST gap of the half that makes unit u, behind lds_retire.  Read in the unit's own
+  // first gap they were first used two gaps on, and the compiler's wait there (always lgkmcnt(0)) also sat out the operand reads issued
+  // in between.  From here they are several MFMAs old at the next wait the compiler places (in front of a half's first MFMA).
+  __device__ __forceinline__ void bias_next() {
+    if constexpr (P == 2) {
+      if (u + 1 < HS) {
+        const int ob = (u + 1) >> 1, m = (u + 1) & 1;
+        const float* bl = cx.sm_small + OFF_BIAS + lo_ * 256 + ob * 32 + 16 * m + 4 * cx.hi;
+        cx.nb0 = *reinterpret_cast<const f32x4*>(bl); cx.nb1 = *reinterpret_cast<const f32x4*>(bl + 8);
+      }
+    }
   }
   // element e = j or 4 + j of the unit: accumulator + bias (fp16x3: accumulator x next layer's input scale + bias, exact), relu
   __device__ __forceinline__ float act(int e, float b) const {
@@ -383,8 +454,14 @@ struct UnitWork {
       cx.gbits[u >> 2] |= t << (8 * (u & 3));
     }
   }
-  __device__ __forceinline__ void seq(int c) { unit_seq<is_bf16<P>()>(*this, c); }
-  template <bool EVEN> __device__ __forceinline__ void step8(int t) { unit_step8<EVEN, is_bf16<P>()>(*this, t); }
+  __device__ __forceinline__ void seq(int c) {
+    unit_seq<is_bf16<P>()>(*this, c); dens_seq(c);
+    if (c == 11) bias_next();
+  }
+  template <bool EVEN> __device__ __forceinline__ void step8(int t) {
+    unit_step8<EVEN, is_bf16<P>()>(*this, t);
+    if (t == 23) bias_next();
+  }
   // fp16x1 (slot_step8_one / slot_step4_one) and finish_layer: the unit in 12 pieces, in order
   __device__ __forceinline__ void prefetch() { bias(); }
   __device__ __forceinline__ void operator()(int j) {
@@ -465,6 +542,19 @@ struct NoWork {
   __device__ __forceinline__ void seq(int) {}
   template <bool EVEN> __device__ __forceinline__ void step8(int) {}
 };
+// fp16x3, the work of an IPE K-step (ipe_steps): the B operands of IPE K-step m (hi, lo: two LDS reads) in gap T of an 8-block K-step
+template <int T>
+struct IpeFetch {
+  const float* src;
+  int m;
+  bf16x8& ph;
+  bf16x8& pl;
+  template <bool EVEN> __device__ __forceinline__ void step8(int t) {
+    if (t != T) return;
+    ph = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(src + (m * 2 + 0) * 256));
+    pl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(src + (m * 2 + 1) * 256));
+  }
+};
 // The work of the LAST K-step of layer l (which re-packs nothing: all 16 units of the previous layer exist, cx.hv is dead): blocks 0..3 of the
 // layer being finished are final once that K-step's first half is through, so their accumulator reads (v_accvgpr_read) go behind the MFMAs
 // of its second half instead of in front of the next layer.  Split modes: as many per gap as the per-gap schedule allows (take_n; gap 0 one less: the compiler pads the first read behind the MFMAs with an s_nop), 47 of the
@@ -506,9 +596,9 @@ struct AccTake {
     }
   }
 };
-template <int P>
-__device__ __forceinline__ UnitWork<P> unit_work(int u, int lo, Ctx& cx, Unit& out) {
-  return UnitWork<P>{cx, out, u, lo, lo < 8 ? 0.f : (!is_bf16<P>() ? -F16_MAX : -__builtin_inff()), {}, {}, cx.sc, {}, 0.f, 0.f, {}, {}};
+template <int P, bool DENS = false>
+__device__ __forceinline__ UnitWork<P, DENS> unit_work(int u, int lo, Ctx& cx, Unit& out) {
+  return UnitWork<P, DENS>{cx, out, u, lo, lo < 8 ? 0.f : (!is_bf16<P>() ? -F16_MAX : -__builtin_inff()), {}, {}, cx.sc, {}, 0.f, 0.f, {}, {}, {}, {}};
 }
 
 // End of layer l: move the rest of the accumulators out of the AGPRs (the next layer starts from C = 0 in the same registers) and
@@ -526,6 +616,10 @@ __device__ __forceinline__ void finish_layer(const f32x16 (&acc)[8], int l, Ctx&
   if constexpr (P == 2)
     cx.sc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, cx.sm_small[OFF_SCALE + l])));
   UnitWork<P> w = unit_work<P>(0, l, cx, cx.xn);
+  if constexpr (P == 2) {  // unit 1's biases for K-step 0 of the layer's consumer (UnitWork::bias_next reads the others)
+    const float* bl = unit0_bias(cx, l) + 16;
+    cx.nb0 = *reinterpret_cast<const f32x4*>(bl); cx.nb1 = *reinterpret_cast<const f32x4*>(bl + 8);
+  }
   if constexpr (is_split<P>()) {  // (hi, rem and lo of a pair apart: see UnitWork)
     w.b0 = cx.hb0; w.b1 = cx.hb1;  // (read by AccTake)
 #pragma unroll
@@ -570,6 +664,39 @@ __device__ __forceinline__ void alpha_head(Ctx& cx) {
     }
   cx.sig_part = (p0 + p1) + (p2 + p3);
 }
+
+// fp16x3, a pass with colour heads whose tap is not composited in front of the views layer: the views K-loop re-packs layer 7 unit by
+// unit, i.e. makes relu(fma(hv, s_7, b_7)) a second time -- its units add their terms to the dot product as they go (UnitWork<2, true>)
+// and alpha_head's 128 x 3 VALU + 64 LDS reads with the matrix pipe idle go.  dens_open: unit 0's terms (finish_layer made unit 0; its
+// last three are handed on like every unit's); DensTail: the last unit's three, in the empty second half of the last hidden slot;
+// dens_close: alpha_head's final sum.
+__device__ __forceinline__ void dens_open(Ctx& cx) {
+  const float* bl = cx.sm_small + OFF_BIAS + 7 * 256 + 4 * cx.hi;
+  const float* wa = cx.sm_small + OFF_WALPHA + 4 * cx.hi;
+  const f32x4 b0 = *reinterpret_cast<const f32x4*>(bl), b1 = *reinterpret_cast<const f32x4*>(bl + 8);
+  const f32x4 w0 = *reinterpret_cast<const f32x4*>(wa), w1 = *reinterpret_cast<const f32x4*>(wa + 8);
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[j] = __builtin_fmaxf(__builtin_fmaf(cx.hv[j], cx.sc, b0[j]), 0.f);
+    v[4 + j] = __builtin_fmaxf(__builtin_fmaf(cx.hv[4 + j], cx.sc, b1[j]), 0.f);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cx.dp[j] = NM_FMA(v[j], w0[j], 0.f);
+  cx.dp[0] = NM_FMA(v[4], w1[0], cx.dp[0]);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { cx.dv[j] = v[5 + j]; cx.dw[j] = w1[1 + j]; }
+}
+struct DensTail {
+  Ctx& cx;
+  __device__ __forceinline__ void seq(int c) {
+    if (c == 1) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) UnitWork<2, true>::dens_fma(cx.dp[1 + j], cx.dv[j], cx.dw[j]);
+    }
+  }
+};
+__device__ __forceinline__ void dens_close(Ctx& cx) { cx.sig_part = (cx.dp[0] + cx.dp[1]) + (cx.dp[2] + cx.dp[3]); }
 
 // Tapped activations (fp32, after bias and relu) of the finished layer lo -> L2-resident workspace, 1 KiB per store.
 // Once per tile and not hidden behind MFMAs (~2k cycles).
@@ -653,7 +780,7 @@ __device__ __forceinline__ f32x16 mfma_k(int k, const OpHalf& a, const bf16x8& x
 // 1-4 of the second; the DMA pieces alone in gaps 4-11 of the first half; work.step8<EVEN>(t) says what the work does in gap t.
 // (EVEN: the K-step's position in the weight stream is even -- every layer holds an even number of K-steps, so the callers know)
 // (the next slot's operands are read unconditionally: past the last slot they are stale ring contents nobody uses)
-template <int P, bool FIRST, bool EVEN, class Work>
+template <int P, bool FIRST, bool EVEN, bool RQE = false, class Work>
 __device__ __forceinline__ void slot_step8(f32x16 (&acc)[8], Ctx& cx, const bf16x8& xh, const bf16x8& xl, Work work) {
   if constexpr (P == 1) {
     slot_step8_one<FIRST, EVEN>(acc, cx, xh, work);
@@ -669,8 +796,11 @@ __device__ __forceinline__ void slot_step8(f32x16 (&acc)[8], Ctx& cx, const bf16
     acc[k & 3] = mfma_k<P, FIRST>(k, A, xh, xl, acc[k & 3]);
     __builtin_amdgcn_sched_barrier(0);
     if (k < 4) load_pair<P>(B, cur, cx.lane, 1, k);
-    if constexpr (EVEN) {
+    if constexpr (EVEN && !RQE) {
       if (k >= 4) ring_request<P>(cx, g, k - 4);
+    }
+    if constexpr (EVEN && RQE) {  // (pieces 0..5: the previous K-step, behind its barrier)
+      if (k == 4 || k == 5) ring_request<P>(cx, g, k + 2);
     }
     work.template step8<EVEN>(k);
     __builtin_amdgcn_sched_barrier(0);
@@ -685,6 +815,10 @@ __device__ __forceinline__ void slot_step8(f32x16 (&acc)[8], Ctx& cx, const bf16
     acc[4 + (k & 3)] = mfma_k<P, FIRST>(k, B, xh, xl, acc[4 + (k & 3)]);
     __builtin_amdgcn_sched_barrier(0);
     if (k >= 1 && k <= 4) load_pair<P>(cx.opA, nxt, cx.lane, 0, k - 1);
+    if constexpr (!EVEN && RQE) {
+      if (k >= 5 && k <= 10) ring_request<P>(cx, g + 1, k - 5);
+    }
+    if (k == 11) lds_retire<P>();  // (the next slot's A operands: read in gaps 1-4; in front of the work: its bias_next reads stay in flight)
     work.template step8<EVEN>(12 + k);
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -762,6 +896,7 @@ __device__ __forceinline__ void slot_step4x2(f32x16 (&av)[4], Ctx& cx, const bf1
     if constexpr (EVEN) {
       if (k >= 4) ring_request<P>(cx, g, k - 4);
     }
+    if (k == 11) lds_retire<P>();  // (the second K-step's operands: read in gaps 1-4)
     w0.seq(k);
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -776,6 +911,7 @@ __device__ __forceinline__ void slot_step4x2(f32x16 (&av)[4], Ctx& cx, const bf1
     av[k & 3] = mfma_k<P, false>(k, B, x1h, x1l, av[k & 3]);
     __builtin_amdgcn_sched_barrier(0);
     if (k >= 1 && k <= 4) load_pair<P>(cx.opA, nxt, cx.lane, 0, k - 1);
+    if (k == 11) lds_retire<P>();
     w1.seq(k);
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -783,8 +919,10 @@ __device__ __forceinline__ void slot_step4x2(f32x16 (&av)[4], Ctx& cx, const bf1
 }
 
 // The hidden part of the views layer: layer 7's sixteen units (unit 0 in cx.xn) against the folded 128 x 256 matrix
-template <int P>
+// (DENS: fp16x3 only, the density head rides along -- see dens_open)
+template <int P, bool DENS = false>
 __device__ __forceinline__ void views_hidden(f32x16 (&av)[4], Ctx& cx) {
+  static_assert(!DENS || P == 2, "the density head accumulates in the views K-loop in fp16x3 only");
   if constexpr (is_split<P>()) {
 #pragma unroll
     for (int sl = 0; sl < HS / 2; ++sl) {
@@ -792,10 +930,12 @@ __device__ __forceinline__ void views_hidden(f32x16 (&av)[4], Ctx& cx) {
       Unit u1;
       const bf16x8 x0h = __builtin_bit_cast(bf16x8, x0.h), x0l = __builtin_bit_cast(bf16x8, x0.l);
       // (NSLOT_NORGB is even: slot sl of the views layer sits at an even stream position iff sl is even)
-      if (sl == 0) slot_step4x2<P, true, true>(av, cx, x0h, x0l, u1, unit_work<P>(1, 7, cx, u1), unit_work<P>(2, 7, cx, cx.xn));
-      else if (sl + 1 == HS / 2) slot_step4x2<P, false, false>(av, cx, x0h, x0l, u1, unit_work<P>(2 * sl + 1, 7, cx, u1), NoWork{});
-      else if (sl & 1) slot_step4x2<P, false, false>(av, cx, x0h, x0l, u1, unit_work<P>(2 * sl + 1, 7, cx, u1), unit_work<P>(2 * sl + 2, 7, cx, cx.xn));
-      else slot_step4x2<P, false, true>(av, cx, x0h, x0l, u1, unit_work<P>(2 * sl + 1, 7, cx, u1), unit_work<P>(2 * sl + 2, 7, cx, cx.xn));
+      if (sl == 0) slot_step4x2<P, true, true>(av, cx, x0h, x0l, u1, unit_work<P, DENS>(1, 7, cx, u1), unit_work<P, DENS>(2, 7, cx, cx.xn));
+      else if (sl + 1 == HS / 2) {
+        if constexpr (DENS) slot_step4x2<P, false, false>(av, cx, x0h, x0l, u1, unit_work<P, DENS>(2 * sl + 1, 7, cx, u1), DensTail{cx});
+        else slot_step4x2<P, false, false>(av, cx, x0h, x0l, u1, unit_work<P>(2 * sl + 1, 7, cx, u1), NoWork{});
+      } else if (sl & 1) slot_step4x2<P, false, false>(av, cx, x0h, x0l, u1, unit_work<P, DENS>(2 * sl + 1, 7, cx, u1), unit_work<P, DENS>(2 * sl + 2, 7, cx, cx.xn));
+      else slot_step4x2<P, false, true>(av, cx, x0h, x0l, u1, unit_work<P, DENS>(2 * sl + 1, 7, cx, u1), unit_work<P, DENS>(2 * sl + 2, 7, cx, cx.xn));
     }
   } else {
 #pragma unroll
@@ -840,6 +980,21 @@ __device__ __forceinline__ void ipe_steps(f32x16 (&acc)[8], Ctx& cx, const float
     pl = ph;
     if constexpr (is_split<P>()) pl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ipe_src + (m * 2 + 1) * 256));
   };
+  if constexpr (P == 2) {
+    // fp16x3: K-step m + 1's pair is fetched in an empty gap of K-step m (IpeFetch), not in front of its first MFMA, where the LDS latency
+    // was exposed twelve times per tile; only the group's first pair is read up front.  (cx.hv is dead here: the registers are free.)
+    bf16x8 ph, pl, qh, ql;
+    operand(0, ph, pl);
+#pragma unroll
+    for (int m = 0; m < XS; m += 2) {
+      // (gaps: the first K-step of the group carries its eight DMA pieces in the first half, the others pieces 6, 7 in gaps 4, 5)
+      if (m == 0) slot_step8<P, FIRST, true>(acc, cx, ph, pl, IpeFetch<17>{ipe_src, m + 1, qh, ql});
+      else slot_step8<P, false, true, true>(acc, cx, ph, pl, IpeFetch<6>{ipe_src, m + 1, qh, ql});
+      if (m + 2 == XS) slot_step8<P, false, false>(acc, cx, qh, ql, AccTake<P>{acc, cx, l});  // (the IPE steps close layers 0 and 5)
+      else slot_step8<P, false, false, true>(acc, cx, qh, ql, IpeFetch<4>{ipe_src, m + 2, ph, pl});
+    }
+    return;
+  }
 #pragma unroll
   for (int m = 0; m < XS; m += 2) {  // (XS is even; pairs so that the position parity is a template argument)
     bf16x8 ph, pl;
@@ -868,7 +1023,8 @@ struct Tap7InRegisters {
 
 // One pts layer (l = 1..7): unit ks+1 of the finished layer l-1 (in cx.hv) is made in the shadow of K-step ks.
 // (feature_linear is no layer of this kernel: it has no activation, so nerf_pack_split multiplies it into the views layer.)
-template <int P, class Tap7 = Tap7Workspace>
+// (DENS: the caller's views K-loop accumulates the density head -- views_hidden<2, true> -- and this layer only opens the sum)
+template <int P, bool DENS = false, class Tap7 = Tap7Workspace>
 __device__ __forceinline__ void layer_pass(f32x16 (&acc)[8], int l, Ctx& cx, const float* ipe_src, const Tap7& tap7 = Tap7()) {
   if (l - 1 == cx.tap) dump_tap(l - 1, cx);
 #pragma unroll
@@ -876,11 +1032,11 @@ __device__ __forceinline__ void layer_pass(f32x16 (&acc)[8], int l, Ctx& cx, con
     {
       const Unit xc = cx.xn;
       if (ks == 0) slot_step8<P, true, true>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 1, l - 1, cx, cx.xn));
-      else slot_step8<P, false, true>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 1, l - 1, cx, cx.xn));
+      else slot_step8<P, false, true, request_early<P>()>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 1, l - 1, cx, cx.xn));
     }
     {
       const Unit xc = cx.xn;
-      if (ks + 2 < HS) slot_step8<P, false, false>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 2, l - 1, cx, cx.xn));
+      if (ks + 2 < HS) slot_step8<P, false, false, request_early<P>()>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), unit_work<P>(ks + 2, l - 1, cx, cx.xn));
       // (every layer, no branch in the MFMA stream: in layer 5 the skip connection's IPE steps still follow, what is taken here is
       //  overwritten by their own AccTake)
       else slot_step8<P, false, false>(acc, cx, __builtin_bit_cast(bf16x8, xc.h), __builtin_bit_cast(bf16x8, xc.l), AccTake<P>{acc, cx, l});
@@ -898,7 +1054,8 @@ __device__ __forceinline__ void layer_pass(f32x16 (&acc)[8], int l, Ctx& cx, con
     // (a pass without colour heads has no K-loop behind this point: it does the same after the layer loop, behind tap_prefetch)
     if (cx.rgb) {
       if (cx.tap == 7 && !tap7.on) dump_tap(7, cx);
-      alpha_head(cx);
+      if constexpr (DENS) dens_open(cx);
+      else alpha_head(cx);
       if (tap7.on) tap7.fn(cx);  // (here and not behind the loop for the same reason; the eight accumulator blocks are free at this point)
     }
   }

@@ -5,7 +5,8 @@
 A change of instruction PLACEMENT inside a K-step (csrc/nerf_split_chain.h) cannot change a bit, so anything but equality everywhere is a
 bug.  Both builds are loaded by path with ctypes (the loader of scripts/ab_nerf_libs.py) next to the package's own library, which only
 makes the inputs and packs the blobs: the blob layout must be the same in all three.  Seeded inputs, `synth` weights.
-  nm_nerf_fwd_{fp16x3,bf16x3}: the four pass types of tests/test_nerf_ring_schedule_gpu.py x with / without appearance row (Cambridge
+  nm_nerf_fwd_{fp16x3,bf16x3}: the four pass types of tests/test_nerf_ring_schedule_gpu.py and a tap on each of layers 0..6 with and
+    without colour heads x with / without appearance row (Cambridge
     network) x S in {32, 64, 128, 256} x R giving 1, 5 and 2.5 x CU-count tiles of 128 samples, the last one ragged where a tile holds
     several rays
   nm_nerf_points_fwd_rays_bf16x3 / nm_nerf_points_bwd_tap_bf16x3: one, five and 2.5 x CU-count tiles
@@ -30,6 +31,9 @@ PASSES = {  # tests/test_nerf_ring_schedule_gpu.py
     "norgb_tap3": dict(tap_layer=3, need_rgb=False, need_feat=True),
     "norgb_nofeat": dict(tap_layer=-1, need_rgb=False, need_feat=False),
 }
+for _tap in (0, 1, 2, 4, 5, 6):  # every other tap layer that goes through the workspace, with and without colour heads
+    PASSES[f"rgb_tap{_tap}"] = dict(tap_layer=_tap, need_rgb=True, need_feat=True)
+    PASSES[f"norgb_tap{_tap}"] = dict(tap_layer=_tap, need_rgb=False, need_feat=True)
 ENTRIES = ("nm_nerf_fwd_fp16x3", "nm_nerf_fwd_bf16x3", "nm_nerf_points_fwd_rays_bf16x3", "nm_nerf_points_bwd_tap_bf16x3", "nm_nerf_points_gate_bytes")
 
 

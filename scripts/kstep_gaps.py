@@ -9,7 +9,9 @@ slot_step4x2: the same blocks), a half on its own is a slot_step4.  "odd" K-step
 pieces of the weight request.  Per gap (the instructions behind MFMA k of a half, up to the next MFMA) the mix is printed as
   <n> ds_read, <n> VALU (accumulator reads included), <n> s_nop, DMA pieces, waits and barriers; scalar ALU is listed but not counted,
 and the gap is marked `OVER` unless it is one of (nerf_split_chain.h, "Per-gap schedule"):
-  one DMA piece and nothing else  |  <= 2 ds_read + <= 3 VALU/s_nop  |  <= 5 VALU/s_nop.
+  one DMA piece and nothing else  |  <= 2 ds_read + <= 3 VALU/s_nop  |  <= 5 VALU/s_nop  |  <= 4 ds_read and nothing else (the bias
+  reads of a views-layer unit)  |  one global store and nothing else (a row of the tapped layer stored from inside a K-loop: DESIGN
+  section 3.1, round 10).
 K-steps with the same mix in every gap are printed once, with their count and the line of the first (--all: every K-step).  The gap behind
 a K-step's last MFMA is the hand-over to whatever follows when no K-step follows directly (or only across a branch); it is printed but not judged.
 """
@@ -40,6 +42,8 @@ def classify(op):
         return "ds_other"
     if op.startswith("global_load_lds") or (op.startswith("buffer_load") and op.endswith("lds")):
         return "dma"
+    if op.startswith(("global_store", "buffer_store")):
+        return "store"
     if op.startswith(("global_", "buffer_", "flat_", "scratch_")):
         return "vmem"
     if op == "s_nop":
@@ -57,7 +61,7 @@ def classify(op):
 
 class Gap:
     def __init__(self):
-        self.n = dict(ds=0, ds_other=0, dma=0, vmem=0, nop=0, wait=0, barrier=0, valu=0, salu=0, other=0)
+        self.n = dict(ds=0, ds_other=0, dma=0, vmem=0, store=0, nop=0, wait=0, barrier=0, valu=0, salu=0, other=0)
         self.ops = []
 
     def add(self, op, text):
@@ -70,14 +74,18 @@ class Gap:
     def over(self):
         n = self.n
         if n["dma"]:
-            return n["dma"] > 1 or self.vector() or n["ds"] or n["ds_other"] or n["vmem"]
+            return n["dma"] > 1 or self.vector() or n["ds"] or n["ds_other"] or n["vmem"] or n["store"]
+        if n["store"]:
+            return n["store"] > 1 or self.vector() or n["ds"] or n["ds_other"] or n["vmem"]
         if n["ds"] or n["ds_other"]:
+            if n["ds"] <= 4 and not (n["ds_other"] or self.vector() or n["vmem"]):
+                return False
             return n["ds"] + n["ds_other"] > 2 or self.vector() > 3 or n["vmem"]
         return self.vector() > 5 or n["vmem"]
 
     def mix(self, salu=True):
         n, parts = self.n, []
-        for key, label in (("dma", "DMA piece"), ("ds", "ds_read"), ("ds_other", "other ds"), ("vmem", "vmem"), ("valu", "VALU"), ("nop", "s_nop"),
+        for key, label in (("dma", "DMA piece"), ("ds", "ds_read"), ("ds_other", "other ds"), ("vmem", "vmem"), ("store", "store"), ("valu", "VALU"), ("nop", "s_nop"),
                            ("wait", "s_waitcnt"), ("barrier", "s_barrier"), ("salu", "(SALU)"), ("other", "other")):
             if n[key] and (salu or key != "salu"):
                 parts.append(f"{n[key]} {label}")
