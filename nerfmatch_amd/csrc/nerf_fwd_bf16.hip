@@ -53,7 +53,8 @@ static_assert(TILE == SCAN_TILE, "the compositing scan of nerf_sample.h spans tw
 // Two calls per tile (PART 0: the ring rows, right after the last K-loop; PART 1: the IPE rows, behind the head that follows): 28 KiB per
 // wavefront in one burst outruns the CU's miss queue and the wavefront sits in ISSUE for most of the latency it wanted to hide (A/B on
 // one box, 4 x 4800 x 64 with all heads: one burst -0.9 % of a launch, two -1.6 ... -2.2 %, three -1.1 %: profiles/r4_ab_tap_prefetch.log).
-template <int PART>
+// OWN: the kernel owns M0 (nerf_split_chain.h, dma_slot) -- it is set and not handed back.
+template <int PART, bool OWN>
 __device__ __forceinline__ void tap_prefetch(Ctx& cx) {
   // (the caller has waited for this wavefront's last operand reads of the ring: NM_MLP_DONE_WAIT)
   if constexpr (PART == 0) __builtin_amdgcn_s_barrier();  // everybody else is through with the ring as well
@@ -66,7 +67,13 @@ __device__ __forceinline__ void tap_prefetch(Ctx& cx) {
     const char* sp = src + q * 4096;
     const float* dp = q < 4 ? cx.tap_ring + q * 1024 : cx.tap_ipe + (q - 4) * 1024;
     const unsigned lds = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)dp);
-    unsigned m0_saved;  // (M0 belongs to the compiler: handed back as found)
+    if constexpr (OWN) {
+      asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off\n\tglobal_load_lds_dwordx4 %1, off offset:1024\n\t"
+                   "global_load_lds_dwordx4 %1, off offset:2048\n\tglobal_load_lds_dwordx4 %1, off offset:3072"
+                   :: "s"(lds), "v"(sp) : "memory");
+      continue;
+    }
+    unsigned m0_saved;  // (a kernel with a builtin LDS-DMA: M0 belongs to the compiler and is handed back as found)
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %2, off\n\tglobal_load_lds_dwordx4 %2, off offset:1024\n\t"
                  "global_load_lds_dwordx4 %2, off offset:2048\n\tglobal_load_lds_dwordx4 %2, off offset:3072\n\ts_mov_b32 m0, %0"
                  : "=&s"(m0_saved) : "s"(lds), "v"(sp) : "memory");
@@ -461,9 +468,9 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
     if (!need_rgb) {
       if (cx.tap == 7) dump_tap(7, cx);  // (in front of the wait: its stores are retired before the rows are asked back)
       NM_MLP_DONE_WAIT();
-      if (cx.tap_pref) tap_prefetch<0>(cx);
+      if (cx.tap_pref) tap_prefetch<0, owns_m0<P>()>(cx);
       alpha_head(cx);
-      if (cx.tap_pref) tap_prefetch<1>(cx);
+      if (cx.tap_pref) tap_prefetch<1, owns_m0<P>()>(cx);
     } else {
       // ---- views layer + rgb head.  Input: layer 7's activations (cx.hv, bias + relu like any pts layer) through the PRODUCT
       // views_w[:, :256] . feature_w that nerf_pack_split forms (feature_linear is linear: one 128 x 256 map instead of a 256 x 256
@@ -502,7 +509,7 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
       views_extras<P>(av, cx, exh, exl, a.app_row == nullptr);
       TRACE(11);
       NM_MLP_DONE_WAIT();
-      if (cx.tap_pref) tap_prefetch<0>(cx);
+      if (cx.tap_pref) tap_prefetch<0, owns_m0<P>()>(cx);
       const float* bv = sm_small + OFF_BVIEWS + 4 * hh;
       const float* wr = sm_small + OFF_WRGB + 4 * hh;
       float pr = 0.f, pg = 0.f, pb = 0.f;
@@ -529,7 +536,7 @@ __device__ __forceinline__ void nerf_fwd_body(const NerfArgs& a) {
       c_r = sigmoid(pr);
       c_g = sigmoid(pg);
       c_b = sigmoid(pb);
-      if (cx.tap_pref) tap_prefetch<1>(cx);
+      if (cx.tap_pref) tap_prefetch<1, owns_m0<P>()>(cx);
     }
     const float sigma_raw = (cx.sig_part + nm_shfl_xor32(cx.sig_part)) + sm_small[OFF_MISC];
     TRACE(12);

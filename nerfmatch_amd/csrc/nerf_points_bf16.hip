@@ -236,6 +236,7 @@ __device__ __forceinline__ void make_unit0_b(Ctx& cx, const u32x4& gw) {
   for (int p = 0; p < 4; ++p) w.lo(p);
 }
 // one product of the backward chain: NKS K-steps x NOB output blocks on the units of cx.hv (unit 0 is in cx.xn)
+// (mode 3 = the arithmetic of mode 0 with the weight request that leaves M0 to the compiler: nerf_split_chain.h, owns_m0)
 template <int NOB, int NKS, bool GATED>
 __device__ __forceinline__ void bwd_product(f32x16 (&acc)[NOB], Ctx& cx, const u32x4& gw) {
 #pragma unroll
@@ -244,22 +245,22 @@ __device__ __forceinline__ void bwd_product(f32x16 (&acc)[NOB], Ctx& cx, const u
       const Unit xc = cx.xn;
       const bf16x8 xh = __builtin_bit_cast(bf16x8, xc.h), xl = __builtin_bit_cast(bf16x8, xc.l);
       if constexpr (NOB == 8) {
-        if (ks == 0) slot_step8<0, true, true>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 1, cx, cx.xn, gw));
-        else slot_step8<0, false, true>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 1, cx, cx.xn, gw));
+        if (ks == 0) slot_step8<3, true, true>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 1, cx, cx.xn, gw));
+        else slot_step8<3, false, true>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 1, cx, cx.xn, gw));
       } else {
-        if (ks == 0) slot_step4<0, true, true>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 1, cx, cx.xn, gw));
-        else slot_step4<0, false, true>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 1, cx, cx.xn, gw));
+        if (ks == 0) slot_step4<3, true, true>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 1, cx, cx.xn, gw));
+        else slot_step4<3, false, true>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 1, cx, cx.xn, gw));
       }
     }
     {
       const Unit xc = cx.xn;
       const bf16x8 xh = __builtin_bit_cast(bf16x8, xc.h), xl = __builtin_bit_cast(bf16x8, xc.l);
       if constexpr (NOB == 8) {
-        if (ks + 2 < NKS) slot_step8<0, false, false>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 2, cx, cx.xn, gw));
-        else slot_step8<0, false, false>(acc, cx, xh, xl, NoWork{});
+        if (ks + 2 < NKS) slot_step8<3, false, false>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 2, cx, cx.xn, gw));
+        else slot_step8<3, false, false>(acc, cx, xh, xl, NoWork{});
       } else {
-        if (ks + 2 < NKS) slot_step4<0, false, false>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 2, cx, cx.xn, gw));
-        else slot_step4<0, false, false>(acc, cx, xh, xl, NoWork{});
+        if (ks + 2 < NKS) slot_step4<3, false, false>(acc, cx, xh, xl, unit_work_b<GATED>(ks + 2, cx, cx.xn, gw));
+        else slot_step4<3, false, false>(acc, cx, xh, xl, NoWork{});
       }
     }
   }
@@ -295,7 +296,7 @@ __device__ __forceinline__ void points_bwd_body(const PointsArgs& a) {
     const int sample = bid * TILE + wave * 32 + s;
     const bool valid = sample < a.n;
     const size_t sc = (size_t)(valid ? sample : a.n - 1);
-    ring_open<0>(blob_slots, ring, wave, lane);
+    ring_open<3>(blob_slots, ring, wave, lane);
     const u32x4* gt = a.gates + (size_t)bid * 9 * 256 + tid;
     const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.g4 + sc * 4);
     Ctx cx;
@@ -324,8 +325,8 @@ __device__ __forceinline__ void points_bwd_body(const PointsArgs& a) {
           }
         }
     }
-    ring_open_wait<0>(cx);
-    load_half<0>(cx.opA, ring, lane, 0);
+    ring_open_wait<3>(cx);
+    load_half<3>(cx.opA, ring, lane, 0);
     const u32x4 none = {0u, 0u, 0u, 0u};
     f32x16 acc[8];
     // views^T -> xd columns

@@ -15,8 +15,9 @@ namespace nmbf {
 //   P = 1  "fp16x1": operands rounded once to fp16, ONE MFMA per product block (8 KiB slots) -- opt-in throughput mode of
 //                    the lean render's coarse pass: DESIGN.md section 3.1d
 //   P = 4  bf16x3 + the ReLU gates of every layer recorded as bits (the pointwise forward of the iNeRF refinement, nerf_points_bf16.hip)
+//   P = 3  bf16x3 of the pointwise backward: the arithmetic of P = 0 with the weight request of rounds 7-10 (see owns_m0)
 // Operands are carried as 16-byte vectors typed bf16x8 in all modes; P = 1, 2 reinterpret them as 8 x fp16.
-template <int P> constexpr bool is_bf16() { return P == 0 || P == 4; }
+template <int P> constexpr bool is_bf16() { return P == 0 || P == 3 || P == 4; }
 template <int P> constexpr bool has_gates() { return P == 4; }
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -89,10 +90,25 @@ __device__ __forceinline__ void park_ipe(float* dst, F value) {
 // The 4 pieces share ONE global address and ONE M0 (LDS base) and differ only in the instruction's immediate offset,
 // which the hardware adds on both sides -- measured 31 instead of 58 cycles of issue per piece beside the MFMAs.
 // Address = uniform slot base (SGPR pair) + one 32-bit per-lane offset: no 64-bit VGPR arithmetic per slot.
+// Who owns M0: a kernel of the split modes issues EVERY LDS-DMA as inline asm (here, ring_request, the render kernel's tap_prefetch), so the
+// compiler emits no instruction of its own that reads or writes M0 in it and the asm sets M0 without handing it back (M0 is reserved: a
+// clobber of it is not honoured, which is why a kernel that keeps one builtin LDS-DMA -- fp16x1 -- keeps the builtin everywhere and the
+// save / restore around its asm pieces).  `scripts/kstep_gaps.py --m0` lists what touches M0 in a kernel; tests/test_nerf_m0_cpu.py runs it.
+// The pointwise backward (P = 3) stays as it was as well: with the running request state of ring_arm its register allocation, which has no
+// VGPR to spare, went to scratch (651 VGPR spills).
+template <int P> constexpr bool owns_m0() { return is_split<P>() && P != 3; }
 template <int P>
 __device__ __forceinline__ void dma_slot(const char* blob_slots, int g, float* ring, int wave, int lane) {
   const unsigned voff = (unsigned)(wave * (slot_bytes<P>() / 4) + lane * 16);
   const char* base = blob_slots + (size_t)g * slot_bytes<P>();  // uniform
+  if constexpr (owns_m0<P>()) {
+    const float* q = ring_slot<P>(ring, g) + wave * (slot_floats<P>() / 4);
+    const unsigned lds = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)q);
+    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
+                 "global_load_lds_dwordx4 %1, %2 offset:2048\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072"
+                 :: "s"(lds), "v"(voff), "s"(base) : "memory");
+    return;
+  }
   const auto* src = (const __attribute__((address_space(1))) void*)(base + voff);
   auto* dst = (__attribute__((address_space(3))) void*)(ring_slot<P>(ring, g) + wave * (slot_floats<P>() / 4));
   __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
@@ -194,7 +210,12 @@ struct Ctx {
   int tap;          // layer whose activations are tapped (-1: none)
   int g;            // next weight slot
   unsigned dma_voff;  // split modes, ring_request: this lane's byte offset inside a slot (its wavefront's quarter + 16 lane) and
-  unsigned dma_lds;   //   the LDS byte address of its wavefront's quarter of ring position 0 (uniform: an SGPR); set by ring_open_wait
+  unsigned dma_lds;   //   (P = 3) the LDS byte address of its wavefront's quarter of ring position 0 (uniform: an SGPR); set by ring_open_wait
+  // owns_m0: the running state of the weight request, all uniform (SGPRs), set by ring_open_wait and stepped by ring_arm:
+  unsigned long long dma_p, dma_q;  // global address of the second / the first slot of the request being issued (before ring_arm: dma_p = the
+                                    //   last slot requested so far)
+  unsigned dma_m, dma_s;            // LDS byte address of this wavefront's quarter of the request's first ring position (0 or 2), and the
+                                    //   sum of the two (the position steps and wraps as m = s - m)
   OpHalf opA;       // A operands of the next half slot, fetched one half slot ahead
   OpHalf opB;       // fp16x1: blocks 4-7 of the next slot (the whole slot is fetched one K-step ahead there)
   f32x4 hb0, hb1;   // split modes: biases of unit 0 of the layer being finished, read by its last K-step (AccTake) for finish_layer
@@ -219,25 +240,64 @@ struct Ctx {
 // (ring_acquire_two: vmcnt(0)) retires them, a K-step of ~1100 cycles after the request against 250-400 of L2-warm landing time.  A
 // tile opens with slots 0 and 1 (ring_open); past its last slot the stream runs on into the blob's padding, branch free.
 // Piece j & 3 of slot g + 2 + (j >> 2): the same address, M0 and immediate offsets as dma_slot's four.  Inline asm like tap_prefetch
-// (nerf_fwd_bf16.hip), M0 handed back as found: the compiler cannot tell these LDS writes from the operands the next ds_read fetches
+// (nerf_fwd_bf16.hip): the compiler cannot tell these LDS writes from the operands the next ds_read fetches
 // and may wait vmcnt(0) in front of it; and the address is the uniform slot base in an SGPR pair plus the lane's 32-bit offset -- no
 // 64-bit VGPR pair kept alive beside the accumulators (the pointwise backward has none to spare).  One asm statement per piece and no
 // sched_barrier of its own where a work piece shares the gap: the K-loops' bodies are close to the size up to which `#pragma unroll`
 // unrolls fully, and a loop left rolled indexes cx.hv at run time -- Ctx in scratch.
+// Round 11: a DMA gap holds the piece and nothing else.  A scalar instruction takes an issue turn like a VALU one (scripts/ubench/fillers.hip:
+// six per gap hide behind an MFMA, ten do not; ten beside a piece cost 50 cycles), and through round 10 the first piece of a slot had the
+// 64-bit `blob_slots + slot * 16 KiB`, the ring position from `g` and the M0 save / set / restore beside it, 9-11 scalar instructions.  Now
+// the request's addresses are running state (Ctx::dma_p, dma_q, dma_m), stepped by ring_arm in two gaps in FRONT of the request's first piece
+// that carry no DMA (three scalar instructions each), M0 is set there once for the first slot, and the second slot's ring position -- always
+// the next one: a request is an (even, odd) pair of slots -- is one s_add on M0 behind the first slot's last piece.  The requests of a tile
+// are consecutive pairs of slots starting with (2, 3), so the state needs no slot number: ring_open_wait resets it where cx.g is reset.
+template <int P>
+__device__ __forceinline__ void ring_arm(Ctx& cx, int stage) {
+  if constexpr (!owns_m0<P>()) return;
+  if (stage == 0) {
+    cx.dma_q = cx.dma_p + (unsigned)slot_bytes<P>();
+    cx.dma_m = cx.dma_s - cx.dma_m;
+    asm volatile("" : "+s"(cx.dma_q), "+s"(cx.dma_m));  // (made here, not where the pieces use them)
+  } else {
+    cx.dma_p = cx.dma_q + (unsigned)slot_bytes<P>();
+    asm volatile("s_mov_b32 m0, %1" : "+s"(cx.dma_p) : "s"(cx.dma_m));
+  }
+}
+// (g: the even K-step the request belongs to -- used by the form that does not own M0 only, which makes every piece's addresses from it and
+//  hands M0 back as found)
 template <int P>
 __device__ __forceinline__ void ring_request(const Ctx& cx, int g, int j) {
-  const int slot = g + 2 + (j >> 2);
-  const char* base = cx.blob_slots + (size_t)slot * slot_bytes<P>();  // uniform
-  const unsigned lds = cx.dma_lds + (unsigned)(slot & (ring_slots<P>() - 1)) * slot_bytes<P>();
-  unsigned m0_saved;
+  static_assert(slot_bytes<P>() == 0x4000 || !is_split<P>(), "the M0 step behind piece 3 is one slot");
+  if constexpr (!owns_m0<P>()) {
+    const int slot = g + 2 + (j >> 2);
+    const char* base = cx.blob_slots + (size_t)slot * slot_bytes<P>();  // uniform
+    const unsigned lds = cx.dma_lds + (unsigned)(slot & (ring_slots<P>() - 1)) * slot_bytes<P>();
+    unsigned m0_saved;
 #define NM_DMA_PIECE(OFS)                                                                                                        \
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %2, %3 offset:" #OFS "\n\ts_mov_b32 m0, %0" \
                : "=&s"(m0_saved) : "s"(lds), "v"(cx.dma_voff), "s"(base) : "memory")
-  switch (j & 3) {  // (a compile-time constant after unrolling)
-    case 0: NM_DMA_PIECE(0); break;
-    case 1: NM_DMA_PIECE(1024); break;
-    case 2: NM_DMA_PIECE(2048); break;
-    default: NM_DMA_PIECE(3072); break;
+    switch (j & 3) {  // (a compile-time constant after unrolling)
+      case 0: NM_DMA_PIECE(0); break;
+      case 1: NM_DMA_PIECE(1024); break;
+      case 2: NM_DMA_PIECE(2048); break;
+      default: NM_DMA_PIECE(3072); break;
+    }
+#undef NM_DMA_PIECE
+    return;
+  }
+#define NM_DMA_PIECE(OFS, BASE) asm volatile("global_load_lds_dwordx4 %0, %1 offset:" #OFS :: "v"(cx.dma_voff), "s"(BASE) : "memory")
+  switch (j) {  // (a compile-time constant after unrolling)
+    case 0: NM_DMA_PIECE(0, cx.dma_q); break;
+    case 1: NM_DMA_PIECE(1024, cx.dma_q); break;
+    case 2: NM_DMA_PIECE(2048, cx.dma_q); break;
+    case 3:  // (+ M0 to the second slot's ring position)
+      asm volatile("global_load_lds_dwordx4 %0, %1 offset:3072\n\ts_add_u32 m0, m0, 0x4000" :: "v"(cx.dma_voff), "s"(cx.dma_q) : "memory", "scc");
+      break;
+    case 4: NM_DMA_PIECE(0, cx.dma_p); break;
+    case 5: NM_DMA_PIECE(1024, cx.dma_p); break;
+    case 6: NM_DMA_PIECE(2048, cx.dma_p); break;
+    default: NM_DMA_PIECE(3072, cx.dma_p); break;
   }
 #undef NM_DMA_PIECE
 }
@@ -259,7 +319,15 @@ template <int P>
 __device__ __forceinline__ void ring_open_wait(Ctx& cx) {
   cx.dma_voff = (unsigned)(cx.wave * (slot_bytes<P>() / 4) + cx.lane * 16);
   const float* q = cx.ring + cx.wave * (slot_floats<P>() / 4);
-  cx.dma_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)q);
+  const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)q);
+  if constexpr (owns_m0<P>()) {
+    // the first request is slots (2, 3) into ring positions (2, 3): ring_arm steps from "slot 1 requested last, position 0"
+    cx.dma_m = lds0; cx.dma_s = 2u * lds0 + 2u * (unsigned)slot_bytes<P>();
+    cx.dma_p = (unsigned long long)(size_t)(cx.blob_slots + slot_bytes<P>());
+    cx.dma_q = cx.dma_p;
+  } else {
+    cx.dma_lds = lds0;
+  }
   NM_WAIT_VMCNT(0);
   __builtin_amdgcn_s_barrier();
 }
@@ -296,7 +364,9 @@ __device__ __forceinline__ unsigned gate_byte(const u32x4& h) {
 // ---- Per-gap schedule ---------------------------------------------------------------------------------------------------------------
 // One wavefront per SIMD: an MFMA holds vector issue for 8 of its 32 cycles, so what sits in the gap behind it hides while its issue costs
 // stay within 24 cycles (VALU / s_nop 4 each, two ds_read_b128 <= 3, an LDS-DMA piece 31-60).  Every gap is therefore one of
-//   (a) one DMA piece and nothing else   (b) <= 2 ds_read_b128 + <= 3 VALU   (c) <= 5 VALU (an s_nop counts as one);
+//   (a) one DMA piece and nothing else   (b) <= 2 ds_read_b128 + <= 3 VALU   (c) <= 5 VALU (an s_nop counts as one; so does a
+// scalar ALU instruction -- round 11: ring_arm's three, in front of an even K-step's pieces in first-half gaps 2, 3 or, request_early, in the
+// odd K-step's first-half gap 5 and second-half gap 4, are not in the table below);
 // scripts/kstep_gaps.py prints what the compiler made of it (profiles/r8_kstep_gaps_*.log).  8-block K-step (slot_step8), gap k = behind
 // MFMA k of the half; B = operands of blocks 4-7 of this slot, A' = operands of blocks 0-3 of the next slot:
 //   gap        | odd K-step, fp16x3       | odd, bf16 modes    | even K-step, fp16x3      | even, bf16 modes
@@ -331,7 +401,8 @@ __device__ __forceinline__ unsigned gate_byte(const u32x4& h) {
 //   * bf16 modes, even K-steps, second half 7-11 (6 VALU each; P = 4: + the ~10 of the gate byte in the last): hi is four instructions
 //     there (no mixed-precision FMA reads the packed half: two conversions, a shift and a mask), and 44 VALU do not fit into the 45 issue
 //     slots behind the bias reads in whole operations.  P = 4, odd K-steps: the gate byte is one operation of ~10 in an otherwise empty gap.
-//   * the IPE K-steps of layer 0, DMA gaps 4 and 8: two v_readlane each -- the slot address comes back from an SGPR spilled to a VGPR lane.
+//   * (through round 10: the IPE K-steps of layer 0, DMA gaps 4 and 8, two v_readlane each -- the slot address came back from an SGPR spilled
+//     to a VGPR lane.  With the request's addresses as running state the reload is the tile's first ring_arm's, in first-half gap 2.)
 //   * a layer's last K-step (AccTake): nothing; the 17 accumulator reads that do not fit go to the head of finish_layer, where they run
 //     while the K-loop's last MFMAs drain.
 //   * views layer, even positions (slot_step4x2 / slot_step4): two units per 24 MFMAs (72 VALU, 20 ds_read) and 8 DMA pieces are more than
@@ -797,10 +868,14 @@ __device__ __forceinline__ void slot_step8(f32x16 (&acc)[8], Ctx& cx, const bf16
     __builtin_amdgcn_sched_barrier(0);
     if (k < 4) load_pair<P>(B, cur, cx.lane, 1, k);
     if constexpr (EVEN && !RQE) {
+      if (k == 2 || k == 3) ring_arm<P>(cx, k - 2);
       if (k >= 4) ring_request<P>(cx, g, k - 4);
     }
     if constexpr (EVEN && RQE) {  // (pieces 0..5: the previous K-step, behind its barrier)
       if (k == 4 || k == 5) ring_request<P>(cx, g, k + 2);
+    }
+    if constexpr (!EVEN && RQE) {  // (the next K-step's request: its addresses, in a gap this mode leaves empty)
+      if (k == 5) ring_arm<P>(cx, 0);
     }
     work.template step8<EVEN>(k);
     __builtin_amdgcn_sched_barrier(0);
@@ -816,6 +891,7 @@ __device__ __forceinline__ void slot_step8(f32x16 (&acc)[8], Ctx& cx, const bf16
     __builtin_amdgcn_sched_barrier(0);
     if (k >= 1 && k <= 4) load_pair<P>(cx.opA, nxt, cx.lane, 0, k - 1);
     if constexpr (!EVEN && RQE) {
+      if (k == 4) ring_arm<P>(cx, 1);
       if (k >= 5 && k <= 10) ring_request<P>(cx, g + 1, k - 5);
     }
     if (k == 11) lds_retire<P>();  // (the next slot's A operands: read in gaps 1-4; in front of the work: its bias_next reads stay in flight)
@@ -864,6 +940,7 @@ __device__ __forceinline__ void slot_step4(f32x16 (&acc)[4], Ctx& cx, const bf16
     __builtin_amdgcn_sched_barrier(0);
     if (k >= 1 && k <= 4) load_pair<P>(cx.opA, nxt, cx.lane, 0, k - 1);
     if constexpr (EVEN) {
+      if (k == 2 || k == 3) ring_arm<P>(cx, k - 2);
       if (k >= 4) ring_request<P>(cx, g, k - 4);
     }
     work.seq(k);
@@ -893,7 +970,8 @@ __device__ __forceinline__ void slot_step4x2(f32x16 (&av)[4], Ctx& cx, const bf1
     av[k & 3] = mfma_k<P, FIRST>(k, A, x0h, x0l, av[k & 3]);
     __builtin_amdgcn_sched_barrier(0);
     if (k >= 1 && k <= 4) load_pair<P>(B, cur, cx.lane, 1, k - 1);  // the second K-step's operands
-    if constexpr (EVEN) {
+    if constexpr (EVEN) {  // (ring_arm: gap 0 holds reads only, gap 2 the fewest VALU of gaps 1-3)
+      if (k == 0 || k == 2) ring_arm<P>(cx, k >> 1);
       if (k >= 4) ring_request<P>(cx, g, k - 4);
     }
     if (k == 11) lds_retire<P>();  // (the second K-step's operands: read in gaps 1-4)
