@@ -8,7 +8,7 @@ sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
 import torch
 from conftest import load_golden
 from nerfmatch_amd import ops
-from test_nerf_gpu import make_renderer
+from nerf_kernel_util import make_renderer
 from test_resample_truth_gpu import resample_fp64
 from test_surface_seeds_gpu import SEEDS
 

@@ -2,7 +2,7 @@ import sys, torch
 sys.path.insert(0, "tests"); sys.path.insert(0, ".")
 from conftest import load_golden
 from nerfmatch_amd import ops
-from test_nerf_gpu import make_renderer
+from nerf_kernel_util import make_renderer
 from test_surface_seeds_gpu import SEEDS
 from test_resample_truth_gpu import resample_fp64
 gpu = torch.device("cuda:0")

@@ -13,7 +13,7 @@ sys.path.insert(0, str(ROOT / "tests"))
 import torch
 
 from conftest import load_golden
-from test_nerf_gpu import make_renderer
+from nerf_kernel_util import make_renderer
 from test_surface_seeds_gpu import SEEDS, REF_KEY
 
 torch.set_grad_enabled(False)

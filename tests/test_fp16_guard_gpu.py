@@ -9,7 +9,7 @@ import torch
 
 from conftest import load_golden
 from nerfmatch_amd import _lib, ops, synth
-from test_nerf_gpu import make_renderer, maxdiff
+from nerf_kernel_util import make_renderer, maxdiff
 
 pytestmark = pytest.mark.gpu
 OUT_KEYS = ("weights", "feat", "pts", "rgb", "depth", "acc")

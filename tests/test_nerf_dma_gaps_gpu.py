@@ -8,16 +8,14 @@ a tile takes another form (32, 64, 128; 256: two chunks, the stream starts over 
 ragged second round) and 2.5 x CU count (a workgroup's third tile), zero_tail with its leftover pass -- and checks bit for bit that a
 bundle's outputs do not depend on how many tiles its workgroups ran before.
 
-Helpers and the 1e-4-of-scale bar: tests/test_nerf_gpu.py, tests/test_nerf_tap7_early_gpu.py (as tests/test_nerf_gap_work_gpu.py)."""
+The 1e-4-of-scale bar, networks and launches: tests/nerf_kernel_util.py (the networks of tests/test_nerf_gap_work_gpu.py)."""
 import functools
 
 import pytest
 import torch
 
+from nerf_kernel_util import KEYS, compare, fence_posts, launch, oracle_rays, styled_network, tol_for
 from nerfmatch_amd import ops, synth
-from oracle import nerf_oracle as no
-from test_nerf_gpu import TOL, tol_for
-from test_nerf_tap7_early_gpu import KEYS, _compare, _network
 
 pytestmark = pytest.mark.gpu
 ROWS = (32, 64, 128, 256, 96)
@@ -26,17 +24,10 @@ CONFIGS = ((True, True, 3), (True, False, 7), (True, False, None), (False, False
 
 
 @functools.lru_cache(maxsize=None)
-def _all_rays():
-    H = W = 256
-    K = torch.tensor([[200.0, 0, W / 2], [0, 200.0, H / 2], [0, 0, 1]])
-    return no.make_rays(H, W, K, synth.camera_pose(3), ds=2).contiguous()  # 16384 rays
-
-
-@functools.lru_cache(maxsize=None)
 def _bundle(S, R, first=0):
-    rays = _all_rays()[first:first + R].contiguous()
+    rays = oracle_rays(256, 256, 200.0, 3, 2)[first:first + R].contiguous()  # (of 16384 rays)
     assert rays.shape[0] == R
-    return rays, no.sample_coarse(rays, S, synth.uniform01((R, S + 1), 100 + S + 7 * first))
+    return rays, fence_posts(rays, S, 100 + S + 7 * first)
 
 
 def _rays_for(S, tiles):
@@ -51,15 +42,8 @@ def _tile_counts():
 
 
 def _launch(precision, app, rays, t, tap, rgb, **kw):
-    ren, _, row = _network(None, app)
-    dev = torch.device("cuda:0")
-    blob = ren.nerf_coarse.packed(dev, precision)
-    with torch.no_grad():
-        out = ops.nerf_fwd(blob, rays.to(dev), t.to(dev), None if row is None else row.to(dev), tap_layer=-1 if tap is None else tap,
-                           need_rgb=rgb, need_feat=tap is not None, **kw)
-    if precision == "fp16x3":
-        assert not blob.nm_guard.read()[0], "an fp16x3 operand saturated: the outputs are the fp32 kernel's"
-    return out
+    ren, _, row = styled_network(None, app)
+    return launch(ren, "coarse", precision, rays, t, row, tap_layer=-1 if tap is None else tap, need_rgb=rgb, need_feat=tap is not None, **kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -84,7 +68,7 @@ def test_stream_lengths_and_restarts_vs_fp32_kernel(gpu, built_lib, precision, S
         ref = _fp32(app, S, R, tap, rgb)
         assert out["weights"].shape == (R, S) and (out["rgb"] is None) == (not rgb) and (out["feat"] is None) == (tap is None)
         assert float(ref["weights"].sum(-1).max()) > 0.3  # not vacuous
-        _compare(out, ref, tol, False, f"{precision} S {S} R {R} rgb {rgb} app {app} tap {tap} vs fp32 kernel", _keys(rgb, tap))
+        compare(out, ref, tol, False, f"{precision} S {S} R {R} rgb {rgb} app {app} tap {tap} vs fp32 kernel", _keys(rgb, tap))
 
 
 @pytest.mark.parametrize("S", [64, 128])
@@ -92,17 +76,16 @@ def test_stream_lengths_and_restarts_vs_fp32_kernel(gpu, built_lib, precision, S
 def test_leftover_pass_vs_fp32_kernel(gpu, built_lib, precision, S):
     """zero_tail on a fine-style row over 2.5 x CU count tiles: every workgroup runs two or three regular tiles of S/2 samples per ray and
     then the leftover pass over the samples it queued, whose stream starts over like a tile's"""
-    dev = torch.device("cuda:0")
     R = _rays_for(S // 2, _tile_counts()["third_tile"])
     rays, t_c = _bundle(S, R)
     w_c = _launch(precision, False, rays, t_c, None, False)["weights"]
-    t_f, flag = ops.resample(t_c.to(dev), w_c, synth.resample_jitter((R, S + 1), 200 + S).to(dev), want_tail_flag=True)
+    t_f, flag = ops.resample(t_c.to(w_c.device), w_c, synth.resample_jitter((R, S + 1), 200 + S).to(w_c.device), want_tail_flag=True)
     assert int(flag.item()) == 0  # the premise holds: the zero-tail path is taken
     out = _launch(precision, False, rays, t_f, 3, True, zero_tail=True, tail_flag=flag)
     ref = _launch("fp32", False, rays, t_f, 3, True, zero_tail=True, tail_flag=flag)
     assert float(ref["weights"].sum(-1).max()) > 0.3
     assert float(out["weights"][:, S // 2 + 1:].abs().max()) == 0.0
-    _compare(out, ref, tol_for(precision, "default"), False, f"{precision} zero tail S {S} R {R} vs fp32 kernel")
+    compare(out, ref, tol_for(precision, "default"), False, f"{precision} zero tail S {S} R {R} vs fp32 kernel")
 
 
 @pytest.mark.parametrize("rgb", [True, False])

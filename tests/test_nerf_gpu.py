@@ -3,55 +3,20 @@
 Tolerances: sampling rows are elementwise fp32 -> 1e-6; anything through the 8-layer MLP -> 1e-4
 (BASELINE.json north_star: "rendered features and match scores within 1e-4 fp32"), taken relative to the tensor's scale
 max(1, max|reference|): absolute 1e-4 for the unit-scale fixtures, and the same 1e-4 of full scale for the trained-like
-"surface" fixture (round 3: activations up to 18, densities +-1e4 whose fp32 ulp alone is 1e-3)."""
+"surface" fixture (round 3: activations up to 18, densities +-1e4 whose fp32 ulp alone is 1e-3).
+The bars themselves (TOL, relerr, tol_for) and make_renderer: tests/nerf_kernel_util.py."""
 import numpy as np
 import pytest
 import torch
 
-from conftest import abs_bound, load_golden
+from conftest import load_golden
+from nerf_kernel_util import SPLIT, TOL, make_renderer, maxdiff, relerr, tol_for
 from nerfmatch_amd import synth, ops, _lib
 from nerfmatch_amd.nerf.renderer import NerfRenderer
 from oracle import nerf_oracle as no
 
 pytestmark = pytest.mark.gpu
 CASES = ["r32_s32", "r128_s64_app", "r32_s32_last", "surface_r512_s128", "surface_r256_s64_app"]
-TOL = 1e-4
-
-
-def maxdiff(a, b):
-    return (a.detach().cpu().float() - torch.as_tensor(b).float()).abs().max().item()
-
-
-def relerr(a, b, what=None):
-    """max |a - b| in units of the reference tensor's scale max(1, max|b|).  With `what`: the ABSOLUTE maximum is also held to its
-    recorded bound (conftest.abs_bound: 1.5 x the value measured when tests/golden/abs_bounds.json was made) -- an of-scale bar alone
-    could hide a drift on the trained-like fixtures, whose scales are 20 (activations) to 1e4 (densities)."""
-    b = torch.as_tensor(b).float()
-    d = maxdiff(a, b)
-    if what is not None:
-        abs_bound(what, d)
-    return d / max(1.0, b.abs().max().item() if b.numel() else 1.0)
-
-
-SPLIT = ["fp16x3", "bf16x3"]  # the two operand splits of the 16-bit matrix-core kernel (fp16x3 = the default parity arithmetic)
-
-
-def tol_for(precision, case):
-    """1e-4 everywhere, with ONE stated exception (round 3 finding): the bf16 split (16 mantissa bits) on the trained-like
-    "surface" fixture -- densities of +-1e4 come out ~0.25 off, compositing weights up to 7e-4, rendered features 1.4e-4 of
-    scale.  It is no longer the default; its bound there is 2e-3 and the measured values are printed."""
-    return 2e-3 if (precision == "bf16x3" and case.startswith("surface")) else TOL
-
-
-def make_renderer(fx, gpu, S=None):
-    app = bool(fx["app"])
-    cfg = synth.nerf_config("cambridge" if app else "7scenes", num_pts=S or fx["S"], img_wh=(fx["W"], fx["H"]))
-    ren = NerfRenderer(cfg, num_frames=5 if app else None, training=False, stop_layer=fx["stop_layer"])
-    style = str(fx["style"]) if "style" in fx and str(fx["style"]) else None
-    sd = synth.nerf_state_dict(seed=int(fx["weights_seed"]), app_vocab=5 if app else 0, density_bias=float(fx["density_shift"]) if (style and "density_shift" in fx) else (0.0 if style else 3.0), style=style)
-    ren.load_state_dict(sd, strict=True)
-    ren.precision = "fp32"  # the tests of the split kernels switch it explicitly (the class default is "fp16x3")
-    return ren.to(gpu).eval(), sd
 
 
 def test_library_loaded(gpu, built_lib):

@@ -10,7 +10,7 @@ Cases: the four pass types x {fp16x3, bf16x3} x S in {32, 64, 128, 256} x the ti
 appearance row at S = 32 and 256 (the parity of the views layer's K-step count differs between the two); trained-like weights (synth
 style "surface": the re-packing scale is not 1, activations are large) on fp16x3; the pointwise forward / backward pair of the iNeRF
 refinement at one and five tiles.
-Checks: every output against the fp32-MFMA kernel (csrc/nerf_fwd.hip) on the same inputs at TOL of tests/test_nerf_gpu.py (1e-4 of the
+Checks: every output against the fp32-MFMA kernel (csrc/nerf_fwd.hip) on the same inputs at TOL of tests/nerf_kernel_util.py (1e-4 of the
 tensor's scale, the bar of the split kernels); the pointwise pair against the fp32 GEMM chain at the bars of tests/test_inerf_gpu.py;
 three repeated launches bit-equal.  Seeded inputs only; every reference is computed once and never written."""
 import functools
@@ -18,11 +18,8 @@ import functools
 import pytest
 import torch
 
-from nerfmatch_amd import inerf, ops, synth
-from nerfmatch_amd.nerf.renderer import NerfRenderer
-from test_inerf_gpu import _points_case
-from test_nerf_gpu import TOL, relerr
-from test_nerf_ring_schedule_gpu import KEYS, PASSES
+from nerf_kernel_util import PASSES, TOL, camera_rays, compare_repeated, fence_posts, launch, network, points_bundle, points_pair
+from nerfmatch_amd import inerf
 
 pytestmark = pytest.mark.gpu
 TILES = (1, 2, 5)
@@ -35,79 +32,49 @@ def _rays(S, tiles):
 
 # (S, R) without repeats: S = 256 has one ray (two tiles) for both 1 and 2
 SIZES = sorted({(S, _rays(S, n)) for S in (32, 64, 128, 256) for n in TILES})
+# arguments of nerf_kernel_util.network
+NETWORKS = {"7scenes": ("7scenes", 11), "cambridge_row": ("cambridge", 11), "cambridge_no_row": ("cambridge", 11),
+            "surface": ("7scenes", 0, "surface")}  # (seed 0, the bench's trained-like leg: other seeds leave the part of space these cameras see empty)
 
 
-@functools.lru_cache(maxsize=None)
 def _network(net):
     """(renderer, appearance row or None): "7scenes", "surface" (trained-like weights), "cambridge_row", "cambridge_no_row" """
-    if net == "cambridge_no_row":
-        return _network("cambridge_row")[0], None
-    app = net == "cambridge_row"
-    dev = torch.device("cuda:0")
-    cfg = synth.nerf_config("cambridge" if app else "7scenes", num_pts=64)
-    ren = NerfRenderer(cfg, num_frames=5 if app else None, training=False, stop_layer=3)
-    if net == "surface":  # (seed 0, the bench's trained-like leg: other seeds leave the part of space these cameras see empty)
-        sd = synth.nerf_state_dict(seed=0, style="surface")
-    else:
-        sd = synth.nerf_state_dict(seed=11, app_vocab=5 if app else 0, density_bias=3.0)
-    ren.load_state_dict(sd, strict=True)
-    ren.to(dev).eval()
-    ren.calibrate(dev)  # fp16x3 operand scales from the seeded probe bundle
-    return ren, (sd["embedding_a.weight"][1].contiguous().to(dev) if app else None)
+    ren, _, row = network(*NETWORKS[net])
+    return ren, (None if net == "cambridge_no_row" else row)
 
 
 @functools.lru_cache(maxsize=None)
 def _inputs(S, R, net):
     """R rays spread over an image and their fence posts.  The "surface" network occupies about a quarter of space (synth.SURFACE_STYLE), so a
     handful of rays may all miss it: there the R rays are those of 240 candidates on which the REFERENCE kernel finds the most opacity."""
-    dev = torch.device("cuda:0")
-    allrays = ops.raygen(synth.intrinsics(), synth.camera_pose(2), 480, 640, dev)[0]
+    allrays = camera_rays(2)
     if net == "surface":
         cand = allrays[7::20].contiguous()
-        t = ops.sample_coarse(cand, synth.uniform01((cand.shape[0], S + 1), 300 + S).to(dev), S)
-        with torch.no_grad():
-            acc = ops.nerf_fwd(_network(net)[0].nerf_fine.packed(dev, "fp32"), cand, t, tap_layer=-1, need_rgb=False, need_feat=False)["acc"]
+        t = fence_posts(cand, S, 300 + S)
+        acc = launch(_network(net)[0], "fine", "fp32", cand, t, tap_layer=-1, need_rgb=False, need_feat=False)["acc"]
         keep = torch.sort(torch.topk(acc, R).indices).values
         return cand[keep].contiguous(), t[keep].contiguous()
     rays = allrays[37:37 + 61 * R:61].contiguous()
     assert rays.shape[0] == R
-    return rays, ops.sample_coarse(rays, synth.uniform01((R, S + 1), 300 + S + R).to(dev), S)
+    return rays, fence_posts(rays, S, 300 + S + R)
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(net, S, R, name):
     ren, row = _network(net)
-    rays, t = _inputs(S, R, net)
-    with torch.no_grad():
-        out = ops.nerf_fwd(ren.nerf_fine.packed(rays.device, "fp32"), rays, t, row, **PASSES[name])
+    out = launch(ren, "fine", "fp32", *_inputs(S, R, net), row, **PASSES[name])
     return {k: v.clone() for k, v in out.items() if v is not None}
 
 
 def _launch(precision, net, S, R, name):
     ren, row = _network(net)
-    rays, t = _inputs(S, R, net)
-    blob = ren.nerf_fine.packed(rays.device, precision)
-    with torch.no_grad():
-        out = ops.nerf_fwd(blob, rays, t, row, **PASSES[name])
-    if precision == "fp16x3":  # the guarded fp32 pass must not have rewritten what this file is about
-        assert not blob.nm_guard.read()[0], "an fp16x3 operand saturated: the outputs are the fp32 kernel's"
-    return {k: v for k, v in out.items() if v is not None}
+    return {k: v for k, v in launch(ren, "fine", precision, *_inputs(S, R, net), row, **PASSES[name]).items() if v is not None}
 
 
 def _check(precision, net, S, R, name):
     assert R * S <= 6 * 128 < 128 * torch.cuda.get_device_properties(0).multi_processor_count  # fewer tiles than workgroups
-    ref = _reference(net, S, R, name)
-    assert float(ref["weights"].sum(-1).max()) > 0.3  # not vacuous
     runs = [_launch(precision, net, S, R, name) for _ in range(3)]
-    for k in KEYS:
-        if k not in ref:
-            assert k not in runs[0]
-            continue
-        err = relerr(runs[0][k].reshape(R, -1), ref[k].cpu().reshape(R, -1))
-        print(f"{precision} S {S} R {R} {name} {net} {k}: {err:.2e} of scale")
-        assert err < TOL, f"{k}: {err:.2e}"
-        for again in runs[1:]:
-            assert torch.equal(runs[0][k], again[k]), f"{k} differs between repeated launches"
+    compare_repeated(runs, _reference(net, S, R, name), TOL, f"{precision} S {S} R {R} {name} {net}")
 
 
 @pytest.mark.parametrize("name", list(PASSES))
@@ -133,10 +100,10 @@ def test_trained_like_weights(gpu, built_lib, S, R, name):
 
 @functools.lru_cache(maxsize=None)
 def _points_net(app):
-    """the fine network of tests/test_inerf_gpu.py::_points_case as fp32 GEMM chain and as fused kernels, built once"""
+    """(appearance row, the fine network as fp32 GEMM chain, the same as fused kernels), built once"""
     gpu = torch.device("cuda:0")
-    ren = _points_case(gpu, app, 1, 65, seed=41)[0]
-    return ren, inerf.FineField(ren.nerf_fine, gpu), inerf.FusedField(ren.nerf_fine, gpu)
+    ren, _, row = network("cambridge" if app else "7scenes", 41, calibrate=False)
+    return row, inerf.FineField(ren.nerf_fine, gpu), inerf.FusedField(ren.nerf_fine, gpu)
 
 
 SEEDS = {9: 7, 1: 37}  # bundles per ray count: 4095 and 2405 rows
@@ -153,47 +120,20 @@ def test_pointwise_pair_at_one_and_five_tiles(gpu, built_lib, app, R):
     L2 norm (measured: seeded bundles of 585 samples hold 0 to 3 such rows): a single launch of these sizes cannot resolve either bar.  So
     the launch is repeated on SEEDS[R] seeded bundles and both bars are taken over all their rows (4095 and 2405: no fewer than the 2405 of
     the smallest case of test_tapped_points_kernels_vs_gemm_chain); the forward bars and bit-equal repeats hold per launch."""
-    Sa, S, tap = 65, 128, 3
+    Sa, tap = 65, 3
     n = R * Sa
     assert -(-n // 128) == (1 if R == 1 else 5) and n % 128 != 0
-    ren, chain, fused = _points_net(app)
-    app_row = ren.embedding_a.weight[1].detach().float().contiguous() if app else None
+    app_row, chain, fused = _points_net(app)
     near, err2, ref2, total = [0, 0], [0.0, 0.0], [0.0, 0.0], 0
     for seed in range(SEEDS[R]):
-        g = torch.Generator().manual_seed(1000 * R + seed)
-        o = torch.randn(R, 3, generator=g) * 0.2  # (rays / fence posts as _points_case makes them)
-        d = torch.nn.functional.normalize(torch.randn(R, 3, generator=g), dim=-1)
-        rays = torch.cat([o, d, torch.full((R, 1), 0.01), torch.ones(R, 1), d, torch.full((R, 1), 0.002)], -1).to(gpu).contiguous()
-        z = torch.sort(torch.rand(R, S + 1, generator=g) * 0.9 + 0.05, dim=-1).values.to(gpu).contiguous()
-        xi, xd = inerf._encode(rays, z, Sa, app_row)
-        logit, sig, saved = chain.forward(xi, xd)
-        out4, gates, feats = fused.forward_rays(rays, z, Sa, app_row, tap)
-        h_ref = saved[0][tap]
-        assert (feats - h_ref).abs().max().item() < 1e-5 * max(1.0, h_ref.abs().max().item())
-        assert (out4[:, :3] - logit[:, :3]).abs().max().item() < 1e-5 * max(1.0, logit.abs().max().item())
-        assert (out4[:, 3] - sig[:, 0]).abs().max().item() < 1e-5 * max(1.0, sig.abs().max().item())
-        g_logit = torch.zeros(n, 8, device=gpu)
-        g_logit[:, :3] = torch.randn(n, 3, generator=g).to(gpu) * 1e-4
-        g_sig = torch.zeros(n, 8, device=gpu)
-        g_sig[:, 0] = torch.randn(n, generator=g).to(gpu) * 1e-5
-        w = torch.rand(R, Sa, generator=g).to(gpu) * 0.1
-        g_pf = torch.randn(R, 256, generator=g).to(gpu) * 1e-3
-        g_feats = (w.reshape(n, 1) * g_pf.repeat_interleave(Sa, 0)).contiguous()
-        gxi_ref, gxd_ref = chain.backward(g_logit, g_sig, saved, (tap, g_feats))
-        g4 = torch.cat([g_logit[:, :3], g_sig[:, :1]], 1).contiguous()
-        (a0, a5), gxd = fused.backward(g4, gates, (tap, w, g_pf))
-        for i, (got, want) in enumerate(((a0 + a5, gxi_ref), (gxd, gxd_ref))):  # (bars and their reasons: test_tapped_points_kernels_vs_gemm_chain)
-            assert torch.isfinite(got).all()
+        rays, z, g = points_bundle(R, 1000 * R + seed)
+        p = points_pair(fused, chain, rays, z, Sa, app_row, tap, g, repeats=2)
+        for i, (got, want) in enumerate(p.grads):  # (bars and their reasons: test_tapped_points_kernels_vs_gemm_chain)
             row = (got - want).abs().max(1).values / want.abs().max().item()
             near[i] += int((row <= 2e-4).sum().item())  # (of this launch's largest entry: no laxer than of the largest of all)
             err2[i] += float((got - want).double().pow(2).sum())
             ref2[i] += float(want.double().pow(2).sum())
         total += n
-        for _ in range(2):
-            out4_b, gates_b, feats_b = fused.forward_rays(rays, z, Sa, app_row, tap)
-            assert torch.equal(out4_b, out4) and torch.equal(gates_b, gates) and torch.equal(feats_b, feats)
-            (b0, b5), bxd = fused.backward(g4, gates, (tap, w, g_pf))
-            assert torch.equal(b0, a0) and torch.equal(b5, a5) and torch.equal(bxd, gxd)
     l2 = [(e / r) ** 0.5 for e, r in zip(err2, ref2)]
     print(f"pointwise pair app {app} R {R}: rows within 2e-4 of the chain's gradient: d xi {near[0]} / {total}, d xd {near[1]} / {total}; "
           f"all rows together, L2: d xi {l2[0]:.2e}, d xd {l2[1]:.2e}")

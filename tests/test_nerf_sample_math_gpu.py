@@ -16,8 +16,8 @@ import functools
 import pytest
 import torch
 
-from nerfmatch_amd import ops, synth
-from nerfmatch_amd.nerf.renderer import NerfRenderer
+from nerf_kernel_util import camera_rays, fence_posts, launch, renderer_for
+from nerfmatch_amd import synth
 
 pytestmark = pytest.mark.gpu
 R = 5
@@ -26,18 +26,14 @@ PASSES = (dict(tap_layer=7, need_rgb=True, need_feat=True), dict(tap_layer=-1, n
 
 @functools.lru_cache(maxsize=None)
 def _bias_only_nerf():
-    dev = torch.device("cuda:0")
-    ren = NerfRenderer(synth.nerf_config("7scenes", num_pts=64), training=False, stop_layer=3)
     sd = synth.nerf_state_dict(seed=11)
     for k in sd:
         if k.startswith("nerf_") and k.endswith(".weight"):
             sd[k] = torch.zeros_like(sd[k])
         if k.endswith("alpha_linear.bias"):
             sd[k] = torch.full_like(sd[k], 1.5)
-    ren.load_state_dict(sd, strict=True)
-    ren.to(dev).eval()
-    rays = ops.raygen(synth.intrinsics(), synth.camera_pose(2), 480, 640, dev)[0]
-    return ren.nerf_coarse, rays[:: rays.shape[0] // R][:R].contiguous()  # five rays spread over the image
+    rays = camera_rays(2)
+    return renderer_for("7scenes", sd, calibrate=False), rays[:: rays.shape[0] // R][:R].contiguous()  # five rays spread over the image
 
 
 @pytest.mark.parametrize("S", [32,    # four rays per tile, 32-lane segments
@@ -45,13 +41,10 @@ def _bias_only_nerf():
                                128,   # the cross-wavefront factor
                                256])  # two chunks: the carried transmittance
 def test_compositing_weights_bit_equal_across_kernels(S):
-    net, rays = _bias_only_nerf()
-    dev = rays.device
-    t = ops.sample_coarse(rays, synth.uniform01((R, S + 1), 300 + S).to(dev), S)
+    ren, rays = _bias_only_nerf()
+    t = fence_posts(rays, S, 300 + S)
     for kw in PASSES:
-        with torch.no_grad():
-            w = {p: ops.nerf_fwd(net.packed(dev, p), rays, t, **kw)["weights"] for p in ("fp32", "bf16x3", "fp16x3")}
-        assert not net.packed(dev, "fp16x3").nm_guard.read()[0], "an fp16x3 operand saturated: those weights are the fp32 kernel's"
+        w = {p: launch(ren, "coarse", p, rays, t, **kw)["weights"] for p in ("fp32", "bf16x3", "fp16x3")}  # (launch: the fp16x3 guard did not fire)
         acc = w["fp32"].sum(1)
         print(f"S={S} {kw}: weights in [{w['fp32'].min().item():.3e}, {w['fp32'].max().item():.3e}], per-ray sums {acc.tolist()}")
         assert (w["fp32"] > 0).float().mean() > 0.9 and (acc > 0.05).all() and (acc < 1.0).all()  # (not vacuous: real transmittances)

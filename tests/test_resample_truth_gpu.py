@@ -16,8 +16,7 @@ import torch
 
 from conftest import load_golden
 from nerfmatch_amd import ops
-from test_nerf_gpu import make_renderer
-from test_surface_seeds_gpu import SEEDS
+from nerf_kernel_util import SURFACE_SEEDS as SEEDS, make_renderer
 
 pytestmark = pytest.mark.gpu
 F32_EPS = float(torch.finfo(torch.float32).eps)

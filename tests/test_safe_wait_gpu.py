@@ -24,7 +24,7 @@ def workloads():
     from nerfmatch_amd import ops, synth
     from nerfmatch_amd.matcher import NeRFMatcherMS
     from nerfmatch_amd.modules import PrecomputedBackbone
-    from test_nerf_gpu import make_renderer
+    from nerf_kernel_util import make_renderer
 
     torch.set_grad_enabled(False)
     gpu = torch.device("cuda:0")
