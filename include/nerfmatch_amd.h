@@ -682,7 +682,12 @@ int nm_fine_expectation_bwd(const float* pt_f, const float* win_f, const float* 
  * acc and writes row_t[M] / col_t[N];  loss = acc[0]/acc[2] + acc[1]/acc[3].  nm_match_focal_loss_bwd (same workspace
  * contents) writes ddot[M,N] = grad_loss * d loss / d (im_n . pt_n) and adds d loss / d scale to *dscale (double, may be
  * NULL); grad_loss is a device scalar (NULL = 1).  clamp != 0: conf is clamped to [1e-6, 1 - 1e-6] first (c2f model);
- * clamp == 0: not (NeRFMatcherCoarse.forward_with_metrics, nerfmatch_coarse_trainer.py:380). */
+ * clamp == 0: not (NeRFMatcherCoarse.forward_with_metrics, nerfmatch_coarse_trainer.py:380) -- a positive at conf == 0 (a masked entry) is then
+ * log 0, an infinite loss and NaN gradients, as in the reference.  A conf_gt byte above 1 is in neither mean and neither count and has
+ * t = 0; its ddot is the soft-max coupling alone.  conf_gt, pt_mask and N need no alignment (4-byte aligned pointers and N % 4 == 0 take
+ * the faster kernels).  row_t, col_t, ddot and the loss sums are the same bytes on every call when N % 4 == 0, conf_gt is 4-byte aligned
+ * and the partial sums fit the workspace (4 nx M rounded up to 256, plus 1024 nx, at most 256 N bytes, nx = ceil(N / 256): not for a tall,
+ * narrow pair such as 300 x 8); otherwise col_t and the loss sums are accumulated with atomics.  *dscale always is. */
 int nm_focal_count(const uint8_t* conf_gt, size_t total, double* acc, nmStream_t stream);
 int nm_match_focal_loss(const uint8_t* conf_gt, int M, int N, int C, float alpha, float gamma, int clamp, void* workspace,
                         size_t workspace_bytes, double* acc, float* row_t, float* col_t, nmStream_t stream);

@@ -318,8 +318,10 @@ class _CoarseMatchLoss(Function):
         im_c, pt_c, imn, ptn, gt, acc, row_t, col_t = ctx.saved_tensors
         B, M, Cc = im_c.shape
         N = pt_c.shape[1]
-        if N % 8 != 0:
-            raise _lib.NerfmatchAmdError("the matching-loss backward needs a multiple of 8 point tokens")
+        if N % 8 != 0:  # (nm_match_focal_loss_bwd itself takes any N: tests/test_match_routes_gpu.py case c)
+            raise _lib.NerfmatchAmdError(f"the matching-loss backward needs a multiple of 8 point tokens, got {N}: d_imn = ddot @ pt_n is "
+                                         "ops.linear with K = N, and nm_linear slices K into 8-wide pieces (ops.linear_wgrad, behind "
+                                         "d_ptn, would take N % 4 == 0; the loss kernels any N)")
         dev = im_c.device
         L = lib()
         im_m, pt_m = ctx.masks

@@ -710,6 +710,7 @@ extern "C" int nm_dual_softmax_match(const float* im, const float* pt, int M, in
   if ((flags & NM_MATCH_BF16X3) && N % 8 == 0) rc = nm_internal_sim_bf16x3(imn, ptn, M, N, C, scale, im_mask, pt_mask, w.sim, w.blob, s);
   else rc = nm_internal_sim(imn, ptn, M, N, C, scale, im_mask, pt_mask, w.sim, s);
   if (rc != NM_OK) return rc;
+  // (dispatch restated for the tests as route() in tests/match_loss_util.py: keep the two in step)
   const bool vec = (N % 4 == 0);
   const bool cached = vec && N <= 64 * 4 * ROW_NREG;
   if (cached) row_stats_kernel<4, ROW_NREG><<<(M + 3) / 4, 256, 0, s>>>(w.sim, M, N, w.rmax, w.rsum);
@@ -750,6 +751,7 @@ extern "C" int nm_match_focal_loss(const uint8_t* conf_gt, int M, int N, int C, 
   if (workspace_bytes < w.bytes) return NM_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   // one pass + merge when the partial sums fit the two column-statistics scratch areas of the workspace (free since the statistics were merged)
+  // (dispatch restated for the tests as route() in tests/match_loss_util.py: keep the two in step)
   const int nx = (N + 255) / 256;
   const size_t cap = (size_t)COL_CHUNKS * N * 4;
   if (N % 4 == 0 && ((size_t)conf_gt & 3) == 0 && align256((size_t)nx * M * 4) + (size_t)nx * COL_CHUNKS * 16 <= cap) {
@@ -774,6 +776,7 @@ extern "C" int nm_match_focal_loss_bwd(const uint8_t* conf_gt, const uint8_t* im
   NM_CHECK_ARG(conf_gt && workspace && acc && row_t && col_t && ddot && M > 0 && N > 0 && C > 0 && scale != 0.f);
   Workspace w = carve(workspace, M, N, C);
   if (workspace_bytes < w.bytes) return NM_ERR_WORKSPACE;
+  // (dispatch restated for the tests as route() in tests/match_loss_util.py: keep the two in step)
   if (N % 4 == 0 && ((size_t)conf_gt & 3) == 0 && (!pt_mask || ((size_t)pt_mask & 3) == 0))
     focal_bwd_kernel<4><<<(M + 3) / 4, 256, 0, (hipStream_t)stream>>>(w.sim, conf_gt, im_mask, pt_mask, M, N, w.rmax, w.rsum, w.cmax, w.csum,
                                                                       alpha, gamma, clamp, scale, grad_loss, acc, row_t, col_t, ddot, dscale);
