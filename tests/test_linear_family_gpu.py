@@ -142,7 +142,9 @@ def test_gelu_routes_at_probe_values(gpu, built_lib):
     """The exact-erf GELU is written three times (train.hip, gemm.hip, gemm_bf16.hip).  One column of probes -- zeros of both signs, the
     linear range, the tails where 1 + erf cancels, and arguments far outside erff's table -- through ops.gelu, ops.gelu_bwd (dh = 1) and
     ops.linear(act=GELU) with an identity weight, against float64 0.5 u (1 + erf(u / sqrt 2)) and its derivative Phi(u) + u phi(u).
-    Bar: 1e-6 absolute; on the split path the operand itself carries 2^-16 |u| (x = hi + lo in bf16)."""
+    Bar: 1e-6 absolute; on the split path the operand itself carries 2^-16 |u| (x = hi + lo in bf16).
+    (A fourth and a fifth form, the chained kernels' polynomial gelu_erf of bf16x3.h and gelu_grad of encoder_tail_bwd.hip, see the same
+    probes in test_encoder_tail_stages_gpu.py and test_fine_layer_stages_gpu.py.)"""
     probes = [0.0, -0.0, 1e-8, -1e-8, 0.5, -0.5, 3.0, -3.0, 6.0, -6.0, 12.0, -12.0, 40.0, -40.0, 1e4]
     u = torch.tensor(probes, dtype=torch.float32).repeat(8)  # 120 values = 15 rows of the K = 8 identity product
     u64 = u.double()

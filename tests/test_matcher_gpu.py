@@ -871,6 +871,7 @@ def test_fine_window_layer_one_launch_vs_generic_kernels(gpu, built_lib, K, coun
     """nm_fine_window_layer (round 5: window gather + the fine self-attention encoder layer in one launch on the matrix cores) against the
     window gather followed by the generic layer kernels (LayerNorm, GEMMs, small attention), and against torch's own modules in fp64: windows
     that hang over the map's border (zero padding), several maps, a device count below the slot count, a ragged last workgroup."""
+    from chain_kernel_util import fine_layer_fp64
     from nerfmatch_amd.modules.attention import SelfAttentionBlock
 
     g = torch.Generator().manual_seed(K + B)
@@ -900,18 +901,7 @@ def test_fine_window_layer_one_launch_vs_generic_kernels(gpu, built_lib, K, coun
         assert torch.isfinite(got[:count]).all()
         assert (got[:count] - ref[:count]).abs().max().item() < 2e-5 * scale, ((got[:count] - ref[:count]).abs().max().item(), scale)
         # fp64 evaluation of the same layer with torch ops
-        l = block.layers[0]
-        x = win[:count].double()
-        ln = lambda t, m: torch.nn.functional.layer_norm(t, (128,), m.weight.double(), m.bias.double(), m.eps)
-        xh = ln(x, l.norm1[0])
-        at = l.attention
-        q, k_, v = (xh @ w.weight.double().T for w in (at.proj_q, at.proj_k, at.proj_v))
-        sp = lambda t: t.reshape(count, 25, 8, 16).transpose(1, 2)
-        att = torch.softmax(sp(q) @ sp(k_).transpose(-1, -2) * at.attend.scale(), -1) @ sp(v)
-        a_ = xh + att.transpose(1, 2).reshape(count, 25, 128) @ at.proj_out[0].weight.double().T
-        ff = l.feedforward
-        h1 = torch.nn.functional.gelu(ln(a_, l.norm2) @ ff.layers[0].weight.double().T + ff.layers[0].bias.double())
-        y = xh + h1 @ ff.layers[2].weight.double().T + ff.layers[2].bias.double()
+        y = fine_layer_fp64(win[:count], block)
         e64 = (got[:count].double() - y).abs().max().item() / y.abs().max().item()
         print(f"fine window layer K={K} count={count} B={B}: |one launch - generic| {(got[:count] - ref[:count]).abs().max().item() / scale:.2e}, |one launch - fp64| {e64:.2e} of the largest entry")
         assert e64 < 1e-5
