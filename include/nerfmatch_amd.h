@@ -372,6 +372,37 @@ int nm_raybank_gather(const uint8_t* images, const uint8_t* masks, const float* 
                       long long pos0, long long pos_stride, int n, int norm_ray_dir, float near_plane, float* rays, float* rgbs, long long* ts,
                       float* mask, int* bad, nmStream_t stream);
 
+/* ---- Reference point sets from a device-resident scene cache (csrc/ref_bank.hip) ----------------------------------------------
+ * Replaces NeRFMatchMultiPair.load_ref_pts (nerfmatch/datasets/nerfmatch_dataset.py:441-518) with its reader load_frame_3d
+ * (nerfmatch/datasets/data_loading.py:36-80): k cache files unpickled and stacked per query, k projections of all k n points, the
+ * co-visibility rule, a randperm draw and a copy to the device.  The bank: pt3d [F,n,3] world, pt_feat [F,n,D], pt_mask [F,n] uint8,
+ * cams [F,21] = row-major diag(W / w_f, H / h_f, 1) K_f (9; :486-490) | rows 0..2 of the world-to-camera matrix (12) -- all on the
+ * device.  ref_ids [B,k] int64 (device): the frames of each query; candidate c = s n + r of query b is row r of frame ref_ids[b,s].
+ * A frame id outside [0, F) is clamped into the bank by every kernel and counted by nm_refbank_gather.
+ * Limits (NM_ERR_UNSUPPORTED beyond): k <= 32, k n <= 2^20, P <= 2^20, D % 4 == 0, D <= 1024; B <= 65535.
+ * nerfmatch_amd.ref_bank states the rule in torch. */
+
+/* words [B,k n] uint32: bit j of a candidate's word is set iff its projection into camera j of its query's row satisfies
+ * x >= 0 && y >= 0 && x < img_w && y < img_h (:498): p = R X + t, q = p / p.z, pix = K q in fp32 in nm_gt_supervision's operation order,
+ * no contraction; no depth test; a projection that is not finite sets no bit.  One thread per (query, candidate). */
+int nm_refbank_visibility(const float* pt3d, const float* cams, const long long* ref_ids, int F, int n, int B, int k, int img_w, int img_h,
+                          uint32_t* words, nmStream_t stream);
+
+/* The co-visibility rule (:478, :499-506), one workgroup per query over its N = k n words.  visible = all; for j = 0 .. k-1:
+ * I = |visible & bit_j|, V = |visible|; visible = visible | bit_j if 3 I < V, else visible & bit_j.  decisions [B] int32: bit j = 1 where
+ * the union was taken; n_visible [B] int32 = Nv >= 1; list [B,N] int32: the visible candidates in ascending order, then -1. */
+int nm_refbank_select(const uint32_t* words, int B, int k, int N, int* list, int* n_visible, int* decisions, nmStream_t stream);
+
+/* Output row q of query b (one wavefront each): candidate list[b, perm_b(q mod Nv)], Nv = n_visible[b] (:509-516 with the randperm replaced):
+ * perm_b is nm_raybank_gather's permutation of [0, Nv) with the 4 round keys perm_keys[b] (device uint32 [B,4]; derived by the caller)
+ * and 2 * half_bits = the smallest even number of bits with 2^bits >= Nv, taken from Nv on the device.  list == NULL (then P == k n;
+ * n_visible and perm_keys unused): row q is candidate q, the stacked layout of :585-590.
+ * out_pt3d [B,P,3], out_feat [B,P,D] (bank and output feature rows are copied as 16-byte vectors: both bases 16-byte aligned),
+ * out_mask [B,P] uint8.  *bad (device int, add-only; zeroed by the caller) += the entries of ref_ids outside [0, F). */
+int nm_refbank_gather(const float* pt3d, const float* pt_feat, const uint8_t* pt_mask, const long long* ref_ids, int F, int n, int D, int B,
+                      int k, const int* list, const int* n_visible, const uint32_t* perm_keys, int P, float* out_pt3d, float* out_feat,
+                      uint8_t* out_mask, int* bad, nmStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Matcher half
  * ---------------------------------------------------------------------------------------------- */

@@ -85,6 +85,10 @@ SIGNATURES = {
     "nm_raybank_frame_flags": (i32, [vp, i32, i32, i32, vp, vp]),
     "nm_raybank_gather": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, C.c_longlong, C.POINTER(C.c_uint32), i32, C.c_longlong, C.c_longlong,
                                 i32, i32, f32, vp, vp, vp, vp, vp, vp]),
+    # reference point sets from a device-resident scene cache (ref_bank.hip)
+    "nm_refbank_visibility": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "nm_refbank_select": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    "nm_refbank_gather": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     "nm_linear": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "nm_linear_blob_bytes_bf16x3": (sz, [i32, i32]),
     "nm_linear_qkv_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -5,12 +5,13 @@
 // ~60 flops per ray, 3 + 84 (L2-shared per frame) + 4 bytes read, 48 + 12 + 8 (+ 4) bytes written.  The per-pixel expressions are
 // those of nm_raygen (ray_pixel.h).
 #include "common.h"
+#include "perm.h"
 #include "ray_pixel.h"
 #include <limits.h>
 
 namespace {
 
-constexpr int RB_ROUNDS = 4;  // Feistel rounds of the epoch permutation
+constexpr int RB_ROUNDS = NM_PERM_ROUNDS;  // Feistel rounds of the epoch permutation (perm.h)
 
 struct RayBankArgs {
   const uint8_t* images;       // [F,H,W,3]
@@ -39,19 +40,6 @@ __device__ __forceinline__ void load_pose(const float* __restrict__ cams, long l
   for (int i = 0; i < 9; ++i) pz.kinv[i] = c[i];
 #pragma unroll
   for (int i = 0; i < 12; ++i) pz.c2w[i] = c[9 + i];
-}
-
-// one pass of the keyed bijection of [0, 2^(2 half_bits)): a balanced Feistel network whose round function is nm_mix32
-__device__ __forceinline__ unsigned long long feistel(unsigned long long x, const uint32_t (&keys)[RB_ROUNDS], int hb) {
-  const uint32_t m = (1u << hb) - 1u;
-  uint32_t l = (uint32_t)(x >> hb), r = (uint32_t)x & m;
-#pragma unroll
-  for (int k = 0; k < RB_ROUNDS; ++k) {
-    const uint32_t t = l ^ (nm_mix32(r + keys[k]) & m);
-    l = r;
-    r = t;
-  }
-  return ((unsigned long long)l << hb) | r;
 }
 
 // One thread per pixel of frame f0 + blockIdx.y: the frame's flag is raised when ANY pixel's discriminant is not >= 0 (one atomic per
@@ -84,10 +72,7 @@ __global__ void __launch_bounds__(256) raybank_gather_kernel(RayBankArgs a) {
       pos = pos < 0 ? 0 : a.n_src - 1;
     }
     // cycle walking: the walk from a point below n_src stays on that point's own cycle, which contains it -- it terminates
-    unsigned long long x = (unsigned long long)pos;
-    do x = feistel(x, a.keys, a.half_bits);
-    while (x >= (unsigned long long)a.n_src);
-    j = (long long)x;
+    j = (long long)nm_perm_walk((unsigned long long)pos, (unsigned long long)a.n_src, a.keys, a.half_bits);
   }
   if (j < 0 || j >= a.n_src) {
     bad = true;

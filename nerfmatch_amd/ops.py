@@ -326,6 +326,48 @@ def raybank_gather(images, cams, flags, ts_table, bad, n, ids=None, perm=None, p
     return rays, rgbs, ts, mask
 
 
+def refbank_select(pt3d, cams, ref_ids, img_wh):
+    """The co-visibility rule of a reference point bank (pt3d (F,n,3), cams (F,21) = scaled K | w2c rows 0..2) for the id rows ref_ids
+    (B,k) int64 on the device, at the target resolution img_wh = (W, H): nm_refbank_visibility + nm_refbank_select -> words (B,k n) int32
+    (the uint32 visibility words' bits), list (B,k n) int32 (the visible candidates in ascending order, then -1), n_visible (B,) int32,
+    decisions (B,) int32.  No host synchronisation."""
+    F, n, _ = pt3d.shape
+    B, k = ref_ids.shape
+    assert pt3d.shape == (F, n, 3) and cams.shape == (F, 21)
+    N, dev = k * n, pt3d.device
+    words = torch.empty(B, N, device=dev, dtype=torch.int32)
+    lst = torch.empty(B, N, device=dev, dtype=torch.int32)
+    n_visible = torch.empty(B, device=dev, dtype=torch.int32)
+    decisions = torch.empty(B, device=dev, dtype=torch.int32)
+    st = stream()
+    check(lib().nm_refbank_visibility(dptr(pt3d), dptr(cams), dptr(ref_ids, torch.int64), F, n, B, k, int(img_wh[0]), int(img_wh[1]),
+                                      dptr(words, torch.int32), st), "nm_refbank_visibility")
+    check(lib().nm_refbank_select(dptr(words, torch.int32), B, k, N, dptr(lst, torch.int32), dptr(n_visible, torch.int32),
+                                  dptr(decisions, torch.int32), st), "nm_refbank_select")
+    return dict(words=words, list=lst, n_visible=n_visible, decisions=decisions)
+
+
+def refbank_gather(pt3d, pt_feat, pt_mask, ref_ids, bad, rows, select=None, perm_keys=None, out=None):
+    """nm_refbank_gather: `rows` output rows per query of a reference point bank (pt3d (F,n,3), pt_feat (F,n,D), pt_mask (F,n) bool) for
+    the id rows ref_ids (B,k) int64 on the device -> pt3d (B,rows,3), pt_feat (B,rows,D), pt_mask (B,rows) bool.  select = refbank_select's
+    dict with perm_keys (B,4) int32 (the round keys' bits): row q is candidate list[perm(q mod Nv)]; select=None: row q is candidate q
+    (rows == k n).  bad: device int32[1] counter of clamped frame ids (add-only).  out: (pt3d, pt_feat, pt_mask) to write into."""
+    F, n, D = pt_feat.shape
+    B, k = ref_ids.shape
+    assert pt3d.shape == (F, n, 3) and pt_mask.shape == (F, n) and (select is None) == (perm_keys is None)
+    dev = pt3d.device
+    if out is None:
+        out = (torch.empty(B, rows, 3, device=dev), torch.empty(B, rows, D, device=dev), torch.empty(B, rows, device=dev, dtype=torch.bool))
+    o3, of, om = out
+    assert o3.shape == (B, rows, 3) and of.shape == (B, rows, D) and om.shape == (B, rows) and om.dtype == torch.bool
+    lst, nv = (None, None) if select is None else (select["list"], select["n_visible"])
+    assert select is None or (lst.shape == (B, k * n) and perm_keys.shape == (B, 4))
+    check(lib().nm_refbank_gather(dptr(pt3d), dptr(pt_feat), dptr(pt_mask.view(torch.uint8), torch.uint8), dptr(ref_ids, torch.int64), F, n, D,
+                                  B, k, dptr(lst, torch.int32), dptr(nv, torch.int32), dptr(perm_keys, torch.int32), int(rows), dptr(o3),
+                                  dptr(of), dptr(om.view(torch.uint8), torch.uint8), dptr(bad, torch.int32), stream()), "nm_refbank_gather")
+    return o3, of, om
+
+
 # ----------------------------------------------------------------------------- matcher half
 # Arithmetic of the nn.Linear layers: "fp32" (v_mfma_f32_32x32x2_f32, nm_linear) or "bf16x3" (bf16 MFMA on hi/lo-split
 # operands, fp32-accurate, nm_linear_bf16x3).  Module-level switch like ATTENTION_PRECISION.
