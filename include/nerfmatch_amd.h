@@ -540,7 +540,21 @@ int nm_cat_fourier_bwd(const float* dy, const float* pt3d, int n, int C, int num
  * modules/extract_matches.py:21-36.
  *   im [P,M,C], pt [P,N,C], im_mask [P,M] / pt_mask [P,N] uint8 or NULL; out_i / out_j / out_conf [P,M] (valid prefix:
  *   counts[p]; the slots behind it are written as index 0 / confidence 0); C in {64,128,256,512}; |scale| log2(e) <= 60 (cosine similarities are bounded by |scale|: one fixed shift
- *   serves both soft-maxes) -- otherwise NM_ERR_UNSUPPORTED: use nm_dual_softmax_match per pair. */
+ *   serves both soft-maxes) -- otherwise NM_ERR_UNSUPPORTED: use nm_dual_softmax_match per pair.
+ * What tests/test_match_fused_routes_gpu.py pins down (case table: tests/match_fused_util.py):
+ *   - selection is the reference's mask on EQUAL BITS: row i is matched iff conf[i, j] > threshold (strictly) for a column j that attains the
+ *     row maximum (and, mutual != 0, the maximum of column j); among several such columns the FIRST one is returned.  Bit-identical point rows
+ *     get bit-identical confidences wherever their columns sit (so do bit-identical image rows), so the lowest unmasked copy is the answer;
+ *   - out_i is strictly increasing within a pair; every slot of out_i / out_j / out_conf at or behind counts[p] holds 0 / 0 / 0.0f, so the
+ *     buffers may be read as indices before the counts are known;
+ *   - the masks are bytes, [P][M] and [P][N], 0 = masked; a masked entry is the reference's fill of -1e9 before both soft-maxes: conf 0, except
+ *     that a row AND column without any unmasked entry meet in the uniform value (1/M)(1/N) -- with one side entirely masked every row returns
+ *     column 0 at that confidence (threshold permitting);
+ *   - scale has either sign (the reference's temp_type "div" arrives as 1 / temperature); fabsf(scale) * log2(e), evaluated in float, must be
+ *     <= 60 (the largest such float is accepted, the next one, NaN and infinities are not); P <= 65535; anything else NM_ERR_UNSUPPORTED, and
+ *     like every error it is returned before anything is written;
+ *   - the workspace needs no initialisation and keeps no state between calls: nm_match_fused_workspace_bytes(P, M, N, C) bytes of any content,
+ *     one byte less is NM_ERR_WORKSPACE; pair p of a batch returns the bits it returns alone. */
 size_t nm_match_fused_workspace_bytes(int P, int M, int N, int C);
 int nm_dual_softmax_match_fused(const float* im, const float* pt, int P, int M, int N, int C, float scale, const uint8_t* im_mask,
                                 const uint8_t* pt_mask, float threshold, int mutual, int64_t* out_i, int64_t* out_j,

@@ -19,6 +19,9 @@
 //   compact    ordered compaction per pair
 // Every conf value comes out of the same inlined expression on bit-identical accumulators (the tile code is one function), so
 // the equality tests compare equal bits exactly like the reference's `conf == conf.max()`.
+// Tests: tests/test_match_fused_routes_gpu.py runs the case table of tests/match_fused_util.py (tile-map, compaction, batch, tie, threshold,
+// scale and feature-width edges; tests/test_match_fused_util_cpu.py checks without a GPU that each case reaches the edge it names).  The
+// table restates FT, the tile map of match_tile_kernel and the lane / register position of a column: keep them in step.
 // The same packer and tile K-loop also serve nm_feature_mutual_nn at the end of this file: cosine mutual nearest neighbours of two
 // descriptor sets (the reference's mutual_nn_matching) in ONE tile pass.
 #include "bf16x3.h"
@@ -155,7 +158,8 @@ __device__ __forceinline__ float conf_value(float e, float ics, float irs, float
 // instructions for 64 columns (2 v_cndmask + 1 DPP op per pair; the 16 <-> 16 step is gfx950's v_permlane16_swap + 1 op) against
 // 320 for five DPP steps on every register.  Steps: lane ^ 1, lane ^ 2 (quad_perm), rotate by 4 and by 8 within the row of 16
 // (a rotation is not an involution, but bits 0..1 [0..2] of sender and receiver agree, which is all the pairing needs, and the
-// two receivers of a register cover its four [two] sources once), rows 0 <-> 1 / 2 <-> 3.
+// two receivers of a register cover its four [two] sources once; a SUM rotates by 4 in both directions, halve_sum_ror4 below),
+// rows 0 <-> 1 / 2 <-> 3.
 // Result: out[j] = the reduction of value index i = 32 j + (lane & 31), i.e. of acc[i >> 4][i & 15].
 template <int CTRL>
 __device__ __forceinline__ float dpp_read(float x) {
@@ -179,6 +183,25 @@ __device__ __forceinline__ void halve(const float* in, float* out, bool bit) {
     out[j] = red2<MAX>(keep, dpp_read<CTRL>(send));
   }
 }
+// The rotate-by-4 step of a SUM.  With one rotation for all lanes the register kept by lanes with bit 2 clear adds the row's quads as
+// (q0 + q3) + (q2 + q1) and the one kept by lanes with bit 2 set as (q1 + q0) + (q3 + q2): the rounding of a column sum depended on bit 3 of
+// the column's number, and two bit-identical points eight columns apart got reciprocal sums one ulp apart -- conf no longer equal bits, the
+// first-column rule void (tests/match_fused_util.py, layout "other-class").  Here the two lane classes rotate in opposite directions (each
+// DPP move enabled for its two banks of four lanes), so both registers pair the quads alike, {q0, q1} and {q2, q3}: a column's sum is the
+// same expression wherever the column sits (two moves and an add per pair where the single rotation is one DPP add: 16 more VALU
+// instructions in a pass-1 tile).  A maximum is exact in any order and keeps the single rotation.
+template <int NOUT>
+__device__ __forceinline__ void halve_sum_ror4(const float* in, float* out, bool bit) {
+#pragma unroll
+  for (int j = 0; j < NOUT; ++j) {
+    const float x = in[2 * j], y = in[2 * j + 1];
+    const float keep = bit ? y : x;
+    const int send = __builtin_bit_cast(int, bit ? x : y);
+    int got = __builtin_amdgcn_mov_dpp(send, 0x124, 0xf, 0xa, false);          // row_ror:4 into banks 1 and 3 (lanes with bit 2 set)
+    got = __builtin_amdgcn_update_dpp(got, send, 0x12C, 0xf, 0x5, false);      // row_ror:12 into banks 0 and 2
+    out[j] = keep + __builtin_bit_cast(float, got);
+  }
+}
 template <int MAX>
 __device__ __forceinline__ void column_reduce(const f32x16 (&acc)[4], int lane, float (&out)[2]) {
   float v[64], w1[32], w2[16], w3[8], w4[4];
@@ -186,7 +209,8 @@ __device__ __forceinline__ void column_reduce(const f32x16 (&acc)[4], int lane, 
   for (int i = 0; i < 64; ++i) v[i] = acc[i >> 4][i & 15];
   halve<MAX, 0xB1, 32>(v, w1, lane & 1);    // quad_perm:[1,0,3,2]
   halve<MAX, 0x4E, 16>(w1, w2, lane & 2);   // quad_perm:[2,3,0,1]
-  halve<MAX, 0x124, 8>(w2, w3, lane & 4);   // row_ror:4
+  if constexpr (MAX == 0) halve_sum_ror4<8>(w2, w3, lane & 4);
+  else halve<MAX, 0x124, 8>(w2, w3, lane & 4);   // row_ror:4
   halve<MAX, 0x128, 4>(w3, w4, lane & 8);   // row_ror:8
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
