@@ -663,7 +663,8 @@ int nm_fine_expectation(const float* pt_f, const float* win_f, const int* count,
 
 /* nn.Linear weight gradient dw[N,K] (+)= dy[M,N]^T . x[M,K] (fp32 matrix cores; row slices summed in a fixed order).
  * workspace: nm_linear_wgrad_workspace_bytes(M,N,K) bytes (may be NULL when the whole of M fits one slice and
- * accumulate == 0: NM_ERR_WORKSPACE is returned when it was needed). */
+ * accumulate == 0: NM_ERR_WORKSPACE is returned when it was needed).  N and K multiples of 4, dy / x / dw on 16-byte boundaries
+ * (rows move in 16-byte pieces), else NM_ERR_UNSUPPORTED. */
 size_t nm_linear_wgrad_workspace_bytes(int M, int N, int K);
 int nm_linear_wgrad(const float* dy, const float* x, int M, int N, int K, int accumulate, float* dw, void* workspace,
                     size_t workspace_bytes, nmStream_t stream);

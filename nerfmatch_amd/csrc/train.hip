@@ -475,7 +475,7 @@ extern "C" size_t nm_linear_wgrad_workspace_bytes(int M, int N, int K) {
 extern "C" int nm_linear_wgrad(const float* dy, const float* x, int M, int N, int K, int accumulate, float* dw, void* workspace,
                                size_t workspace_bytes, nmStream_t stream) {
   NM_CHECK_ARG(dy && x && dw && M > 0 && N > 0 && K > 0);
-  if (N % 4 != 0 || K % 4 != 0) return NM_ERR_UNSUPPORTED;  // 16-byte row pieces
+  if (N % 4 != 0 || K % 4 != 0 || ((size_t)dy & 15) || ((size_t)x & 15) || ((size_t)dw & 15)) return NM_ERR_UNSUPPORTED;  // 16-byte row pieces
   hipStream_t s = (hipStream_t)stream;
   const int tiles = ((N + 63) / 64) * ((K + 63) / 64);
   // enough workgroups to fill 256 CUs twice over, slices of at least 256 rows (64 per wavefront)

@@ -675,6 +675,8 @@ def attention_projected(x_q, w_q, x_kv, w_stack, B, L, S, heads, scale):
 def nchw_to_tokens(x, pe_table=None):
     """(B,C,h,w) -> (B,h*w,C), optionally adding the sine PE table (C,Hmax,Wmax)."""
     x = x.contiguous()
+    if pe_table is not None:
+        pe_table = pe_table.contiguous()
     B, Cc, h, w = x.shape
     y = torch.empty(B, h * w, Cc, device=x.device, dtype=torch.float32)
     th, tw = (pe_table.shape[1], pe_table.shape[2]) if pe_table is not None else (0, 0)
@@ -684,7 +686,10 @@ def nchw_to_tokens(x, pe_table=None):
 
 def feature_normalize(x):
     """x (B,N,D) is centred IN PLACE (per set b: minus the mean over its N rows); returns the centred set divided by its largest row norm
-    (nm_feature_normalize; the coarse model's `pt_feat_norm` option)."""
+    (nm_feature_normalize; the coarse model's `pt_feat_norm` option).  x must be contiguous: a silent copy would be centred instead of the
+    caller's tensor."""
+    if not x.is_contiguous():
+        raise _lib.NerfmatchAmdError("feature_normalize centres x in place: hand over a contiguous tensor")
     B, N, D = x.shape
     y = torch.empty_like(x)
     check(lib().nm_feature_normalize(dptr(x), B, N, D, dptr(y), stream()), "nm_feature_normalize")
@@ -693,6 +698,7 @@ def feature_normalize(x):
 
 def cat_fourier(feat, pt3d, num_freqs=15):
     """(n,C),(n,3) -> (n, ld) = [feat | x | sin/cos(2^f x)...] zero padded to a multiple of 8 columns."""
+    feat, pt3d = feat.contiguous(), pt3d.contiguous()
     n, Cc = feat.shape
     ld = ((Cc + 3 + 6 * num_freqs + 7) // 8) * 8
     out = torch.empty(n, ld, device=feat.device, dtype=torch.float32)
@@ -890,6 +896,7 @@ def fine_windows_batch(ffeat, map_ids, i_ids, count, win=5, stride=4):
 
 def assemble_matches(pt2d, pt3d, i_ids, j_ids, expec_f, mconf, win, fine_ds):
     """One pair's match assembly in one launch (nm_assemble_matches): -> mpt2d_c (K,2), mpt2d_f (K,2), mpt3d (K,3), pred_mask (K,) bool."""
+    pt2d, pt3d, i_ids, j_ids, expec_f, mconf = (t.contiguous() for t in (pt2d, pt3d, i_ids, j_ids, expec_f, mconf))
     K, dev = i_ids.shape[0], pt2d.device
     c2, f2, p3 = (torch.empty(K, 2, device=dev), torch.empty(K, 2, device=dev), torch.empty(K, 3, device=dev))
     mask = torch.empty(K, device=dev, dtype=torch.bool)
@@ -998,6 +1005,7 @@ def fine_pt_proj(src, ids, count, lin0, lin1):
 
 
 def gather_rows(src, ids, count):
+    """out[k] = src[ids[k]] for the slots k < count (a device int32); slots k >= count are NOT written: they hold whatever the fresh buffer held."""
     K, dim = ids.shape[0], src.shape[1]
     out = torch.empty(K, dim, device=src.device, dtype=torch.float32)
     if K:

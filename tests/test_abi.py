@@ -41,6 +41,18 @@ def test_argument_validation_without_gpu(built_lib):
     assert h.nm_sample_coarse(null, null, 4, 32, null, null) == 1
     assert h.nm_nerf_fwd(null, null, null, null, 1, 32, 0, 0, -1.0, 0, null, null, null, null, null, null, null, null, null) == 1
     assert h.nm_linear(null, null, null, null, null, null, 4, 4, 8, 0, null, null) == 1
+    # the weight-gradient kernels move 16-byte row pieces (the split-bf16 one 8-byte pieces of dy): misaligned operands are refused
+    buf = (C.c_char * 256)()
+    base = (C.addressof(buf) + 15) & ~15
+    p, off4, off8 = C.c_void_p(base), C.c_void_p(base + 4), C.c_void_p(base + 8)
+    for dy, x, dw in ((off4, p, p), (p, off4, p), (p, p, off4), (off8, p, p), (p, off8, p), (p, p, off8)):
+        assert h.nm_linear_wgrad(dy, x, 8, 4, 4, 0, dw, null, 0, null) == _lib.NM_ERR_UNSUPPORTED
+    assert h.nm_linear_wgrad(p, p, 8, 6, 4, 0, p, null, 0, null) == _lib.NM_ERR_UNSUPPORTED  # N not a multiple of 4
+    assert h.nm_linear_wgrad(null, p, 8, 4, 4, 0, p, null, 0, null) == 1
+    assert h.nm_linear_wgrad(p, p, 8, 4, 4, 1, p, null, 0, null) == 4  # aligned: the next check in line (accumulate needs a workspace)
+    for dy, x, dw in ((off4, p, p), (p, off8, p), (p, p, off8)):
+        assert h.nm_linear_wgrad_bf16x3(dy, x, 8, 4, 4, 0, dw, null, null, 0, null) == _lib.NM_ERR_UNSUPPORTED
+    assert h.nm_linear_wgrad_bf16x3(off8, p, 8, 4, 4, 1, p, null, null, 0, null) == 4  # dy needs 8 bytes only
 
 
 def test_library_of_another_abi_version_is_refused(built_lib, monkeypatch):
