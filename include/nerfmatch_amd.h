@@ -403,6 +403,28 @@ int nm_refbank_gather(const float* pt3d, const float* pt_feat, const uint8_t* pt
                       int k, const int* list, const int* n_visible, const uint32_t* perm_keys, int P, float* out_pt3d, float* out_feat,
                       uint8_t* out_mask, int* bad, nmStream_t stream);
 
+/* ---- Pillow-exact Lanczos resize of 8-bit images (csrc/image_prep.hip) --------------------------------------------------------
+ * Replaces PIL.Image.resize(img_wh, Image.LANCZOS) and the arithmetic behind it in the reference's process_img
+ * (nerfmatch/datasets/nerfmatch_dataset.py:36-61; nerfbase.py:197-237): every output byte equals Pillow's.
+ * src [F,H,W,C] uint8, C in {1, 3} -> out_u8 [F,h,w,C] and / or out_f32 [F,C,h,w] = lut[c * 256 + byte] (lut: device float [C,256],
+ * needed with out_f32); each output may be NULL, not both.  One launch for all frames; a tile of NM_IMAGE_TILE_W x NM_IMAGE_TILE_H
+ * output pixels per workgroup.
+ * Tables of an axis in -> out (device int32, made on the host: nerfmatch_amd.image_prep.lanczos_tables states the arithmetic):
+ *   bounds [out,2] = (first source index, number of taps) of every output; coefficients in fixed point with 22 fractional bits,
+ *   coef_x [ksize_x, w] TAP-major (row x holds tap x of every output column), coef_y [h, ksize_y] output-major.
+ *   ksize = ceil(3 max(in / out, 1)) * 2 + 1 (anything else: NM_ERR_ARG), or 0 with NULL tables for an axis that keeps its size.
+ * The horizontal pass runs first and is rounded and clipped to uint8; the vertical pass filters those bytes; a pixel is
+ * clip((2^21 + sum_x k[x] src[first + x]) >> 22, 0, 255) in int32.
+ * white_where (may be NULL): [F,h,w] uint8 at OUTPUT resolution; where it is >= 128 the pixel is 255 in every channel in both outputs.
+ * Limits (NM_ERR_UNSUPPORTED beyond): C in {1, 3}; every side <= 8192; a reduction of at most 8 x per axis (ksize <= 51), any
+ * enlargement; F <= 65535.  src, out_u8 and out_f32 must be 16-byte aligned (NM_ERR_ARG).  Every check is made before anything is
+ * enqueued. */
+#define NM_IMAGE_TILE_W 64
+#define NM_IMAGE_TILE_H 32
+int nm_image_resize_u8(const uint8_t* src, int F, int H, int W, int C, const int* coef_x, const int* bounds_x, int ksize_x,
+                       const int* coef_y, const int* bounds_y, int ksize_y, int h, int w, const uint8_t* white_where, const float* lut,
+                       uint8_t* out_u8, float* out_f32, nmStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Matcher half
  * ---------------------------------------------------------------------------------------------- */

@@ -89,6 +89,8 @@ SIGNATURES = {
     "nm_refbank_visibility": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "nm_refbank_select": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "nm_refbank_gather": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+    # Pillow-exact Lanczos resize of uint8 images (image_prep.hip)
+    "nm_image_resize_u8": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "nm_linear": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "nm_linear_blob_bytes_bf16x3": (sz, [i32, i32]),
     "nm_linear_qkv_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -25,8 +25,8 @@ An epoch visits every training pixel once in a shuffled order that is never mate
 ranks takes positions k R w + r R + [0, R): what a position yields depends neither on R nor on w; the last partial batch is dropped.
 
 A bank on a GPU runs the HIP kernels (csrc/ray_bank.hip; no fallback).  A bank on device="cpu" takes the plain-torch statements of the
-same rules below, which are also what the kernels are tested against.  Loading and resizing image files, white-background blending and
-annotation parsing stay with the caller: the bank starts from uint8 tensors."""
+same rules below, which are also what the kernels are tested against.  The bank starts from uint8 tensors at the training resolution:
+image_prep.nerf_frames resizes and blends decoded frames; decoding image files and annotation parsing stay with the caller."""
 import math
 
 import torch

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from . import dist as nmdist
-from . import ops
+from . import image_prep, ops
 from .matcher import NeRFMatcherCoarse, NeRFMatcherMS
 from .nerf_evaluator import GenericModelEvaluator, load_nerf_render_from_ckpt  # noqa: F401
 from .utils import data_to_device, merge_configs
@@ -650,6 +650,14 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
             if ms is not None:
                 cur.wait_stream(ms)
 
+    def _prepare_queries(self, batch):
+        """`image` and the scaled `K` of a batch that carries decoded queries `image_u8` (Q,H,W,3) uint8 instead of `image`: the reference's
+        process_img (nerfmatch_dataset.py:267-268) with `img_wh` and `imagenet_norm` of the data configuration, on the evaluator's device."""
+        conf = getattr(self.config, "data", Namespace())
+        if "image" not in batch:
+            batch["image_u8"] = torch.as_tensor(batch["image_u8"]).to(self.device)
+        return image_prep.prepare_query_batch(batch, conf.img_wh, imagenet_norm=getattr(conf, "imagenet_norm", False))
+
     def eval_batch(self, batch, renderer=None, inerf_conf=None, iters=1, mutual=True, match_thres=0.0, match_oracle=False,
                    solver="colmap", rthres=1, center_subpixel=False, visualize=False, overlay_ims=None, query2query=False,
                    retrieval_only=False, cached_pt=True, cache_iters=False, debug=False):
@@ -657,6 +665,8 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
         `c2w_ests`, and `iter_t_errs` / `iter_R_errs` as one trace per query; `c2w_est` and the traces are the query's own when Q == 1)."""
         if visualize:
             raise NotImplementedError("overlay visualisation is out of scope (SURVEY.md section 2)")
+        if "image_u8" in batch:  # decoded queries: resized and normalised here (image_prep.py), K scaled; any other batch is untouched
+            batch = self._prepare_queries(batch)
         o = self._opts(inerf_conf=inerf_conf, iters=iters, mutual=mutual, match_thres=match_thres, solver=solver, rthres=rthres,
                        center_subpixel=center_subpixel, query2query=query2query, retrieval_only=retrieval_only, cached_pt=cached_pt,
                        cache_iters=cache_iters, debug=debug, match_oracle=match_oracle)

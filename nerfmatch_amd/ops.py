@@ -368,6 +368,28 @@ def refbank_gather(pt3d, pt_feat, pt_mask, ref_ids, bad, rows, select=None, perm
     return o3, of, om
 
 
+def image_resize_u8(src, wh, tables_x, tables_y, white_where=None, lut=None, want_u8=True):
+    """nm_image_resize_u8: src (F,H,W,C) uint8 on the device, C in {1, 3} -> (uint8 (F,h,w,C) or None, float32 (F,C,h,w) or None) at
+    wh = (w, h).  tables_x = (coef (ksize, w) int32 TAP-major, bounds (w, 2) int32) on the device, or None when the width stays;
+    tables_y = (coef (h, ksize), bounds (h, 2)), or None when the height stays.  white_where (F,h,w) uint8: 255 where it is >= 128.
+    lut (C,256) float32 on the device asks for the float output.  One launch, no host synchronisation."""
+    F, H, W, Cn = src.shape
+    w, h = int(wh[0]), int(wh[1])
+    assert (tables_x is None) == (W == w) and (tables_y is None) == (H == h) and (want_u8 or lut is not None)
+    assert white_where is None or tuple(white_where.shape) == (F, h, w)
+    assert lut is None or tuple(lut.shape) == (Cn, 256)
+    (cx, bx), (cy, by) = tables_x or (None, None), tables_y or (None, None)
+    kx, ky = 0 if cx is None else cx.shape[0], 0 if cy is None else cy.shape[1]
+    assert cx is None or (cx.shape == (kx, w) and bx.shape == (w, 2))
+    assert cy is None or (cy.shape == (h, ky) and by.shape == (h, 2))
+    out_u8 = torch.empty(F, h, w, Cn, device=src.device, dtype=torch.uint8) if want_u8 else None
+    out_f = None if lut is None else torch.empty(F, Cn, h, w, device=src.device, dtype=torch.float32)
+    check(lib().nm_image_resize_u8(dptr(src, torch.uint8), F, H, W, Cn, dptr(cx, torch.int32), dptr(bx, torch.int32), kx,
+                                   dptr(cy, torch.int32), dptr(by, torch.int32), ky, h, w, dptr(white_where, torch.uint8), dptr(lut),
+                                   dptr(out_u8, torch.uint8), dptr(out_f), stream()), "nm_image_resize_u8")
+    return out_u8, out_f
+
+
 # ----------------------------------------------------------------------------- matcher half
 # Arithmetic of the nn.Linear layers: "fp32" (v_mfma_f32_32x32x2_f32, nm_linear) or "bf16x3" (bf16 MFMA on hi/lo-split
 # operands, fp32-accurate, nm_linear_bf16x3).  Module-level switch like ATTENTION_PRECISION.
