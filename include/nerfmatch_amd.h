@@ -403,6 +403,37 @@ int nm_refbank_gather(const float* pt3d, const float* pt_feat, const uint8_t* pt
                       int k, const int* list, const int* n_visible, const uint32_t* perm_keys, int P, float* out_pt3d, float* out_feat,
                       uint8_t* out_mask, int* bad, nmStream_t stream);
 
+/* ---- Covisibility pair lists from a device-resident scene cache (csrc/covis_pairs.hip) ----------------------------------------
+ * Replaces the downloaded `train_pair_txt` lists (pairs-db-covis20.txt; parsed by load_retrieval_pairs / load_topk_retrieval_pairs,
+ * nerfmatch/datasets/data_loading.py:94-127), which an SfM toolchain made from a sparse model: which frames see each other follows from
+ * the cached renders alone.  The bank is the one of the section above without its features: pt3d [F,n,3] world points in ray order,
+ * pt_mask [F,n] uint8, cams [F,21] -- all on the device.  rows [Q] int32 (device; may be NULL: Q == F and row q is frame q): the query
+ * frames; an id outside [0, F) is clamped into the bank.  nerfmatch_amd.covis_pairs states the rule in torch.
+ * Projection: p = R X + t, q = p / p.z, pix = K q in fp32 in nm_gt_supervision's operation order, no contraction.  A point is SEEN by a
+ * camera iff pix is finite, p.z > 0 (a depth-sign test, unlike nm_refbank_visibility), 0 <= x < img_w and 0 <= y < img_h; with the
+ * depth test (zself != NULL; the frames' points are one per cell of a gw x gh grid over the image, gw gh == n) also: for the cell
+ * c = ((int)y gh / img_h) gw + (int)x gw / img_w of the query frame i, pt_mask[i,c] != 0, zq = zself[i,c] > 0 and
+ * fabsf(p.z - zq) <= depth_tol * zq (one fp32 product).
+ * Limits (NM_ERR_UNSUPPORTED beyond): F <= 2^20, n <= 2^20, Q <= 2^20, Q F <= 2^31, k <= 64, image and grid sides <= 8192.
+ * Every check is made before anything is enqueued.  Integer counts, one writer per element: two runs give the same bytes. */
+#define NM_COVIS_QUERY_TILE 32 /* query cameras per workgroup of nm_covis_scores */
+
+/* zself [F,n]: p.z of point (f, r) under camera f -- frame f's own depth map.  pt_mask (may be NULL): where it is 0 the cell holds NaN
+ * instead, which fails nm_covis_scores' test zq > 0 like the mask itself.  One thread per point. */
+int nm_covis_self_depth(const float* pt3d, const uint8_t* pt_mask, const float* cams, int F, int n, float* zself, nmStream_t stream);
+
+/* scores [Q,F] int32: scores[q,j] = #{ r : pt_mask[j,r] != 0 and point (j, r) is seen by frame rows[q] }, the diagonal like any other
+ * entry.  zself == NULL: no depth test (then gw == gh == 0; depth_tol unused); otherwise nm_covis_self_depth's output WITH the bank's
+ * pt_mask (the kernel gathers 4 bytes per point from it and reads no mask of the query frame), gw gh == n and
+ * 0 <= depth_tol < inf (NM_ERR_ARG otherwise).  One workgroup per (frame j, tile of NM_COVIS_QUERY_TILE rows). */
+int nm_covis_scores(const float* pt3d, const uint8_t* pt_mask, const float* cams, const int* rows, const float* zself, int F, int n, int Q,
+                    int img_w, int img_h, int gw, int gh, float depth_tol, int* scores, nmStream_t stream);
+
+/* ids [Q,k] int32: row q lists the frames j != rows[q] with scores[q,j] >= min_score (and >= 0) by score descending, then index
+ * ascending, padded with -1; n_pairs [Q] int32: how many it lists.  One workgroup per row, k rounds of an arg-max over the packed key
+ * (score << 32) | (F - 1 - j). */
+int nm_covis_topk(const int* scores, const int* rows, int Q, int F, int k, int min_score, int* ids, int* n_pairs, nmStream_t stream);
+
 /* ---- Pillow-exact Lanczos resize of 8-bit images (csrc/image_prep.hip) --------------------------------------------------------
  * Replaces PIL.Image.resize(img_wh, Image.LANCZOS) and the arithmetic behind it in the reference's process_img
  * (nerfmatch/datasets/nerfmatch_dataset.py:36-61; nerfbase.py:197-237): every output byte equals Pillow's.

@@ -89,6 +89,10 @@ SIGNATURES = {
     "nm_refbank_visibility": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "nm_refbank_select": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "nm_refbank_gather": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+    # covisibility pair lists from a device-resident scene cache (covis_pairs.hip)
+    "nm_covis_self_depth": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "nm_covis_scores": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]),
+    "nm_covis_topk": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     # Pillow-exact Lanczos resize of uint8 images (image_prep.hip)
     "nm_image_resize_u8": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "nm_linear": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),

@@ -17,6 +17,9 @@ LIB = LIBDIR / "libnerfmatch_amd.so"
 STAMP = LIBDIR / "build.stamp"
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}", "-Wno-unused-result"]
+# Flags of single sources.  covis_pairs: the SLP vectoriser packs the projection's independent fp32 products and sums into v_pk_mul_f32 /
+# v_pk_add_f32 (half rate, plus the moves and wait states that pair their operands) and the lane predicates into 16-bit vectors.
+EXTRA_FLAGS = {"covis_pairs": ["-fno-slp-vectorize"]}
 
 
 def sources():
@@ -29,6 +32,7 @@ def _digest():
         h.update(p.name.encode())
         h.update(p.read_bytes())
     h.update(" ".join(FLAGS).encode())
+    h.update(repr(sorted(EXTRA_FLAGS.items())).encode())
     return h.hexdigest()
 
 
@@ -62,7 +66,7 @@ def build(force=False, verbose=False, safe=False):
     procs = []
     for src in sources():
         obj = LIBDIR / (src.stem + ".o")
-        cmd = [hipcc, *FLAGS, "-c", str(src), "-o", str(obj)]
+        cmd = [hipcc, *FLAGS, *EXTRA_FLAGS.get(src.stem, []), "-c", str(src), "-o", str(obj)]
         if verbose:
             cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         if do_lib or not obj.exists():
@@ -72,7 +76,7 @@ def build(force=False, verbose=False, safe=False):
             continue
         if src.stem in SAFE_SOURCES:
             sobj = LIBDIR / (src.stem + ".safewait.o")
-            procs.append((src, subprocess.Popen([hipcc, *FLAGS, "-DNM_SAFE_WAIT", "-c", str(src), "-o", str(sobj)], stdout=subprocess.PIPE,
+            procs.append((src, subprocess.Popen([hipcc, *FLAGS, *EXTRA_FLAGS.get(src.stem, []), "-DNM_SAFE_WAIT", "-c", str(src), "-o", str(sobj)], stdout=subprocess.PIPE,
                                                 stderr=subprocess.STDOUT, text=True)))
             safe_objs.append(sobj)
         else:

@@ -368,6 +368,46 @@ def refbank_gather(pt3d, pt_feat, pt_mask, ref_ids, bad, rows, select=None, perm
     return o3, of, om
 
 
+def covis_self_depth(pt3d, cams, pt_mask=None):
+    """nm_covis_self_depth: pt3d (F,n,3), cams (F,21) on the device -> zself (F,n): p.z of every frame's points under its own camera; with
+    pt_mask (F,n) bool, NaN where it is false: the depth map covis_scores gathers from."""
+    F, n, _ = pt3d.shape
+    assert pt3d.shape == (F, n, 3) and cams.shape == (F, 21) and (pt_mask is None or (pt_mask.shape == (F, n) and pt_mask.dtype == torch.bool))
+    zself = torch.empty(F, n, device=pt3d.device, dtype=torch.float32)
+    mask = None if pt_mask is None else pt_mask.view(torch.uint8)
+    check(lib().nm_covis_self_depth(dptr(pt3d), dptr(mask, torch.uint8), dptr(cams), F, n, dptr(zself), stream()), "nm_covis_self_depth")
+    return zself
+
+
+def covis_scores(pt3d, pt_mask, cams, rows, img_wh, zself=None, grid_wh=None, depth_tol=None):
+    """nm_covis_scores: how many of frame j's masked points (pt3d (F,n,3), pt_mask (F,n) bool) the frames rows (Q,) int32 (device; None: all
+    frames) see under cams (F,21) at img_wh = (W, H) -> scores (Q,F) int32.  zself (F,n) with grid_wh = (gw, gh) and depth_tol: the depth
+    test; zself is covis_self_depth(pt3d, cams, pt_mask): the kernel reads the query frames' masks from it.  One launch, no host
+    synchronisation."""
+    F, n, _ = pt3d.shape
+    assert pt3d.shape == (F, n, 3) and pt_mask.shape == (F, n) and pt_mask.dtype == torch.bool and cams.shape == (F, 21)
+    assert (zself is None) == (grid_wh is None) == (depth_tol is None) and (zself is None or zself.shape == (F, n))
+    Q = F if rows is None else rows.numel()
+    gw, gh = (0, 0) if grid_wh is None else (int(grid_wh[0]), int(grid_wh[1]))
+    scores = torch.empty(Q, F, device=pt3d.device, dtype=torch.int32)
+    check(lib().nm_covis_scores(dptr(pt3d), dptr(pt_mask.view(torch.uint8), torch.uint8), dptr(cams), dptr(rows, torch.int32), dptr(zself), F, n, Q,
+                                int(img_wh[0]), int(img_wh[1]), gw, gh, 0.0 if depth_tol is None else float(depth_tol), dptr(scores, torch.int32),
+                                stream()), "nm_covis_scores")
+    return scores
+
+
+def covis_topk(scores, rows, k, min_score=1):
+    """nm_covis_topk: scores (Q,F) int32 whose row q belongs to frame rows[q] (rows (Q,) int32 on the device; None: frame q)
+    -> ids (Q,k) int32 padded with -1, n_pairs (Q,) int32.  One launch, no host synchronisation."""
+    Q, F = scores.shape
+    assert rows is None or rows.shape == (Q,)
+    ids = torch.empty(Q, int(k), device=scores.device, dtype=torch.int32)
+    n_pairs = torch.empty(Q, device=scores.device, dtype=torch.int32)
+    check(lib().nm_covis_topk(dptr(scores, torch.int32), dptr(rows, torch.int32), Q, F, int(k), int(min_score), dptr(ids, torch.int32),
+                              dptr(n_pairs, torch.int32), stream()), "nm_covis_topk")
+    return ids, n_pairs
+
+
 def image_resize_u8(src, wh, tables_x, tables_y, white_where=None, lut=None, want_u8=True):
     """nm_image_resize_u8: src (F,H,W,C) uint8 on the device, C in {1, 3} -> (uint8 (F,h,w,C) or None, float32 (F,C,h,w) or None) at
     wh = (w, h).  tables_x = (coef (ksize, w) int32 TAP-major, bounds (w, 2) int32) on the device, or None when the width stays;

@@ -29,13 +29,16 @@ The rule of "rand" for one query with the frames f_0 .. f_{k-1}:
      seed is query_seed(seed, sample_keys[b]) and its epoch is `draw`.  The key does not depend on the position
      in the batch, so a query yields the same rows alone or inside any batch.
 
-Out of scope: image files, pair lists and annotation parsing; masks other than the ones handed to the constructor."""
+A bank also answers which frames see each other (`covisibility_pairs`: covis_pairs.py on the bank's own tensors), which is the pair
+list `draw_ref_ids` draws from.
+
+Out of scope: image files and annotation parsing; masks other than the ones handed to the constructor."""
 import functools
 
 import numpy as np
 import torch
 
-from . import scene_cache, supervision
+from . import covis_pairs, scene_cache, supervision
 from .nerf.ray_bank import epoch_ids, perm_params
 
 MAX_K = 32            # one bit per view in a 32-bit word
@@ -121,13 +124,7 @@ class ReferencePointBank:
         if min(self.img_wh) < 1:
             raise ValueError(f"img_wh {self.img_wh} must be positive")
         c2w = torch.as_tensor(c2w).detach().to("cpu", torch.float32).reshape(F, 4, 4)
-        K = torch.as_tensor(K).detach().to("cpu", torch.float32)
-        K = K.expand(F, 3, 3) if K.dim() == 2 else K.reshape(F, 3, 3)
-        wh = torch.as_tensor(frame_wh).detach().to("cpu", torch.float32)
-        wh = wh.expand(F, 2) if wh.dim() == 1 else wh.reshape(F, 2)
-        # sK @ rK of nerfmatch_dataset.py:486-490 in fp32 (a diagonal times a matrix: one product per entry, the same bits as the matmul)
-        scale = torch.stack([self.img_wh[0] / wh[:, 0], self.img_wh[1] / wh[:, 1], torch.ones(F)], -1)
-        sK = scale[:, :, None] * K
+        cams = covis_pairs.camera_rows(c2w, K, frame_wh, self.img_wh)  # sK @ rK of nerfmatch_dataset.py:486-490 | w2c rows 0..2
         self.c2w_host = c2w
         self.unnorm_scene = None if unnorm_scene is None else torch.as_tensor(unnorm_scene).detach().to("cpu", torch.float32).reshape(4, 4)
         if pt_mask is None:
@@ -139,7 +136,7 @@ class ReferencePointBank:
         self.pt3d = pt3d.contiguous().to(dev)
         self.pt_feat = pt_feat.contiguous().to(dev)
         self.pt_mask = pt_mask.ne(0).contiguous().to(dev)
-        self.cams = torch.cat([sK.reshape(F, 9), supervision.w2c_from_c2w(c2w).reshape(F, 12)], 1).contiguous().to(dev)
+        self.cams = cams.to(dev)
         self.c2w = c2w.contiguous().to(dev)
         self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
 
@@ -179,6 +176,17 @@ class ReferencePointBank:
         if len(rids) < k:
             raise ValueError(f"{len(rids)} reference frames, {k} are needed")
         return rids[:k]
+
+    def covisibility_pairs(self, k=20, depth_tol=None, ds=None, rows=None, min_score=1):
+        """The k most covisible frames of every frame of the bank (or of `rows`), by the rule of covis_pairs.py on the bank's points, masks
+        and camera rows -> ids (Q,k) int32 padded with -1, n_pairs (Q,) int32, on the bank's device; covis_pairs.pairs_dict(rows, ids) is the
+        `pair_ids` draw_ref_ids takes its rows from.  depth_tol with ds: the depth test on the grid (W // ds, H // ds) of the frames'
+        points (the coarse stride they were rendered at)."""
+        if (depth_tol is None) != (ds is None):
+            raise ValueError("the depth test needs both depth_tol and ds")
+        grid_wh = None if ds is None else (self.img_wh[0] // int(ds), self.img_wh[1] // int(ds))
+        return covis_pairs.covisibility_pairs(self.pt3d, self.pt_mask, self.cams, self.img_wh, rows=rows, depth_tol=depth_tol, grid_wh=grid_wh,
+                                              k=k, min_score=min_score)
 
     @property
     def bad_ids(self):
