@@ -559,6 +559,35 @@ int nm_attention_fp8(const float* q, const float* k, const float* v, int ldq, in
 int nm_add_sine_pe(const float* x, const float* pe_table, int B, int h, int w, int C, int table_h, int table_w,
                    float* y, nmStream_t stream);
 
+/* ---- ConvFormer image backbone: the memory-bound kernels (csrc/convformer.hip) -----------------------------------------------
+ * The backbone of the reference (MetaFormer_MS / init_backbone, nerfmatch/modules/__init__.py:14-113) is the stem plus stages 0 and 1
+ * of timm's convformer_b36 / caformer_b36.  Activations are channel-last rows; its 1x1 convolutions are nm_linear, its LayerNorms
+ * nm_layernorm.  All four: fp32, caller's buffers, 16-byte aligned (NM_ERR_ARG otherwise; the one exception: nm_conv_patches' NCHW
+ * input, see there), every check before anything is enqueued.
+ *
+ * nm_dwconv7_nhwc: y[b,h,w,c] = sum_(ky,kx) w49c[ky*7+kx, c] * a(x[b, h+ky-3, w+kx-3, c]), x, y [B,H,W,C], w49c [49,C] tap-major.
+ *   a = StarReLU (below) when act_scale / act_bias (device pointers to one float each; both or neither) are given, else the identity;
+ *   a tap outside the image contributes 0 (the padding is applied BEHIND the activation).  Per output one fmaf chain over the 49 taps in
+ *   (ky, kx) order from 0: independent of tile and batch position.  x != y.
+ *   Limits (NM_ERR_UNSUPPORTED beyond): C a multiple of 64 up to 1024, H, W <= 8192, B <= 65535.  A workgroup makes
+ *   NM_DWCONV_TILE_H x NM_DWCONV_TILE_W outputs of 32 channels.
+ * nm_star_relu: y[i] = scale[0] * relu(x[i])^2 + bias[0] as r = x < 0 ? 0 : x; t = r * r; t = scale * t; y = t + bias (three roundings; a NaN
+ *   passes through).  scale, bias: device pointers.  In place (y == x) allowed.
+ * nm_conv_patches: rows [B*Ho*Wo, ld], Ho = (H + 2 pad - k) / stride + 1 (Wo alike): column (ky*k + kx)*C + c of row (b, oy, ox) is
+ *   x[b, c, oy*stride - pad + ky, ox*stride - pad + kx], zero outside the image; columns k*k*C .. ld-1 are written as zero.
+ *   layout 0: x [B,C,H,W], read as single floats and therefore only 4-byte aligned (image q of a batch of odd-sized images);
+ *   layout 1: x [B,H,W,C], 16-byte aligned.  ld % 8 == 0 and ld >= k*k*C (NM_ERR_ARG otherwise).  The convolution is then
+ *   nm_linear(rows, w [N, ld] in the same column order, bias).  Limits: k <= 7, stride <= 8, pad < k, C <= 1024, H, W <= 8192.
+ * nm_nhwc_to_nchw: y[b,c,p] = x[b,p,c] for x [B,HW,C] (the inverse direction of nm_add_sine_pe).  Limits: C % 4 == 0, B <= 65535. */
+#define NM_DWCONV_TILE_H 16
+#define NM_DWCONV_TILE_W 16
+int nm_dwconv7_nhwc(const float* x, const float* w49c, const float* act_scale, const float* act_bias, int B, int H, int W, int C, float* y,
+                    nmStream_t stream);
+int nm_star_relu(const float* x, const float* scale, const float* bias, size_t n, float* y, nmStream_t stream);
+int nm_conv_patches(const float* x, int layout, int B, int C, int H, int W, int k, int stride, int pad, int ld, float* rows,
+                    nmStream_t stream);
+int nm_nhwc_to_nchw(const float* x, int B, int HW, int C, float* y, nmStream_t stream);
+
 /* The reference's encoding MODULES as callable entry points (its evaluator reaches into renderer.xyz_encoder / dirs_encoder directly,
  * nerfmatch/nerfmatch_evaluator.py:385-393).  The fused kernels never call these: they produce the same encodings as MFMA operands.
  *   nm_mip_encode: PositionalEncodingMIP.forward(x, y) (nerfmatch/nerf/embedding.py:66-84) for x, y [n, D], scales 2^min_deg .. 2^(min_deg +

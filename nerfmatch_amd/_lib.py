@@ -95,6 +95,11 @@ SIGNATURES = {
     "nm_covis_topk": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     # Pillow-exact Lanczos resize of uint8 images (image_prep.hip)
     "nm_image_resize_u8": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    # ConvFormer image backbone: depthwise 7x7, StarReLU, convolution patches, channel-last -> planes (convformer.hip)
+    "nm_dwconv7_nhwc": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "nm_star_relu": (i32, [vp, vp, vp, sz, vp, vp]),
+    "nm_conv_patches": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "nm_nhwc_to_nchw": (i32, [vp, i32, i32, i32, vp, vp]),
     "nm_linear": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "nm_linear_blob_bytes_bf16x3": (sz, [i32, i32]),
     "nm_linear_qkv_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
@@ -171,6 +176,7 @@ NM_ATTN_BF16X3 = 1
 NM_NERF_ZERO_TAIL = 4
 NM_MATCH_BF16X3 = 1
 NM_MATCH_STATS_ONLY = 2
+NM_DWCONV_TILE_H, NM_DWCONV_TILE_W = 16, 16
 
 
 class NerfmatchAmdError(RuntimeError):

@@ -289,6 +289,13 @@ class _MatcherBase(nn.Module):
                 cfeat.shape[0] == pt_feat.shape[0] and cfeat.shape[2] * cfeat.shape[3] == pt_feat.shape[1] and
                 (self.cfeat_proj.weight.shape[0] if self.cfeat_proj is not None else cfeat.shape[1]) == self.cfeat_dim)
 
+    def _backbone_maps(self, img):
+        """self.backbone(img) with autograd recording only inside autograd.training(), like every other stage of the matcher: an inference
+        pass records nothing whatever torch's grad mode is, so the native backbone (modules/convformer.py), which leaves its HIP kernels
+        whenever autograd must record, stays on them."""
+        with torch.set_grad_enabled(ag.is_training()):
+            return self.backbone(img)
+
     def image_tokens(self, img):
         """The image side of the coarse matcher -- backbone, tokens, sine PE, self-attention block -- as a constant: with frozen parameters
         and an image that asks for no gradient nothing here is differentiated, so it runs on the fused inference kernels and builds no
@@ -416,7 +423,7 @@ class NeRFMatcherMS(_MatcherBase):
         """Image tokens and fine map (reference :237-256).  With `pt_feat` (the point features about to be matched): if the two
         token sets can share one pass through the self-attention block (_shared_sa_batchable) the image tokens are returned
         WITHOUT it, for extract_pt_feat(..., im_tokens=...) to finish; the third return value says which."""
-        cfeat, ffeat = self.backbone(img)
+        cfeat, ffeat = self._backbone_maps(img)
         defer = pt_feat is not None and self._shared_sa_batchable(cfeat, pt_feat)
         if self.ffeat_proj is not None:
             b, f, hf, wf = ffeat.shape
@@ -826,7 +833,7 @@ class NeRFMatcherCoarse(_MatcherBase):
         self.keep_conf = True
 
     def extract_im_feat(self, img):
-        cfeat = self.backbone(img)
+        cfeat = self._backbone_maps(img)
         if isinstance(cfeat, (list, tuple)):
             cfeat = cfeat[0]
         return self.tokens_from_cfeat(cfeat)

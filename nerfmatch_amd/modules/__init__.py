@@ -1,13 +1,13 @@
-"""Image backbones (contract only).
+"""Image backbones.
 
 The reference uses timm's ConvFormer/CAFormer-B36 patched to emit 1/8 and 1/2 resolution maps
-(nerfmatch/modules/__init__.py:14-113).  timm is third-party code that is absent from the reference tree and
-is out of the hot-path scope; only the OUTPUT CONTRACT matters here:
+(nerfmatch/modules/__init__.py:14-113): the stem and stages 0-1 of that network, which modules/convformer.py builds on the
+HIP kernels (names 'convformer', 'convformer384', 'caformer', 'caformer384'; timm is not needed).  The OUTPUT CONTRACT:
     init_backbone_8_2(...)  -> module with .feat_dim == [256, 128], forward(img) -> (cfeat (B,256,H/8,W/8),
                                                                                     ffeat (B,128,H/2,W/2))
-    init_backbone(...)      -> module with .feat_dim == 256,        forward(img) -> cfeat (B,256,H/8,W/8)
-`backbone="stub"` selects a small deterministic torch stand-in with that contract (synthetic benchmarks, tests);
-any other name needs timm and is delegated to it when importable."""
+    init_backbone(...)      -> module with .feat_dim == 256,        forward(img) -> cfeat (B,256,H/8,W/8) or, as timm's
+                                                                                    feature networks do, the one-element list [cfeat]
+`backbone="stub"` selects a small deterministic torch stand-in with that contract (synthetic benchmarks, tests)."""
 import torch
 from torch import nn
 import torch.nn.functional as F
@@ -46,24 +46,42 @@ class PrecomputedBackbone(nn.Module):
         return self.outs
 
 
-def _need_timm(name):
-    try:
-        import timm  # noqa: F401
-    except ImportError as e:
-        raise NotImplementedError(
-            f"backbone '{name}' is timm's ConvFormer/CAFormer (third-party, not part of the reference tree, out of scope); "
-            "install timm and plug a module with the documented contract, or use backbone='stub'") from e
-    raise NotImplementedError("timm is importable but the ConvFormer stride patching is not part of this build; "
-                              "pass a module via model.backbone = ...")
+_CONVFORMER = ("convformer", "convformer384", "caformer", "caformer384")
+
+
+def _convformer_name(name):
+    """True for the four names the native ConvFormer stages serve; the FPN variants (BatchNorm, bilinear upsampling; no shipped config
+    selects them) and anything else are refused."""
+    if name in _CONVFORMER:
+        return True
+    if isinstance(name, str) and name.endswith("_fpn") and name[:-4] in _CONVFORMER:
+        raise NotImplementedError(f"backbone '{name}': the FPN head of the reference's MetaFormer_MS is not part of this build "
+                                  f"(use '{name[:-4]}', which every shipped config selects)")
+    raise NotImplementedError(f"backbone '{name}' is not known: the native backbones are {_CONVFORMER} (stem and stages 0-1 of timm's "
+                              "ConvFormer/CAFormer-B36, modules/convformer.py) and 'stub'; or pass a module via model.backbone = ...")
 
 
 def init_backbone_8_2(backbone="stub", pretrained=False):
     if backbone == "stub":
         return StubBackbone(two_scales=True)
-    _need_timm(backbone)
+    _convformer_name(backbone)
+    from .convformer import ConvFormerMS, pretrained_notice
+
+    if pretrained:
+        pretrained_notice(backbone)
+    return ConvFormerMS()
 
 
 def init_backbone(backbone="stub", pretrained=False, downsample=8):
     if backbone == "stub":
         return StubBackbone(two_scales=False)
-    _need_timm(backbone)
+    _convformer_name(backbone)
+    if downsample != 8:
+        raise ValueError(f"init_backbone: downsample {downsample}: the native ConvFormer stages end at 1/8 resolution")
+    from .convformer import ConvFormerStages, pretrained_notice
+
+    if pretrained:
+        pretrained_notice(backbone)
+    m = ConvFormerStages(4, 2, 2, (1,))
+    m.feat_dim = 256
+    return m

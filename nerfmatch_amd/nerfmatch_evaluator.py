@@ -900,9 +900,10 @@ class NeRFMatchEvaluator(GenericModelEvaluator):
 def load_nerfmatch_from_ckpt(ckpt_path, args=None, root_dir=".", arg_mask=None, data_loader=None, backbone=None):
     """Lightning checkpoint of the reference -> evaluator (reference :69-115).
 
-    The image backbone is timm's ConvFormer (third party, out of scope): pass it as `backbone` (a module with the contract of
-    nerfmatch_amd.modules: .feat_dim and forward(img) -> (cfeat, ffeat) | cfeat) and its `model.backbone.*` tensors are loaded
-    into it; without one the checkpoint's backbone tensors are dropped and the stub backbone stays (synthetic benchmarks).
+    The image backbone named by the hyper-parameters ('convformer384' in every shipped config) is built natively
+    (nerfmatch_amd.modules.convformer) and takes the checkpoint's `model.backbone.*` tensors.  `backbone`: a module with the contract
+    of nerfmatch_amd.modules (.feat_dim and forward(img) -> (cfeat, ffeat) | cfeat) to use instead; its `model.backbone.*` tensors are
+    loaded into it.  With the parameter-free stub the checkpoint's backbone tensors are dropped (synthetic benchmarks).
     Every other key must match: missing or unexpected matcher weights raise (the reference's strict=False would let a
     renamed weight pass silently)."""
     ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)

@@ -746,6 +746,71 @@ def nchw_to_tokens(x, pe_table=None):
     return y
 
 
+def nhwc_to_nchw(x, out=None):
+    """(B,h,w,C) channel-last -> (B,C,h,w) planes (nm_nhwc_to_nchw), into `out` when given: a contiguous fp32 device tensor of that
+    shape (a slice along the batch of a larger one will do); anything else raises."""
+    B, h, w, Cc = x.shape
+    y = torch.empty(B, Cc, h, w, device=x.device, dtype=torch.float32) if out is None else out
+    assert tuple(y.shape) == (B, Cc, h, w)
+    check(lib().nm_nhwc_to_nchw(dptr(x), B, h * w, Cc, dptr(y), stream()), "nm_nhwc_to_nchw")
+    return y
+
+
+def conv_out_size(n, k, stride, pad):
+    return (n + 2 * pad - k) // stride + 1
+
+
+def conv_patches(x, k, stride, pad, ld, channel_last=False):
+    """The k x k patches of a strided convolution as GEMM rows (nm_conv_patches): x (B,C,H,W), or (B,H,W,C) with channel_last ->
+    (B*Ho*Wo, ld), columns in (ky, kx, c) order and zero from k*k*C on; also returns (Ho, Wo)."""
+    if channel_last:
+        B, H, W, Cc = x.shape
+    else:
+        B, Cc, H, W = x.shape
+    Ho, Wo = conv_out_size(H, k, stride, pad), conv_out_size(W, k, stride, pad)
+    if Ho < 1 or Wo < 1:
+        raise _lib.NerfmatchAmdError(f"conv_patches: a {H}x{W} image is smaller than the {k}x{k} kernel with padding {pad}")
+    rows = torch.empty(B * Ho * Wo, int(ld), device=x.device, dtype=torch.float32)
+    check(lib().nm_conv_patches(dptr(x), int(bool(channel_last)), B, Cc, H, W, int(k), int(stride), int(pad), int(ld), dptr(rows), stream()),
+          "nm_conv_patches")
+    return rows, (Ho, Wo)
+
+
+def conv_weight_rows(weight, ld):
+    """A Conv2d weight (N, C, k, k) as the (N, ld) matrix that multiplies conv_patches' rows: columns in (ky, kx, c) order, zero-padded
+    to ld; cached until the tensor changes, like every derived copy of a weight."""
+    N = weight.shape[0]
+    kkc = weight.shape[1] * weight.shape[2] * weight.shape[3]
+    return _linear_cached(("convrows", int(ld)), weight,
+                          lambda w: torch.nn.functional.pad(w.permute(0, 2, 3, 1).reshape(N, kkc), (0, int(ld) - kkc)).contiguous())
+
+
+def dwconv_weight_taps(weight):
+    """A depthwise 7x7 weight (C, 1, 7, 7) as nm_dwconv7_nhwc's tap-major (49, C) matrix, cached until the tensor changes."""
+    return _linear_cached(("dwtaps",), weight, lambda w: w.reshape(w.shape[0], 49).t().contiguous())
+
+
+def dwconv7_nhwc(x, weight, act_scale=None, act_bias=None, taps=None):
+    """Depthwise 7x7 convolution, stride 1, zero padding 3, of channel-last x (B,H,W,C) (nm_dwconv7_nhwc); weight: the (C,1,7,7)
+    parameter (or taps: its (49, C) form).  act_scale / act_bias: the two 1-element StarReLU parameters, applied to x on the way in."""
+    B, H, W, Cc = x.shape
+    w49 = dwconv_weight_taps(weight) if taps is None else taps
+    assert tuple(w49.shape) == (49, Cc)
+    y = torch.empty_like(x)
+    check(lib().nm_dwconv7_nhwc(dptr(x), dptr(w49), dptr(act_scale), dptr(act_bias), B, H, W, Cc, dptr(y), stream()), "nm_dwconv7_nhwc")
+    return y
+
+
+def star_relu(x, scale, bias, inplace=False):
+    """scale * relu(x)**2 + bias (nm_star_relu); scale, bias: 1-element device tensors."""
+    if not x.is_contiguous():
+        raise _lib.NerfmatchAmdError("star_relu: hand over a contiguous tensor")
+    y = x if inplace else torch.empty_like(x)
+    if x.numel():
+        check(lib().nm_star_relu(dptr(x), dptr(scale), dptr(bias), x.numel(), dptr(y), stream()), "nm_star_relu")
+    return y
+
+
 def feature_normalize(x):
     """x (B,N,D) is centred IN PLACE (per set b: minus the mean over its N rows); returns the centred set divided by its largest row norm
     (nm_feature_normalize; the coarse model's `pt_feat_norm` option).  x must be contiguous: a silent copy would be centred instead of the

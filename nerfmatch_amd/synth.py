@@ -132,6 +132,50 @@ def nerf_state_dict(seed=0, app_vocab=0, hid=256, xyz_freqs=15, dirs_freqs=4, de
     return sd
 
 
+def backbone_state_dict(seed=0, kind="c2f"):
+    """Keys of the ConvFormer stages (modules/convformer.py: timm's flattened feature-network names) as they sit under `backbone.` in a
+    matcher: kind "c2f" -> `model.stem.conv.weight`, ... (NeRFMatcherMS keeps the network at backbone.model), kind "coarse" ->
+    `stem.conv.weight`, ... (NeRFMatcherCoarse's backbone is the network itself).  Convolution weights and biases U(+-sqrt(3 / fan_in))
+    (unit gain through a layer), norm weights U(0.5, 1.5), StarReLU scale U(0.7, 1.1) and bias U(-0.6, -0.2)."""
+    if kind not in ("c2f", "coarse"):
+        raise ValueError(kind)
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    pre = "model." if kind == "c2f" else ""
+
+    def conv(name, cout, cin, k, bias=False):
+        b = math.sqrt(3.0 / (cin * k * k))
+        sd[f"{pre}{name}.weight"] = _uniform(rng, (cout, cin, k, k), b)
+        if bias:
+            sd[f"{pre}{name}.bias"] = _uniform(rng, (cout,), b)
+
+    def norm(name, dim):
+        sd[f"{pre}{name}.weight"] = torch.from_numpy(rng.uniform(0.5, 1.5, size=(dim,)).astype(np.float32))
+
+    def act(name):
+        sd[f"{pre}{name}.scale"] = torch.from_numpy(rng.uniform(0.7, 1.1, size=(1,)).astype(np.float32))
+        sd[f"{pre}{name}.bias"] = torch.from_numpy(rng.uniform(-0.6, -0.2, size=(1,)).astype(np.float32))
+
+    conv("stem.conv", 128, 3, 7, bias=True)
+    norm("stem.norm", 128)
+    for s, (d, depth) in enumerate(((128, 3), (256, 12))):
+        if s == 1:
+            norm("stages_1.downsample.norm", 128)
+            conv("stages_1.downsample.conv", 256, 128, 3, bias=True)
+        for i in range(depth):
+            b = f"stages_{s}.blocks.{i}"
+            norm(f"{b}.norm1", d)
+            conv(f"{b}.token_mixer.pwconv1", 2 * d, d, 1)
+            act(f"{b}.token_mixer.act1")
+            sd[f"{pre}{b}.token_mixer.dwconv.weight"] = _uniform(rng, (2 * d, 1, 7, 7), math.sqrt(3.0 / 49))
+            conv(f"{b}.token_mixer.pwconv2", d, 2 * d, 1)
+            norm(f"{b}.norm2", d)
+            conv(f"{b}.mlp.fc1", 4 * d, d, 1)
+            act(f"{b}.mlp.act")
+            conv(f"{b}.mlp.fc2", d, 4 * d, 1)
+    return sd
+
+
 def _encoder_layer(sd, rng, name, dim, cross=False):
     for p in ("q", "k", "v"):
         _linear(sd, rng, f"{name}.attention.proj_{p}", dim, dim, bias=False)
