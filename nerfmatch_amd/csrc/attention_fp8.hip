@@ -1,7 +1,9 @@
 // Flash-style softmax attention for head_dim 32 with BOTH contractions on fp8 (OCP e4m3) matrix-core operands -- the
 // throughput configuration BASELINE.json config 5 names ("fp8 MFMA attention").  NOT a parity arithmetic: e4m3 carries 3
 // mantissa bits; the error against the fp32 result is reported by bench.py (`variants.attention_fp8`) and bounded by
-// tests/test_matcher_gpu.py::test_attention_fp8_error_bound, never asserted at 1e-4.
+// tests/test_matcher_gpu.py::test_attention_fp8_error_bound, never asserted at 1e-4.  The arithmetic itself, as this header and
+// the body state it, is pinned output by output to a CPU emulation (tests/attention_fp8_util.py) by
+// tests/test_attention_fp8_gpu.py::test_kernel_against_the_emulation: fp32 rounding plus single e4m3 steps of a probability.
 // Reference arithmetic it approximates: FullAttention, nerfmatch/modules/attention.py:44-57 (fp32 einsum, softmax, einsum).
 //
 // What changes against the split-bf16 kernel (attention_v2.hip, three bf16 MFMAs per product block):
