@@ -588,6 +588,33 @@ int nm_conv_patches(const float* x, int layout, int B, int C, int H, int W, int 
                     nmStream_t stream);
 int nm_nhwc_to_nchw(const float* x, int B, int HW, int C, float* y, nmStream_t stream);
 
+/* ---- ConvFormer image backbone: backward of the kernels above (csrc/convformer_bwd.hip) ----------------------------------------
+ * Same conventions: fp32, caller's buffers, 16-byte aligned, every check before anything is enqueued, NM_ERR_UNSUPPORTED beyond the
+ * forward kernel's limits.  a(x) = scale * relu(x)^2 + bias, r = relu(x).  Every reduction (dw49c, dscale, dbias) is the sum, in a fixed
+ * order, of per-workgroup partial sums kept in `workspace` (at least *_workspace_bytes(...) bytes, else NM_ERR_WORKSPACE): no atomics, the
+ * same bits on every run.  dscale_dbias: two floats, {dscale, dbias}; NULL = not wanted (no reduction, no workspace).
+ *
+ * nm_dwconv7_nhwc_bwd_input: da[b,h,w,c] = sum_(ky,kx) w49c[ky*7+kx, c] * dy[b, h-ky+3, w-kx+3, c] (dy zero outside the image), one fmaf
+ *   chain per element.  With x and act_scale (both or neither): dx = da * (2 * (scale * r(x))) in that order of roundings,
+ *   dscale = sum da * r(x)^2, dbias = sum da over all elements; without: dx = da, and dscale_dbias must be NULL.  dx != dy, dx != x.
+ * nm_dwconv7_nhwc_bwd_weight: dw49c[t,c] = sum_(b,h,w) dy[b,h,w,c] * a(x[b, h+ky-3, w+kx-3, c]) over the in-image terms, t = ky*7 + kx,
+ *   tap-major [49,C] like the forward's w49c; a = the identity without act_scale / act_bias (both or neither).
+ * nm_star_relu_bwd: dx[i] = dy[i] * (2 * (scale * r(x[i]))), dscale = sum dy * r(x)^2, dbias = sum dy; any n >= 1; out of place.
+ * nm_conv_patches_bwd: the adjoint of nm_conv_patches for layout 1 with C % 4 == 0 (anything else: NM_ERR_UNSUPPORTED):
+ *   dx[b,iy,ix,c] = sum of drows[(b,oy,ox), (ky*k+kx)*C + c] over the (ky, kx) with oy*stride - pad + ky = iy and ox*stride - pad + kx = ix,
+ *   added in ascending (ky, kx) order; the columns k*k*C .. ld-1 of drows are not read.  Same limits as nm_conv_patches. */
+size_t nm_dwconv7_nhwc_bwd_input_workspace_bytes(int B, int H, int W, int C);
+int nm_dwconv7_nhwc_bwd_input(const float* dy, const float* w49c, const float* x, const float* act_scale, int B, int H, int W, int C, float* dx,
+                              float* dscale_dbias, void* workspace, size_t workspace_bytes, nmStream_t stream);
+size_t nm_dwconv7_nhwc_bwd_weight_workspace_bytes(int B, int H, int W, int C);
+int nm_dwconv7_nhwc_bwd_weight(const float* dy, const float* x, const float* act_scale, const float* act_bias, int B, int H, int W, int C,
+                               float* dw49c, void* workspace, size_t workspace_bytes, nmStream_t stream);
+size_t nm_star_relu_bwd_workspace_bytes(size_t n);
+int nm_star_relu_bwd(const float* x, const float* dy, const float* scale, size_t n, float* dx, float* dscale_dbias, void* workspace,
+                     size_t workspace_bytes, nmStream_t stream);
+int nm_conv_patches_bwd(const float* drows, int layout, int B, int C, int H, int W, int k, int stride, int pad, int ld, float* dx,
+                        nmStream_t stream);
+
 /* The reference's encoding MODULES as callable entry points (its evaluator reaches into renderer.xyz_encoder / dirs_encoder directly,
  * nerfmatch/nerfmatch_evaluator.py:385-393).  The fused kernels never call these: they produce the same encodings as MFMA operands.
  *   nm_mip_encode: PositionalEncodingMIP.forward(x, y) (nerfmatch/nerf/embedding.py:66-84) for x, y [n, D], scales 2^min_deg .. 2^(min_deg +

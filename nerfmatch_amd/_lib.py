@@ -100,6 +100,13 @@ SIGNATURES = {
     "nm_star_relu": (i32, [vp, vp, vp, sz, vp, vp]),
     "nm_conv_patches": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "nm_nhwc_to_nchw": (i32, [vp, i32, i32, i32, vp, vp]),
+    "nm_dwconv7_nhwc_bwd_input_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "nm_dwconv7_nhwc_bwd_input": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "nm_dwconv7_nhwc_bwd_weight_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "nm_dwconv7_nhwc_bwd_weight": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "nm_star_relu_bwd_workspace_bytes": (sz, [sz]),
+    "nm_star_relu_bwd": (i32, [vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+    "nm_conv_patches_bwd": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "nm_linear": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "nm_linear_blob_bytes_bf16x3": (sz, [i32, i32]),
     "nm_linear_qkv_bf16x3": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),

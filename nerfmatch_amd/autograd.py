@@ -409,3 +409,108 @@ class _FineExpectation(Function):
 
 def fine_expectation(pt_f, win_f, win=5):
     return _FineExpectation.apply(pt_f, win_f, win)
+
+
+# ----------------------------------------------------------------------------- ConvFormer backbone (modules/convformer.py)
+class _DwConv7Nhwc(Function):
+    """Depthwise 7x7 convolution of StarReLU(x), channel-last: nm_dwconv7_nhwc forward, nm_dwconv7_nhwc_bwd_input / _bwd_weight backward.
+    Saves x; the weight's gradient comes back in the parameter's own (C,1,7,7) layout."""
+
+    @staticmethod
+    def forward(ctx, x, weight, act_scale, act_bias):
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight, act_scale, act_bias)
+        return ops.dwconv7_nhwc(x, weight.detach(), None if act_scale is None else act_scale.detach(),
+                                None if act_bias is None else act_bias.detach())
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, act_scale, act_bias = ctx.saved_tensors
+        act = act_scale is not None
+        need = ctx.needs_input_grad
+        dx, dw49, dsb = ops.dwconv7_nhwc_bwd(dy, x, ops.dwconv_weight_taps(weight), None if not act else act_scale.detach(),
+                                            None if not act else act_bias.detach(), need=(need[0], need[1], act and (need[2] or need[3])))
+        dw = dw49.t().reshape(weight.shape) if need[1] else None
+        return dx, dw, dsb[0:1] if act and need[2] else None, dsb[1:2] if act and need[3] else None
+
+
+def dwconv7_nhwc(x, weight, act_scale=None, act_bias=None):
+    return _DwConv7Nhwc.apply(x, weight, act_scale, act_bias)
+
+
+class _StarRelu(Function):
+    """scale * relu(x)**2 + bias, out of place; saves x (nm_star_relu / nm_star_relu_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, scale, bias):
+        x = x.contiguous()
+        ctx.save_for_backward(x, scale)
+        return ops.star_relu(x, scale.detach(), bias.detach())
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, scale = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dsb = ops.star_relu_bwd(x, dy, scale.detach(), need_params=need[1] or need[2])
+        return dx if need[0] else None, dsb[0:1] if need[1] else None, dsb[1:2] if need[2] else None
+
+
+def star_relu(x, scale, bias):
+    return _StarRelu.apply(x, scale, bias)
+
+
+class _ConvPatches(Function):
+    """ops.conv_patches' rows; the backward (nm_conv_patches_bwd) exists for channel-last inputs only."""
+
+    @staticmethod
+    def forward(ctx, x, k, stride, pad, ld, channel_last):
+        ctx.meta = (tuple(x.shape), k, stride, pad, channel_last)
+        return ops.conv_patches(x.contiguous(), k, stride, pad, ld, channel_last)[0]
+
+    @staticmethod
+    def backward(ctx, drows):
+        shape, k, stride, pad, channel_last = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        if not channel_last:
+            raise _lib.NerfmatchAmdError("conv_patches: the backward exists for channel-last inputs only")
+        return ops.conv_patches_bwd(drows, shape, k, stride, pad), None, None, None, None, None
+
+
+def conv_patches(x, k, stride, pad, ld, channel_last=False):
+    return _ConvPatches.apply(x, k, stride, pad, ld, channel_last)
+
+
+class _NhwcToNchw(Function):
+    """(B,h,w,C) -> (B,C,h,w); the backward is the inverse transpose (nm_add_sine_pe without a table)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return ops.nhwc_to_nchw(x.contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, Cc, h, w = dy.shape
+        return ops.nchw_to_tokens(dy).view(B, h, w, Cc)
+
+
+def nhwc_to_nchw(x):
+    return _NhwcToNchw.apply(x)
+
+
+class _ConvWeightRows(Function):
+    """ops.conv_weight_rows' (N, ld) matrix of a Conv2d weight; the gradient returns in the parameter's (N,C,k,k) layout."""
+
+    @staticmethod
+    def forward(ctx, weight, ld):
+        ctx.shape = tuple(weight.shape)
+        return ops.conv_weight_rows(weight, ld).detach()  # (a tensor object of its own: the cached one is handed out again)
+
+    @staticmethod
+    def backward(ctx, drows):
+        N, Cc, k, _ = ctx.shape
+        return drows[:, :k * k * Cc].view(N, k, k, Cc).permute(0, 3, 1, 2), None
+
+
+def conv_weight_rows(weight, ld):
+    return _ConvWeightRows.apply(weight, ld)

@@ -16,36 +16,12 @@
 // then start on both 128-byte halves of the 256-byte bank row; with an even pitch all four start on the same half (2-way conflict).
 // Arithmetic intensity: 98 flop per 8 bytes of compulsory traffic; at the chip's copy rate that is close to the rate of unpacked fp32
 // FMAs, so the kernel is expected to sit between the two bounds, not at the copy rate.
-#include "common.h"
+#include "convformer_tile.h"
 
 namespace {
 
-constexpr int DW_TH = NM_DWCONV_TILE_H, DW_TW = NM_DWCONV_TILE_W;
-constexpr int DW_CS = 32;                 // channels of a workgroup (8 lanes x 4 channels = 128 B per pixel)
-constexpr int DW_RUN = 8;                 // outputs along x per lane
-constexpr int DW_THREADS = 256;
-constexpr int DW_LOADS = 8;               // staging: 16-byte loads of a thread in flight together
-constexpr int DW_IH = DW_TH + 6, DW_IW = DW_TW + 6;
-constexpr int DW_PITCH = DW_IW | 1;       // pixels per staged row (odd, see above)
-constexpr int DW_QUADS = DW_CS / 4;       // 16-byte words per pixel
-constexpr int DW_MAX_SIDE = 8192, DW_MAX_C = 1024;
-
 static_assert((DW_TW / DW_RUN) * DW_TH * DW_QUADS == DW_THREADS, "one run of outputs per lane");
 static_assert((DW_IH * DW_PITCH + 49) * DW_CS * 4 <= 80 * 1024, "two workgroups per compute unit");
-
-// StarReLU, op for op (three roundings; a NaN passes through the comparison)
-__device__ __forceinline__ float star_relu1(float x, float scale, float bias) {
-  const float r = x < 0.f ? 0.f : x;
-  float t = r * r;
-  t = scale * t;
-  return t + bias;
-}
-__device__ __forceinline__ f32x4 star_relu4(f32x4 v, float scale, float bias) {
-  f32x4 o;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) o[i] = star_relu1(v[i], scale, bias);
-  return o;
-}
 
 __global__ void __launch_bounds__(DW_THREADS) dwconv7_nhwc_kernel(const float* __restrict__ x, const float* __restrict__ w49c,
                                                                   const float* __restrict__ act_scale, const float* __restrict__ act_bias,
@@ -180,8 +156,6 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const float* __restri
     if (p0 + p < HW && c0 + c < C) y[base + (size_t)(c0 + c) * HW + p0 + p] = tile[p][c];
   }
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

@@ -292,7 +292,7 @@ class _MatcherBase(nn.Module):
     def _backbone_maps(self, img):
         """self.backbone(img) with autograd recording only inside autograd.training(), like every other stage of the matcher: an inference
         pass records nothing whatever torch's grad mode is, so the native backbone (modules/convformer.py), which leaves its HIP kernels
-        whenever autograd must record, stays on them."""
+        whenever torch's grad mode would record outside autograd.training(), stays on them; inside it the backbone records its own kernels."""
         with torch.set_grad_enabled(ag.is_training()):
             return self.backbone(img)
 

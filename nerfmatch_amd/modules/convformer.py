@@ -15,11 +15,14 @@ Parameter names are those of timm's flattened feature network (`stem.conv.weight
 a reference checkpoint's `backbone.*` tensors load with strict=True.  timm itself is not a dependency and parity against timm's own
 module is not pinned by a test; the architecture above is the specification.
 
-Two paths compute it:
+Three paths compute it:
   * device tensors without autograd -- channel-last rows through ops.linear / ops.layernorm and the four kernels of
     csrc/convformer.hip, a chunk of images at a time;
-  * host tensors, or whenever autograd must record -- the same architecture with torch.nn.functional (the behaviour without a GPU,
-    and the training path until backward kernels exist).
+  * device tensors inside `autograd.training()` with a trainable parameter -- the same sequence of kernels, recorded through the
+    Functions of nerfmatch_amd/autograd.py whose backward is csrc/convformer_bwd.hip and the GEMM / LayerNorm backward kernels; the
+    whole batch in one piece (the ordered parameter-gradient sums run over the batch), every block's intermediates kept;
+  * host tensors, an image that requires grad, torch's grad mode outside `autograd.training()`, or `train_native = False` -- the same
+    architecture with torch.nn.functional (the behaviour without a GPU, and the yardstick of scripts/perf_backbone_train.py).
 Parameters require grad by default, so a DIRECT call `backbone(img)` on the device under torch's default grad mode takes the plain-torch
 path: wrap inference in `torch.no_grad()` (the matchers do the equivalent themselves: they record only inside autograd.training()).
 """
@@ -29,6 +32,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
+from .. import autograd as ag
 from .. import ops
 
 DIMS = (128, 256)
@@ -136,6 +140,8 @@ class ConvFormerStages(nn.Module):
         # Native path: images go through in chunks so that the widest intermediate -- fc1's output, 4 d floats per pixel of a stage -- stays
         # under this many bytes (one image per chunk at the least).  Results do not depend on it: every kernel's arithmetic is per row / pixel.
         self.chunk_bytes = 512 << 20
+        # Training inside autograd.training() records through the HIP forward / backward kernels; False: through torch.nn.functional.
+        self.train_native = True
 
     # ---- loading -------------------------------------------------------------------------------------------------------------------
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
@@ -223,6 +229,45 @@ class ConvFormerStages(nn.Module):
             ops.nhwc_to_nchw(x.view(n, h1, w1, DIMS[1]), out=outs[1][b0:b0 + n])
         return [outs[s] for s in self.out_stages]
 
+    # ---- HIP kernels, recorded (nerfmatch_amd.autograd) ------------------------------------------------------------------------------
+    def _block_native_train(self, x, blk, shape):
+        tm, mlp = blk.token_mixer, blk.mlp
+        d = x.shape[1]
+        zero = self._zeros(d, x.device)
+        t = ag.linear(ag.layernorm(x, blk.norm1.weight, zero, EPS), tm.pwconv1.weight.view(2 * d, d))
+        t = ag.dwconv7_nhwc(t.view(*shape, 2 * d), tm.dwconv.weight, tm.act1.scale, tm.act1.bias)
+        x = ag.linear(t.view(-1, 2 * d), tm.pwconv2.weight.view(d, 2 * d), residual=x)
+        t = ag.linear(ag.layernorm(x, blk.norm2.weight, zero, EPS), mlp.fc1.weight.view(4 * d, d))
+        t = ag.star_relu(t, mlp.act.scale, mlp.act.bias)
+        return ag.linear(t, mlp.fc2.weight.view(d, 4 * d), residual=x)
+
+    def _forward_native_train(self, img):
+        """_forward_native's sequence on the recording functions, the whole batch in one piece: the same kernels, so the same bits."""
+        img = img.contiguous()
+        B, _, H, W = img.shape
+        dev = img.device
+        h0, w0 = (ops.conv_out_size(n, 7, self.stem_stride, self.stem_pad) for n in (H, W))
+        if h0 < 1 or w0 < 1:
+            raise ValueError(f"ConvFormerStages: a {H}x{W} image is smaller than the stem's kernel")
+        h1, w1 = (ops.conv_out_size(n, 3, self.down_stride, 1) for n in (h0, w0))
+        ds = self.stages_1.downsample
+        rows = ag.conv_patches(img, 7, self.stem_stride, self.stem_pad, STEM_LD)
+        x = ag.linear(rows, ag.conv_weight_rows(self.stem.conv.weight, STEM_LD), self.stem.conv.bias)
+        del rows
+        x = ag.layernorm(x, self.stem.norm.weight, self._zeros(DIMS[0], dev), EPS)
+        for blk in self.stages_0.blocks:
+            x = self._block_native_train(x, blk, (B, h0, w0))
+        maps = {0: ag.nhwc_to_nchw(x.view(B, h0, w0, DIMS[0])) if 0 in self.out_stages else None}
+        if 1 in self.out_stages:
+            t = ag.layernorm(x, ds.norm.weight, self._zeros(DIMS[0], dev), EPS)
+            rows = ag.conv_patches(t.view(B, h0, w0, DIMS[0]), 3, self.down_stride, 1, 9 * DIMS[0], True)
+            x = ag.linear(rows, ag.conv_weight_rows(ds.conv.weight, 9 * DIMS[0]), ds.conv.bias)
+            del rows, t
+            for blk in self.stages_1.blocks:
+                x = self._block_native_train(x, blk, (B, h1, w1))
+            maps[1] = ag.nhwc_to_nchw(x.view(B, h1, w1, DIMS[1]))
+        return [maps[s] for s in self.out_stages]
+
     def _records_grad(self, img):
         return torch.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in self.parameters()))
 
@@ -230,6 +275,8 @@ class ConvFormerStages(nn.Module):
         if img.dim() != 4 or img.shape[1] != 3:
             raise ValueError(f"ConvFormerStages: expected an image batch (B,3,H,W), got {tuple(img.shape)}")
         img = img.to(torch.float32)
+        if img.is_cuda and self.train_native and ag.is_training() and not img.requires_grad and any(p.requires_grad for p in self.parameters()):
+            return self._forward_native_train(img)
         if not img.is_cuda or self._records_grad(img):
             return self._forward_torch(img)
         return self._forward_native(img)

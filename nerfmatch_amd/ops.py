@@ -811,6 +811,61 @@ def star_relu(x, scale, bias, inplace=False):
     return y
 
 
+_DWCONV_BWD_INPUT_WS = {}
+_DWCONV_BWD_WEIGHT_WS = {}
+_STAR_RELU_BWD_WS = {}
+
+
+def dwconv7_nhwc_bwd(dy, x, taps, act_scale=None, act_bias=None, need=(True, True, True)):
+    """Backward of dwconv7_nhwc (nm_dwconv7_nhwc_bwd_input / _bwd_weight): dy, x (B,H,W,C), taps (49,C) ->
+    (dx, dw49c (49,C) tap-major, dscale_dbias (2,)); need = which of (dx, dw49c, the two scalars) to compute, None for the others --
+    dw49c alone costs one kernel, the scalars come out of the input-gradient kernel."""
+    B, H, W, Cc = x.shape
+    dy = _aligned16(dy.contiguous())
+    assert dy.shape == x.shape and tuple(taps.shape) == (49, Cc)
+    act = act_scale is not None
+    dx = dw = dsb = None
+    if need[0] or (act and need[2]):
+        dx = torch.empty_like(x)
+        ws = None
+        if act and need[2]:
+            dsb = torch.empty(2, device=x.device, dtype=torch.float32)
+            ws = _scratch(_DWCONV_BWD_INPUT_WS, x.device, lib().nm_dwconv7_nhwc_bwd_input_workspace_bytes(B, H, W, Cc))
+        check(lib().nm_dwconv7_nhwc_bwd_input(dptr(dy), dptr(taps), dptr(x) if act else None, dptr(act_scale), B, H, W, Cc, dptr(dx), dptr(dsb),
+                                              dptr(ws, torch.uint8), 0 if ws is None else ws.numel(), stream()), "nm_dwconv7_nhwc_bwd_input")
+    if need[1]:
+        dw = torch.empty(49, Cc, device=x.device, dtype=torch.float32)
+        ws = _scratch(_DWCONV_BWD_WEIGHT_WS, x.device, lib().nm_dwconv7_nhwc_bwd_weight_workspace_bytes(B, H, W, Cc))
+        check(lib().nm_dwconv7_nhwc_bwd_weight(dptr(dy), dptr(x), dptr(act_scale), dptr(act_bias), B, H, W, Cc, dptr(dw), dptr(ws, torch.uint8),
+                                               ws.numel(), stream()), "nm_dwconv7_nhwc_bwd_weight")
+    return dx if need[0] else None, dw, dsb
+
+
+def star_relu_bwd(x, dy, scale, need_params=True):
+    """Backward of star_relu (nm_star_relu_bwd): -> (dx like x, dscale_dbias (2,) or None)."""
+    dy = _aligned16(dy.contiguous())
+    if not x.is_contiguous() or dy.shape != x.shape:
+        raise _lib.NerfmatchAmdError("star_relu_bwd: x contiguous and dy of its shape")
+    dx = torch.empty_like(x)
+    dsb = torch.zeros(2, device=x.device, dtype=torch.float32) if need_params else None
+    if x.numel():
+        ws = _scratch(_STAR_RELU_BWD_WS, x.device, lib().nm_star_relu_bwd_workspace_bytes(x.numel())) if need_params else None
+        check(lib().nm_star_relu_bwd(dptr(x), dptr(dy), dptr(scale), x.numel(), dptr(dx), dptr(dsb), dptr(ws, torch.uint8),
+                                     0 if ws is None else ws.numel(), stream()), "nm_star_relu_bwd")
+    return dx, dsb
+
+
+def conv_patches_bwd(drows, shape, k, stride, pad):
+    """The adjoint of conv_patches for a channel-last input of `shape` = (B,H,W,C) (nm_conv_patches_bwd): drows (B*Ho*Wo, ld) -> dx."""
+    B, H, W, Cc = shape
+    drows = _aligned16(drows.contiguous())
+    assert drows.shape[0] == B * conv_out_size(H, k, stride, pad) * conv_out_size(W, k, stride, pad)
+    dx = torch.empty(B, H, W, Cc, device=drows.device, dtype=torch.float32)
+    check(lib().nm_conv_patches_bwd(dptr(drows), 1, B, Cc, H, W, int(k), int(stride), int(pad), drows.shape[1], dptr(dx), stream()),
+          "nm_conv_patches_bwd")
+    return dx
+
+
 def feature_normalize(x):
     """x (B,N,D) is centred IN PLACE (per set b: minus the mean over its N rows); returns the centred set divided by its largest row norm
     (nm_feature_normalize; the coarse model's `pt_feat_norm` option).  x must be contiguous: a silent copy would be centred instead of the
