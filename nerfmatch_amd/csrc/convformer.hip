@@ -9,8 +9,9 @@
 //
 // Depthwise kernel.  One workgroup makes a tile of DW_TH x DW_TW outputs of DW_CS = 32 channels.  The (DW_TH + 6) x (DW_TW + 6) input
 // pixels of those channels go to LDS once, 128 contiguous bytes per pixel, activated as they are staged (an out-of-image pixel is staged as
-// zero: the padding comes behind the activation).  A lane owns four channels and a run of DW_RUN = 8 outputs along x of one row; per kernel
-// row it reads the run's 14 inputs and the row's 7 weights as 16-byte LDS words and issues 8 x 7 x 4 fused multiply-adds, so an output
+// zero: the padding comes behind the activation) -- stage_tile of convformer_tile.h, which the backward kernels stage with too; the sums
+// are dw_tile_body of that header, shared with the input-gradient kernel.  A lane owns four channels and a run of DW_RUN = 8 outputs
+// along x of one row; per kernel row it reads the run's 14 inputs and the row's 7 weights as 16-byte LDS words and issues 8 x 7 x 4 fused multiply-adds, so an output
 // costs (7 * 14 + 49) / 8 = 18 LDS reads instead of 98, and an output's sum is one fmaf chain over the taps in (ky, kx) order whatever
 // tile it falls in.  LDS pitch: 23 pixels (odd) -- the run slots of the 16 lanes that one ds_read_b128 cycle serves (two rows x two runs)
 // then start on both 128-byte halves of the 256-byte bank row; with an even pitch all four start on the same half (2-way conflict).
@@ -20,7 +21,6 @@
 
 namespace {
 
-static_assert((DW_TW / DW_RUN) * DW_TH * DW_QUADS == DW_THREADS, "one run of outputs per lane");
 static_assert((DW_IH * DW_PITCH + 49) * DW_CS * 4 <= 80 * 1024, "two workgroups per compute unit");
 
 __global__ void __launch_bounds__(DW_THREADS) dwconv7_nhwc_kernel(const float* __restrict__ x, const float* __restrict__ w49c,
@@ -37,27 +37,7 @@ __global__ void __launch_bounds__(DW_THREADS) dwconv7_nhwc_kernel(const float* _
 
   for (int i = tid; i < 49 * DW_QUADS; i += DW_THREADS)
     w_s[i] = *reinterpret_cast<const f32x4*>(w49c + (size_t)(i / DW_QUADS) * C + c0 + 4 * (i % DW_QUADS));
-  // DW_LOADS global loads of a thread are in flight together: one at a time, the tile's 16 rounds each wait out a memory latency
-  for (int base = 0; base < DW_IH * DW_IW * DW_QUADS; base += DW_LOADS * DW_THREADS) {
-    f32x4 v[DW_LOADS];
-    int dst[DW_LOADS];
-    bool inside[DW_LOADS];
-#pragma unroll
-    for (int u = 0; u < DW_LOADS; ++u) {
-      const int i = base + u * DW_THREADS + tid;
-      const int q = i % DW_QUADS, p = i / DW_QUADS, px = p % DW_IW, py = p / DW_IW;
-      const int gy = ty0 + py - 3, gx = tx0 + px - 3;
-      dst[u] = i < DW_IH * DW_IW * DW_QUADS ? (py * DW_PITCH + px) * DW_QUADS + q : -1;
-      inside[u] = dst[u] >= 0 && gy >= 0 && gy < H && gx >= 0 && gx < W;
-      v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (inside[u]) v[u] = *reinterpret_cast<const f32x4*>(x + (img + (size_t)gy * W + gx) * C + c0 + 4 * q);
-    }
-#pragma unroll
-    for (int u = 0; u < DW_LOADS; ++u) {
-      if (act && inside[u]) v[u] = star_relu4(v[u], sc, bi);
-      if (dst[u] >= 0) in_s[dst[u]] = v[u];
-    }
-  }
+  stage_tile<DW_IH, DW_IW, DW_PITCH>(x, img, ty0 - 3, tx0 - 3, c0, H, W, C, act, sc, bi, in_s, tid);
   __syncthreads();
 
   const int q = tid % DW_QUADS, slot = tid / DW_QUADS;
@@ -65,23 +45,7 @@ __global__ void __launch_bounds__(DW_THREADS) dwconv7_nhwc_kernel(const float* _
   const int oy = ty0 + row, ox0 = tx0 + run * DW_RUN;
   if (oy >= H || ox0 >= W) return;
   f32x4 acc[DW_RUN];
-#pragma unroll
-  for (int r = 0; r < DW_RUN; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1  // (one kernel row's 21 LDS words live at a time: unrolled, the scheduler hoists all 147 and spills)
-  for (int ky = 0; ky < 7; ++ky) {
-    f32x4 in[DW_RUN + 6], wk[7];
-    const f32x4* src = in_s + ((row + ky) * DW_PITCH + run * DW_RUN) * DW_QUADS + q;
-#pragma unroll
-    for (int i = 0; i < DW_RUN + 6; ++i) in[i] = src[i * DW_QUADS];
-#pragma unroll
-    for (int kx = 0; kx < 7; ++kx) wk[kx] = w_s[(ky * 7 + kx) * DW_QUADS + q];
-#pragma unroll
-    for (int kx = 0; kx < 7; ++kx)
-#pragma unroll
-      for (int r = 0; r < DW_RUN; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] = NM_FMA(in[r + kx][c], wk[kx][c], acc[r][c]);
-  }
+  dw_tile_body(in_s, w_s, q, run, row, acc);
   float* out = y + (img + (size_t)oy * W + ox0) * C + c0 + 4 * q;
 #pragma unroll
   for (int r = 0; r < DW_RUN; ++r)
@@ -163,10 +127,9 @@ extern "C" int nm_dwconv7_nhwc(const float* x, const float* w49c, const float* a
                                float* y, nmStream_t stream) {
   NM_CHECK_ARG(x && w49c && y && x != y && B > 0 && H > 0 && W > 0 && C > 0 && (act_scale != nullptr) == (act_bias != nullptr));
   NM_CHECK_ARG(aligned16(x) && aligned16(w49c) && aligned16(y));
-  if (C % 64 || C > DW_MAX_C || H > DW_MAX_SIDE || W > DW_MAX_SIDE || B > 65535) return NM_ERR_UNSUPPORTED;
-  const int tiles_x = (W + DW_TW - 1) / DW_TW, tiles_y = (H + DW_TH - 1) / DW_TH;
-  const dim3 grid(tiles_x * tiles_y, C / DW_CS, B);
-  dwconv7_nhwc_kernel<<<grid, DW_THREADS, 0, (hipStream_t)stream>>>(x, w49c, act_scale, act_bias, H, W, C, tiles_x, y);
+  if (!dw_supported(B, H, W, C)) return NM_ERR_UNSUPPORTED;
+  const DwTiles t = dw_tiles(H, W, DW_TH);
+  dwconv7_nhwc_kernel<<<dim3(t.x * t.y, C / DW_CS, B), DW_THREADS, 0, (hipStream_t)stream>>>(x, w49c, act_scale, act_bias, H, W, C, t.x, y);
   return nm_launch_status();
 }
 
@@ -181,13 +144,10 @@ extern "C" int nm_star_relu(const float* x, const float* scale, const float* bia
 
 extern "C" int nm_conv_patches(const float* x, int layout, int B, int C, int H, int W, int k, int stride, int pad, int ld, float* rows,
                                nmStream_t stream) {
-  NM_CHECK_ARG(x && rows && x != rows && (layout == 0 || layout == 1) && B > 0 && C > 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0);
   // the NCHW gather reads single floats: a batch slice of odd-sized images starts at any multiple of 4 bytes
-  NM_CHECK_ARG(((uintptr_t)x & 3) == 0 && (layout == 0 || aligned16(x)) && aligned16(rows));
-  if (k > 7 || stride > 8 || pad >= k || C > DW_MAX_C || H > DW_MAX_SIDE || W > DW_MAX_SIDE) return NM_ERR_UNSUPPORTED;
-  NM_CHECK_ARG(ld % 8 == 0 && ld >= k * k * C);
-  NM_CHECK_ARG(H + 2 * pad >= k && W + 2 * pad >= k);
-  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+  const bool aligned = ((uintptr_t)x & 3) == 0 && (layout == 0 || aligned16(x)) && aligned16(rows);
+  int Ho, Wo;
+  if (const int err = conv_patch_args(x, rows, aligned, true, layout, B, C, H, W, k, stride, pad, ld, &Ho, &Wo)) return err;
   const size_t total4 = (size_t)B * Ho * Wo * (ld / 4), blocks = (total4 + 255) / 256;
   if (blocks > 0x7fffffffu) return NM_ERR_UNSUPPORTED;
   if (layout == 1 && C % 4 == 0)

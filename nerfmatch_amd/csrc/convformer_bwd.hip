@@ -10,15 +10,17 @@
 // Every reduction is ordered: a workgroup writes its partial sums to the caller's workspace and a finishing kernel adds them in index
 // order.  No floating-point atomics, the same bits on every run.
 //
-// Input gradient.  The forward tile kernel with dy staged in place of x and the taps read mirrored (LDS slot t holds tap 48 - t), so da is
-// one fmaf chain per element whatever tile it falls in; the epilogue reads x at the lane's own outputs, multiplies and keeps the two
+// Input gradient.  The forward tile kernel -- stage_tile and dw_tile_body of convformer_tile.h, the same text for both -- with dy staged
+// in place of x and the taps loaded mirrored (LDS slot t holds tap 48 - t), so da is one fmaf chain per element whatever tile it falls in;
+// the epilogue reads x at the lane's own outputs, multiplies and keeps the two
 // scalar sums, reduced over the workgroup (xor butterfly per wavefront, the four wavefronts in order) into one partial pair.
 //
 // Weight gradient.  The sum runs over pixels, so a lane that owns pixels (the forward's plan) needs all 49 x 4 sums of its channel quad
 // live at once: 196 accumulators next to 32 registers of dy and 56 of staged inputs are more than the 256 registers that still allow two
 // wavefronts per SIMD, and the 49 x 32-lane reduction would come once per tile.  Here a lane owns TAPS instead: channel quad q, kernel row
 // ky and one of four row groups of the tile -- 7 x 4 = 28 accumulators, kept in registers while the workgroup walks a whole strip of tiles
-// along x.  Both operands then come from LDS: the activated inputs with their halo, staged as in the forward kernel, and the tile's dy.
+// along x.  Both operands then come from LDS: the activated inputs with their halo, staged by the forward kernel's stage_tile, and the
+// tile's dy.
 // A wavefront is one row group: its lanes are (q, ky) with ky = 7 idle (one lane in eight), they read the same dy word per q (a broadcast)
 // and input rows row + ky, which the odd pitch spreads over both halves of the bank row as in the forward kernel.  Per run of 8 pixels a
 // lane reads 8 + 14 LDS words for 224 fused multiply-adds.  Tile: BW_TH x 16 pixels with BW_TH = 8, so that inputs (14 x 23 pixels) and
@@ -35,39 +37,16 @@ constexpr int BW_ROWS = BW_TH / BW_GROUPS;                 // rows of a group
 constexpr int SRB_QUADS = 8;                               // nm_star_relu_bwd: 16-byte words per thread
 constexpr int RED_THREADS = 256;
 
-static_assert((DW_TW / DW_RUN) * DW_TH * DW_QUADS == DW_THREADS, "one run of outputs per lane");
 static_assert(BW_TH % BW_GROUPS == 0 && DW_TW % DW_RUN == 0, "whole rows and runs per group");
 static_assert((BW_IH * DW_PITCH + BW_TH * DW_TW) * DW_CS * 4 <= 80 * 1024, "two workgroups per compute unit");
 static_assert(BW_GROUPS * 49 <= BW_IH * DW_PITCH, "the group sums fit into the input tile's LDS");
 
-// ROWS x COLS pixels of DW_CS channels from (y0, x0) on to LDS, PITCH pixels per row; pixels outside the image are staged as zero, the
-// others activated when `act`.  The forward kernel's staging loop without its branches: every load is issued, at the address clamped into
-// the image, and a word from outside is replaced by zeros behind the activation.
-template <int ROWS, int COLS, int PITCH>
-__device__ __forceinline__ void stage_tile(const float* __restrict__ src, size_t img, int y0, int x0, int c0, int H, int W, int C, bool act,
-                                           float sc, float bi, f32x4* __restrict__ dst_s, int tid) {
-  constexpr int N = ROWS * COLS * DW_QUADS;
-  constexpr int LOADS = N < DW_LOADS * DW_THREADS ? (N + DW_THREADS - 1) / DW_THREADS : DW_LOADS;
-  for (int base = 0; base < N; base += LOADS * DW_THREADS) {
-    f32x4 v[LOADS];
-    int dst[LOADS];
-    bool inside[LOADS];
-#pragma unroll
-    for (int u = 0; u < LOADS; ++u) {
-      const int i = min(base + u * DW_THREADS + tid, N - 1);  // (past the end: the last word once more)
-      const int q = i % DW_QUADS, p = i / DW_QUADS, px = p % COLS, py = p / COLS;
-      const int gy = y0 + py, gx = x0 + px;
-      dst[u] = (py * PITCH + px) * DW_QUADS + q;
-      inside[u] = gy >= 0 && gy < H && gx >= 0 && gx < W;
-      const int cy = min(max(gy, 0), H - 1), cx = min(max(gx, 0), W - 1);
-      v[u] = *reinterpret_cast<const f32x4*>(src + (img + (size_t)cy * W + cx) * C + c0 + 4 * q);
-    }
-#pragma unroll
-    for (int u = 0; u < LOADS; ++u) {
-      if (act) v[u] = star_relu4(v[u], sc, bi);
-      dst_s[dst[u]] = inside[u] ? v[u] : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
+// StarReLU's derivative, op for op: returns dx and adds this element's terms of dscale and dbias to ps and pb
+__device__ __forceinline__ float star_relu_bwd1(float x, float dy, float sc, float& ps, float& pb) {
+  const float r = x < 0.f ? 0.f : x;
+  ps += dy * (r * r);
+  pb += dy;
+  return dy * (2.f * (sc * r));
 }
 
 // sum of v over the workgroup's DW_THREADS lanes, valid in thread 0: butterfly per wavefront, then the wavefronts in order
@@ -109,23 +88,7 @@ __global__ void __launch_bounds__(DW_THREADS, 2) dwconv7_bwd_input_kernel(const 
   float ps = 0.f, pb = 0.f;
   if (valid) {
     f32x4 acc[DW_RUN];
-#pragma unroll
-    for (int r = 0; r < DW_RUN; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1  // (one kernel row's 21 LDS words live at a time, as in the forward kernel)
-    for (int ky = 0; ky < 7; ++ky) {
-      f32x4 in[DW_RUN + 6], wk[7];
-      const f32x4* src = in_s + ((row + ky) * DW_PITCH + run * DW_RUN) * DW_QUADS + q;
-#pragma unroll
-      for (int i = 0; i < DW_RUN + 6; ++i) in[i] = src[i * DW_QUADS];
-#pragma unroll
-      for (int kx = 0; kx < 7; ++kx) wk[kx] = w_s[(ky * 7 + kx) * DW_QUADS + q];
-#pragma unroll
-      for (int kx = 0; kx < 7; ++kx)
-#pragma unroll
-        for (int r = 0; r < DW_RUN; ++r)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) acc[r][c] = NM_FMA(in[r + kx][c], wk[kx][c], acc[r][c]);
-    }
+    dw_tile_body(in_s, w_s, q, run, row, acc);
     const size_t o = (img + (size_t)oy * W + ox0) * C + c0 + 4 * q;
 #pragma unroll
     for (int r = 0; r < DW_RUN; ++r) {
@@ -134,12 +97,7 @@ __global__ void __launch_bounds__(DW_THREADS, 2) dwconv7_bwd_input_kernel(const 
       if (act) {
         const f32x4 xv = *reinterpret_cast<const f32x4*>(x + o + (size_t)r * C);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float rr = xv[c] < 0.f ? 0.f : xv[c];
-          ps += acc[r][c] * (rr * rr);
-          pb += acc[r][c];
-          g[c] = acc[r][c] * (2.f * (sc * rr));
-        }
+        for (int c = 0; c < 4; ++c) g[c] = star_relu_bwd1(xv[c], acc[r][c], sc, ps, pb);
       }
       *reinterpret_cast<f32x4*>(dx + o + (size_t)r * C) = g;
     }
@@ -243,13 +201,6 @@ __global__ void __launch_bounds__(RED_THREADS) sum_scalars_kernel(const float* _
   if (tid == 0) out[blockIdx.x] = red_s[0];
 }
 
-__device__ __forceinline__ float star_relu_bwd1(float x, float dy, float sc, float& ps, float& pb) {
-  const float r = x < 0.f ? 0.f : x;
-  ps += dy * (r * r);
-  pb += dy;
-  return dy * (2.f * (sc * r));
-}
-
 // a workgroup covers DW_THREADS * SRB_QUADS 16-byte words; block 0 also holds the scalar tail's (at most three) lanes; part as in
 // dwconv7_bwd_input_kernel
 __global__ void __launch_bounds__(DW_THREADS, 4) star_relu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
@@ -305,17 +256,14 @@ __global__ void __launch_bounds__(256) conv_patches_bwd_kernel(const float* __re
   *reinterpret_cast<f32x4*>(dx + i * 4) = s;
 }
 
-bool dw_supported(int B, int H, int W, int C) { return C % 64 == 0 && C <= DW_MAX_C && H <= DW_MAX_SIDE && W <= DW_MAX_SIDE && B <= 65535; }
-size_t input_workgroups(int B, int H, int W, int C) {
-  return (size_t)((W + DW_TW - 1) / DW_TW) * ((H + DW_TH - 1) / DW_TH) * (C / DW_CS) * B;
-}
+size_t input_workgroups(DwTiles t, int B, int C) { return (size_t)t.x * t.y * (C / DW_CS) * B; }
 size_t star_blocks(size_t n) { return (n / 4 + DW_THREADS * SRB_QUADS - 1) / (DW_THREADS * SRB_QUADS) + (n < 4 ? 1 : 0); }
 
 }  // namespace
 
 extern "C" size_t nm_dwconv7_nhwc_bwd_input_workspace_bytes(int B, int H, int W, int C) {
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || !dw_supported(B, H, W, C)) return 0;
-  return 2 * input_workgroups(B, H, W, C) * sizeof(float);
+  return 2 * input_workgroups(dw_tiles(H, W, DW_TH), B, C) * sizeof(float);
 }
 
 extern "C" int nm_dwconv7_nhwc_bwd_input(const float* dy, const float* w49c, const float* x, const float* act_scale, int B, int H, int W, int C,
@@ -324,19 +272,18 @@ extern "C" int nm_dwconv7_nhwc_bwd_input(const float* dy, const float* w49c, con
   NM_CHECK_ARG(x || !dscale_dbias);
   NM_CHECK_ARG(aligned16(dy) && aligned16(w49c) && aligned16(dx) && aligned16(x));
   if (!dw_supported(B, H, W, C)) return NM_ERR_UNSUPPORTED;
-  const size_t wgs = input_workgroups(B, H, W, C);
+  const DwTiles t = dw_tiles(H, W, DW_TH);
+  const size_t wgs = input_workgroups(t, B, C);
   if (dscale_dbias && (!workspace || workspace_bytes < 2 * wgs * sizeof(float))) return NM_ERR_WORKSPACE;
-  const int tiles_x = (W + DW_TW - 1) / DW_TW, tiles_y = (H + DW_TH - 1) / DW_TH;
-  const dim3 grid(tiles_x * tiles_y, C / DW_CS, B);
   float* part = dscale_dbias ? (float*)workspace : nullptr;
-  dwconv7_bwd_input_kernel<<<grid, DW_THREADS, 0, (hipStream_t)stream>>>(dy, w49c, x, act_scale, H, W, C, tiles_x, dx, part);
+  dwconv7_bwd_input_kernel<<<dim3(t.x * t.y, C / DW_CS, B), DW_THREADS, 0, (hipStream_t)stream>>>(dy, w49c, x, act_scale, H, W, C, t.x, dx, part);
   if (part) sum_scalars_kernel<<<2, RED_THREADS, 0, (hipStream_t)stream>>>(part, wgs, dscale_dbias);
   return nm_launch_status();
 }
 
 extern "C" size_t nm_dwconv7_nhwc_bwd_weight_workspace_bytes(int B, int H, int W, int C) {
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || !dw_supported(B, H, W, C)) return 0;
-  return (size_t)B * ((H + BW_TH - 1) / BW_TH) * 49 * C * sizeof(float);
+  return (size_t)B * dw_tiles(H, W, BW_TH).y * 49 * C * sizeof(float);
 }
 
 extern "C" int nm_dwconv7_nhwc_bwd_weight(const float* dy, const float* x, const float* act_scale, const float* act_bias, int B, int H, int W,
@@ -346,12 +293,11 @@ extern "C" int nm_dwconv7_nhwc_bwd_weight(const float* dy, const float* x, const
   NM_CHECK_ARG(aligned16(dy) && aligned16(x) && aligned16(dw49c) && aligned16(workspace));
   if (!dw_supported(B, H, W, C)) return NM_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < nm_dwconv7_nhwc_bwd_weight_workspace_bytes(B, H, W, C)) return NM_ERR_WORKSPACE;
-  const int tiles_x = (W + DW_TW - 1) / DW_TW, tiles_y = (H + BW_TH - 1) / BW_TH;
-  const size_t parts = (size_t)B * tiles_y;
+  const DwTiles t = dw_tiles(H, W, BW_TH);
+  const size_t parts = (size_t)B * t.y;
   if (parts > 0x7fffffffu) return NM_ERR_UNSUPPORTED;
   float* part = (float*)workspace;
-  dwconv7_bwd_weight_kernel<<<dim3(tiles_y, C / DW_CS, B), DW_THREADS, 0, (hipStream_t)stream>>>(dy, x, act_scale, act_bias, H, W, C, tiles_x,
-                                                                                                 part);
+  dwconv7_bwd_weight_kernel<<<dim3(t.y, C / DW_CS, B), DW_THREADS, 0, (hipStream_t)stream>>>(dy, x, act_scale, act_bias, H, W, C, t.x, part);
   sum_rows_kernel<<<(49 * C + RED_THREADS - 1) / RED_THREADS, RED_THREADS, 0, (hipStream_t)stream>>>(part, (int)parts, 49 * C, dw49c);
   return nm_launch_status();
 }
@@ -373,12 +319,10 @@ extern "C" int nm_star_relu_bwd(const float* x, const float* dy, const float* sc
 
 extern "C" int nm_conv_patches_bwd(const float* drows, int layout, int B, int C, int H, int W, int k, int stride, int pad, int ld, float* dx,
                                    nmStream_t stream) {
-  NM_CHECK_ARG(drows && dx && drows != dx && (layout == 0 || layout == 1) && B > 0 && C > 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0);
-  NM_CHECK_ARG(aligned16(drows) && aligned16(dx));
-  if (layout != 1 || C % 4 || k > 7 || stride > 8 || pad >= k || C > DW_MAX_C || H > DW_MAX_SIDE || W > DW_MAX_SIDE) return NM_ERR_UNSUPPORTED;
-  NM_CHECK_ARG(ld % 8 == 0 && ld >= k * k * C);
-  NM_CHECK_ARG(H + 2 * pad >= k && W + 2 * pad >= k);
-  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+  int Ho, Wo;  // (the adjoint exists for channel-last words only)
+  if (const int err = conv_patch_args(drows, dx, aligned16(drows) && aligned16(dx), layout == 1 && C % 4 == 0, layout, B, C, H, W, k, stride, pad,
+                                      ld, &Ho, &Wo))
+    return err;
   const size_t total4 = (size_t)B * H * W * (C / 4), blocks = (total4 + 255) / 256;
   if (blocks > 0x7fffffffu) return NM_ERR_UNSUPPORTED;
   conv_patches_bwd_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(drows, C, H, W, Ho, Wo, k, stride, pad, ld, total4, dx);

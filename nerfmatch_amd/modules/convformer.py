@@ -15,18 +15,19 @@ Parameter names are those of timm's flattened feature network (`stem.conv.weight
 a reference checkpoint's `backbone.*` tensors load with strict=True.  timm itself is not a dependency and parity against timm's own
 module is not pinned by a test; the architecture above is the specification.
 
-Three paths compute it:
-  * device tensors without autograd -- channel-last rows through ops.linear / ops.layernorm and the four kernels of
-    csrc/convformer.hip, a chunk of images at a time;
-  * device tensors inside `autograd.training()` with a trainable parameter -- the same sequence of kernels, recorded through the
-    Functions of nerfmatch_amd/autograd.py whose backward is csrc/convformer_bwd.hip and the GEMM / LayerNorm backward kernels; the
-    whole batch in one piece (the ordered parameter-gradient sums run over the batch), every block's intermediates kept;
+Two arithmetics compute it, the first on two operation sets:
+  * the kernel walk (`_forward_kernels`): channel-last rows through linear / layernorm and the four kernels of csrc/convformer.hip.
+    Device tensors without autograd run it on `ops.*` (`_INFERENCE`), a chunk of images at a time.  Device tensors inside
+    `autograd.training()` with a trainable parameter run the same walk on the Functions of nerfmatch_amd/autograd.py, whose backward
+    is csrc/convformer_bwd.hip and the GEMM / LayerNorm backward kernels: the whole batch in one piece (the ordered
+    parameter-gradient sums run over the batch), every block's intermediates kept;
   * host tensors, an image that requires grad, torch's grad mode outside `autograd.training()`, or `train_native = False` -- the same
     architecture with torch.nn.functional (the behaviour without a GPU, and the yardstick of scripts/perf_backbone_train.py).
 Parameters require grad by default, so a DIRECT call `backbone(img)` on the device under torch's default grad mode takes the plain-torch
 path: wrap inference in `torch.no_grad()` (the matchers do the equivalent themselves: they record only inside autograd.training()).
 """
 import warnings
+from types import SimpleNamespace
 
 import torch
 from torch import nn
@@ -39,6 +40,12 @@ DIMS = (128, 256)
 DEPTHS = (3, 12)
 EPS = 1e-6
 STEM_LD = 152        # 7 * 7 * 3 = 147 patch columns, padded to the GEMM's K granularity
+
+# The operation sets of the kernel walk.  Recording: the module nerfmatch_amd.autograd itself.  Inference: ops.* under the same names
+# and signatures, StarReLU in place and conv_patches returning its rows only.
+_INFERENCE = SimpleNamespace(linear=ops.linear, layernorm=ops.layernorm, dwconv7_nhwc=ops.dwconv7_nhwc, conv_weight_rows=ops.conv_weight_rows,
+                             star_relu=lambda x, scale, bias: ops.star_relu(x, scale, bias, inplace=True),
+                             conv_patches=lambda *args: ops.conv_patches(*args)[0])
 
 
 class _Conv(nn.Module):
@@ -183,19 +190,21 @@ class ConvFormerStages(nn.Module):
             z = cache[(dim, dev)] = torch.zeros(dim, device=dev, dtype=torch.float32)
         return z
 
-    def _block_native(self, x, blk, shape):
-        """x: rows (n*h*w, d) of the channel-last map `shape` = (n, h, w)."""
+    def _block(self, K, x, blk, shape):
+        """One block on the operation set K.  x: rows (n*h*w, d) of the channel-last map `shape` = (n, h, w)."""
         tm, mlp = blk.token_mixer, blk.mlp
         d = x.shape[1]
         zero = self._zeros(d, x.device)
-        t = ops.linear(ops.layernorm(x, blk.norm1.weight, zero, EPS), tm.pwconv1.weight.view(2 * d, d))
-        t = ops.dwconv7_nhwc(t.view(*shape, 2 * d), tm.dwconv.weight, tm.act1.scale, tm.act1.bias)
-        x = ops.linear(t.view(-1, 2 * d), tm.pwconv2.weight.view(d, 2 * d), residual=x)
-        t = ops.linear(ops.layernorm(x, blk.norm2.weight, zero, EPS), mlp.fc1.weight.view(4 * d, d))
-        t = ops.star_relu(t, mlp.act.scale, mlp.act.bias, inplace=True)
-        return ops.linear(t, mlp.fc2.weight.view(d, 4 * d), residual=x)
+        t = K.linear(K.layernorm(x, blk.norm1.weight, zero, EPS), tm.pwconv1.weight.view(2 * d, d))
+        t = K.dwconv7_nhwc(t.view(*shape, 2 * d), tm.dwconv.weight, tm.act1.scale, tm.act1.bias)
+        x = K.linear(t.view(-1, 2 * d), tm.pwconv2.weight.view(d, 2 * d), residual=x)
+        t = K.linear(K.layernorm(x, blk.norm2.weight, zero, EPS), mlp.fc1.weight.view(4 * d, d))
+        t = K.star_relu(t, mlp.act.scale, mlp.act.bias)
+        return K.linear(t, mlp.fc2.weight.view(d, 4 * d), residual=x)
 
-    def _forward_native(self, img):
+    def _forward_kernels(self, img, recording):
+        """The one walk over the kernels: stem -> stage 0 -> downsample -> stage 1 on channel-last rows.  Inference and recording run
+        this same sequence on their operation sets, so the recorded maps have the inference bits."""
         img = img.contiguous()
         B, _, H, W = img.shape
         dev = img.device
@@ -203,70 +212,40 @@ class ConvFormerStages(nn.Module):
         if h0 < 1 or w0 < 1:
             raise ValueError(f"ConvFormerStages: a {H}x{W} image is smaller than the stem's kernel")
         h1, w1 = (ops.conv_out_size(n, 3, self.down_stride, 1) for n in (h0, w0))
-        outs = {0: torch.empty(B, DIMS[0], h0, w0, device=dev, dtype=torch.float32) if 0 in self.out_stages else None,
-                1: torch.empty(B, DIMS[1], h1, w1, device=dev, dtype=torch.float32) if 1 in self.out_stages else None}
-        per_image = max(h0 * w0 * 4 * DIMS[0], h1 * w1 * 4 * DIMS[1]) * 4
-        step = max(1, int(self.chunk_bytes) // per_image)
+        hw = {0: (h0, w0), 1: (h1, w1)}
+        if recording:  # the whole batch in one piece (the ordered parameter-gradient sums run over the batch); the maps are Function outputs
+            K, step, outs = ag, B, {}
+
+            def emit(s, x, b0):
+                outs[s] = ag.nhwc_to_nchw(x)
+        else:          # a chunk of images at a time, each chunk's planes written straight into the preallocated maps
+            per_image = max(h0 * w0 * 4 * DIMS[0], h1 * w1 * 4 * DIMS[1]) * 4
+            K, step = _INFERENCE, max(1, int(self.chunk_bytes) // per_image)
+            outs = {s: torch.empty(B, DIMS[s], *hw[s], device=dev, dtype=torch.float32) for s in set(self.out_stages)}
+
+            def emit(s, x, b0):
+                ops.nhwc_to_nchw(x, out=outs[s][b0:b0 + x.shape[0]])
         ds = self.stages_1.downsample
         for b0 in range(0, B, step):
             n = min(step, B - b0)
-            rows, _ = ops.conv_patches(img[b0:b0 + n], 7, self.stem_stride, self.stem_pad, STEM_LD)
-            x = ops.linear(rows, ops.conv_weight_rows(self.stem.conv.weight, STEM_LD), self.stem.conv.bias)
+            rows = K.conv_patches(img[b0:b0 + n], 7, self.stem_stride, self.stem_pad, STEM_LD)
+            x = K.linear(rows, K.conv_weight_rows(self.stem.conv.weight, STEM_LD), self.stem.conv.bias)
             del rows
-            x = ops.layernorm(x, self.stem.norm.weight, self._zeros(DIMS[0], dev), EPS)
+            x = K.layernorm(x, self.stem.norm.weight, self._zeros(DIMS[0], dev), EPS)
             for blk in self.stages_0.blocks:
-                x = self._block_native(x, blk, (n, h0, w0))
-            if outs[0] is not None:
-                ops.nhwc_to_nchw(x.view(n, h0, w0, DIMS[0]), out=outs[0][b0:b0 + n])
-            if outs[1] is None:
+                x = self._block(K, x, blk, (n, h0, w0))
+            if 0 in self.out_stages:
+                emit(0, x.view(n, h0, w0, DIMS[0]), b0)
+            if 1 not in self.out_stages:
                 continue
-            t = ops.layernorm(x, ds.norm.weight, self._zeros(DIMS[0], dev), EPS)
-            rows, _ = ops.conv_patches(t.view(n, h0, w0, DIMS[0]), 3, self.down_stride, 1, 9 * DIMS[0], channel_last=True)
-            x = ops.linear(rows, ops.conv_weight_rows(ds.conv.weight, 9 * DIMS[0]), ds.conv.bias)
+            t = K.layernorm(x, ds.norm.weight, self._zeros(DIMS[0], dev), EPS)
+            rows = K.conv_patches(t.view(n, h0, w0, DIMS[0]), 3, self.down_stride, 1, 9 * DIMS[0], True)
+            x = K.linear(rows, K.conv_weight_rows(ds.conv.weight, 9 * DIMS[0]), ds.conv.bias)
             del rows, t
             for blk in self.stages_1.blocks:
-                x = self._block_native(x, blk, (n, h1, w1))
-            ops.nhwc_to_nchw(x.view(n, h1, w1, DIMS[1]), out=outs[1][b0:b0 + n])
+                x = self._block(K, x, blk, (n, h1, w1))
+            emit(1, x.view(n, h1, w1, DIMS[1]), b0)
         return [outs[s] for s in self.out_stages]
-
-    # ---- HIP kernels, recorded (nerfmatch_amd.autograd) ------------------------------------------------------------------------------
-    def _block_native_train(self, x, blk, shape):
-        tm, mlp = blk.token_mixer, blk.mlp
-        d = x.shape[1]
-        zero = self._zeros(d, x.device)
-        t = ag.linear(ag.layernorm(x, blk.norm1.weight, zero, EPS), tm.pwconv1.weight.view(2 * d, d))
-        t = ag.dwconv7_nhwc(t.view(*shape, 2 * d), tm.dwconv.weight, tm.act1.scale, tm.act1.bias)
-        x = ag.linear(t.view(-1, 2 * d), tm.pwconv2.weight.view(d, 2 * d), residual=x)
-        t = ag.linear(ag.layernorm(x, blk.norm2.weight, zero, EPS), mlp.fc1.weight.view(4 * d, d))
-        t = ag.star_relu(t, mlp.act.scale, mlp.act.bias)
-        return ag.linear(t, mlp.fc2.weight.view(d, 4 * d), residual=x)
-
-    def _forward_native_train(self, img):
-        """_forward_native's sequence on the recording functions, the whole batch in one piece: the same kernels, so the same bits."""
-        img = img.contiguous()
-        B, _, H, W = img.shape
-        dev = img.device
-        h0, w0 = (ops.conv_out_size(n, 7, self.stem_stride, self.stem_pad) for n in (H, W))
-        if h0 < 1 or w0 < 1:
-            raise ValueError(f"ConvFormerStages: a {H}x{W} image is smaller than the stem's kernel")
-        h1, w1 = (ops.conv_out_size(n, 3, self.down_stride, 1) for n in (h0, w0))
-        ds = self.stages_1.downsample
-        rows = ag.conv_patches(img, 7, self.stem_stride, self.stem_pad, STEM_LD)
-        x = ag.linear(rows, ag.conv_weight_rows(self.stem.conv.weight, STEM_LD), self.stem.conv.bias)
-        del rows
-        x = ag.layernorm(x, self.stem.norm.weight, self._zeros(DIMS[0], dev), EPS)
-        for blk in self.stages_0.blocks:
-            x = self._block_native_train(x, blk, (B, h0, w0))
-        maps = {0: ag.nhwc_to_nchw(x.view(B, h0, w0, DIMS[0])) if 0 in self.out_stages else None}
-        if 1 in self.out_stages:
-            t = ag.layernorm(x, ds.norm.weight, self._zeros(DIMS[0], dev), EPS)
-            rows = ag.conv_patches(t.view(B, h0, w0, DIMS[0]), 3, self.down_stride, 1, 9 * DIMS[0], True)
-            x = ag.linear(rows, ag.conv_weight_rows(ds.conv.weight, 9 * DIMS[0]), ds.conv.bias)
-            del rows, t
-            for blk in self.stages_1.blocks:
-                x = self._block_native_train(x, blk, (B, h1, w1))
-            maps[1] = ag.nhwc_to_nchw(x.view(B, h1, w1, DIMS[1]))
-        return [maps[s] for s in self.out_stages]
 
     def _records_grad(self, img):
         return torch.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in self.parameters()))
@@ -276,10 +255,10 @@ class ConvFormerStages(nn.Module):
             raise ValueError(f"ConvFormerStages: expected an image batch (B,3,H,W), got {tuple(img.shape)}")
         img = img.to(torch.float32)
         if img.is_cuda and self.train_native and ag.is_training() and not img.requires_grad and any(p.requires_grad for p in self.parameters()):
-            return self._forward_native_train(img)
+            return self._forward_kernels(img, recording=True)
         if not img.is_cuda or self._records_grad(img):
             return self._forward_torch(img)
-        return self._forward_native(img)
+        return self._forward_kernels(img, recording=False)
 
 
 class ConvFormerMS(nn.Module):

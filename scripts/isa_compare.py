@@ -4,8 +4,8 @@
 
 Each named source is compiled twice with the product flags (nerfmatch_amd.build.FLAGS) plus `-S --cuda-device-only` -- once from
 `git archive PARENT` unpacked into a temporary directory, once from the tree.  The assembly is normalised (comment lines, .file / .loc /
-.ident and the per-compilation __hip_cuid_* symbol dropped) and compared; per kernel the resource counts of the code object's metadata
-are listed for both sides.  Needs hipcc, no GPU.  Prints a markdown table (and writes it to --out).
+.ident and the per-compilation __hip_cuid_* symbol dropped) and compared kernel by kernel (label to end of function, the kernel
+descriptor included); per kernel the resource counts of the code object's metadata are listed for both sides.  Needs hipcc, no GPU.  Prints a markdown table (and writes it to --out).
 """
 import argparse
 import os
@@ -53,6 +53,18 @@ def kernels(asm):
     return out
 
 
+def body(lines, name):
+    """the normalised lines of one kernel: from its label to the end of its function, kernel descriptor included"""
+    a = lines.index(name + ":")
+    return lines[a:next(i for i in range(a, len(lines)) if lines[i].startswith(".Lfunc_end"))]
+
+
+def verdict(a, b):
+    if a == b:
+        return f"identical ({len(a)} lines)"
+    return f"same lines in another order ({len(a)} lines)" if sorted(a) == sorted(b) else f"differs ({len(a)} -> {len(b)} lines)"
+
+
 def short(name):
     r = subprocess.run(["c++filt", name], capture_output=True, text=True)
     d = r.stdout.strip() if r.returncode == 0 and r.stdout.strip() else name
@@ -75,13 +87,11 @@ def main():
         for stem in a.stems:
             pa, br = assembly(Path(tmp), stem), assembly(ROOT, stem)
             na, nb = normalised(pa), normalised(br)
-            same = na == nb
-            verdict = f"identical ({len(na)} lines)" if same else f"differs ({len(na)} -> {len(nb)} lines)"
             kp, kb = kernels(pa), kernels(br)
             assert set(kp) == set(kb), (sorted(kp), sorted(kb))
             for k in sorted(kp):
                 cells = [str(kp[k].get(f)) if kp[k].get(f) == kb[k].get(f) else f"**{kp[k].get(f)} -> {kb[k].get(f)}**" for f in FIELDS]
-                lines.append(f"| `{stem}.hip` | `{short(k)}` | {verdict} | " + " | ".join(cells) + " |")
+                lines.append(f"| `{stem}.hip` | `{short(k)}` | {verdict(body(na, k), body(nb, k))} | " + " | ".join(cells) + " |")
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:

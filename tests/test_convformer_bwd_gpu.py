@@ -276,12 +276,16 @@ def test_frozen_backbone_stays_on_the_inference_path(gpu, built_lib, native_only
     state, img, _, _ = bu.case("c2f", (2, 3, 26, 38))
     m = load_stages("c2f", state, gpu).requires_grad_(False)
     calls = []
-    native = ConvFormerStages._forward_native
-    monkeypatch.setattr(ConvFormerStages, "_forward_native", lambda self, x: calls.append(1) or native(self, x))
-    monkeypatch.setattr(ConvFormerStages, "_forward_native_train", lambda self, x: pytest.fail("recorded with every parameter frozen"))
+    walk = ConvFormerStages._forward_kernels
+
+    def spy(self, x, recording):
+        calls.append(recording)
+        return walk(self, x, recording)
+    monkeypatch.setattr(ConvFormerStages, "_forward_kernels", spy)
     with torch.enable_grad(), ag.training():
         maps = m(img.to(gpu))
-    assert calls == [1] and not any(o.requires_grad for o in maps)
+    # the kernel walk ran exactly once, in inference mode and not in recording mode (recorded with every parameter frozen otherwise)
+    assert calls == [False] and not any(o.requires_grad for o in maps)
 
 
 def test_partly_frozen_backbone(gpu, built_lib, native_only):
