@@ -588,6 +588,36 @@ int nm_conv_patches(const float* x, int layout, int B, int C, int H, int W, int 
                     nmStream_t stream);
 int nm_nhwc_to_nchw(const float* x, int B, int HW, int C, float* y, nmStream_t stream);
 
+/* ---- ConvFormer image backbone: the kernels of the fp16 inference walk (csrc/gemm_f16.hip and, beside their fp32 forms, convformer.hip /
+ * matcher_misc.hip) -------------------------------------------------------------------------------------------------
+ * fp16 buffers are `void*` (IEEE binary16 rows).  A value is stored as fp16 by ONE rounding to nearest even that overflows to infinity:
+ * nothing saturates.  `overflow` (device int32, may be NULL): every kernel that stores fp16 adds the number of stored values that are
+ * not finite while the fp32 value they were rounded from was (the GEMM: while the accumulator, before the activation, was) -- by
+ * ordinary vector atomic adds.  Operands 16-byte aligned unless stated (NM_ERR_ARG), every check before anything is enqueued.
+ *
+ * nm_linear_f16: y[M,N] = epi(x[M,K] . w^T), x fp16 rows, the weight a blob of nm_linear_blob_bytes_f16(N, K) bytes written by
+ *   nm_linear_pack_f16 (w [N,K] fp32 on the device, each value rounded to fp16; asynchronous on `stream`), one product per K-step on
+ *   v_mfma_f32_32x32x16_f16 with fp32 accumulation.  epi(v) = a(v + bias) + residual: bias [N] fp32 or NULL; a = StarReLU on the fp32
+ *   accumulator, op for op nm_star_relu, when star_scale / star_bias (device pointers to one float each; both or neither) are given;
+ *   residual [M,N] fp32 or NULL.  out_f16 = 1: y is fp16 rows (residual must be NULL: NM_ERR_ARG); 0: fp32 rows.  Row m's result does not
+ *   depend on M.  K % 8 == 0 and N % 8 == 0 (NM_ERR_UNSUPPORTED otherwise).
+ * nm_layernorm_f16: nm_layernorm's rows (the same arithmetic: the result is nm_layernorm's, rounded) stored as fp16; dim in {128,256,512};
+ *   y 4-byte aligned.
+ * nm_dwconv7_nhwc_f16: nm_dwconv7_nhwc with x and y fp16: the input widens exactly, activation and sums are the fp32 kernel's, the sum is
+ *   rounded once -- the result is nm_dwconv7_nhwc's on the widened input, rounded.  Same limits.
+ * nm_conv_patches_f16: nm_conv_patches with fp16 rows.  layout 0: x fp32 [B,C,H,W] (4-byte aligned), rounded as it is gathered;
+ *   layout 1: x fp16 [B,H,W,C], C % 8 == 0 (NM_ERR_UNSUPPORTED otherwise), copied.  ld % 8 == 0 and ld >= k*k*C. */
+size_t nm_linear_blob_bytes_f16(int N, int K);
+int nm_linear_pack_f16(const float* w, int N, int K, void* blob, nmStream_t stream);
+int nm_linear_f16(const void* x, const void* blob, const float* bias, const float* star_scale, const float* star_bias,
+                  const float* residual, int M, int N, int K, int out_f16, void* y, int* overflow, nmStream_t stream);
+int nm_layernorm_f16(const float* x, const float* gamma, const float* beta, int rows, int dim, float eps, void* y, int* overflow,
+                     nmStream_t stream);
+int nm_dwconv7_nhwc_f16(const void* x, const float* w49c, const float* act_scale, const float* act_bias, int B, int H, int W, int C,
+                        void* y, int* overflow, nmStream_t stream);
+int nm_conv_patches_f16(const void* x, int layout, int B, int C, int H, int W, int k, int stride, int pad, int ld, void* rows,
+                        int* overflow, nmStream_t stream);
+
 /* ---- ConvFormer image backbone: backward of the kernels above (csrc/convformer_bwd.hip) ----------------------------------------
  * Same conventions: fp32, caller's buffers, 16-byte aligned, every check before anything is enqueued, NM_ERR_UNSUPPORTED beyond the
  * forward kernel's limits.  a(x) = scale * relu(x)^2 + bias, r = relu(x).  Every reduction (dw49c, dscale, dbias) is the sum, in a fixed

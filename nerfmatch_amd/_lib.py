@@ -100,6 +100,13 @@ SIGNATURES = {
     "nm_star_relu": (i32, [vp, vp, vp, sz, vp, vp]),
     "nm_conv_patches": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "nm_nhwc_to_nchw": (i32, [vp, i32, i32, i32, vp, vp]),
+    # ... and its fp16 inference walk (gemm_f16.hip, convformer.hip, matcher_misc.hip)
+    "nm_linear_blob_bytes_f16": (sz, [i32, i32]),
+    "nm_linear_pack_f16": (i32, [vp, i32, i32, vp, vp]),
+    "nm_linear_f16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "nm_layernorm_f16": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp]),
+    "nm_dwconv7_nhwc_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "nm_conv_patches_f16": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "nm_dwconv7_nhwc_bwd_input_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "nm_dwconv7_nhwc_bwd_input": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "nm_dwconv7_nhwc_bwd_weight_workspace_bytes": (sz, [i32, i32, i32, i32]),

@@ -77,6 +77,9 @@ def build_parser():
     p.add_argument("--image_hw", type=str, default="480x640")
     p.add_argument("--samples", type=int, default=64, help="samples per ray of the synthetic NeRF (coarse = fine)")
     p.add_argument("--batch_size", type=int, default=1, help="queries per launch sequence (the reference's loop takes 1)")
+    # (no default: absent from the parsed arguments unless given, so that the checkpoint's own `backbone_precision` holds)
+    p.add_argument("--backbone_precision", type=str, default=argparse.SUPPRESS, choices=["same", "fp16"],
+                   help="inference arithmetic of the native ConvFormer backbone (modules/convformer.py); default: what the checkpoint's config says")
     return p
 
 

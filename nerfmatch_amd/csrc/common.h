@@ -40,6 +40,14 @@ extern "C" int nm_stream_cus(nmStream_t stream);
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// fp16 storage of the backbone's fp16 walk: (_Float16)v rounds to nearest even and overflows to infinity (no saturation).  An overflow
+// EVENT is a stored value that is not finite while the fp32 value `src` it was made from is.
+__device__ __forceinline__ bool f16_overflowed(float src, _Float16 h) {
+  return (__builtin_bit_cast(unsigned short, h) & 0x7c00u) == 0x7c00u && (__builtin_bit_cast(unsigned, src) & 0x7f800000u) != 0x7f800000u;
+}
 
 // accumulator layout of a 32x32 MFMA block: register r of a lane in half `hi` holds row (A side) / feature nrow(r, hi) of the block
 __host__ __device__ __forceinline__ constexpr int nrow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }

@@ -23,9 +23,24 @@ namespace {
 
 static_assert((DW_IH * DW_PITCH + 49) * DW_CS * 4 <= 80 * 1024, "two workgroups per compute unit");
 
-__global__ void __launch_bounds__(DW_THREADS) dwconv7_nhwc_kernel(const float* __restrict__ x, const float* __restrict__ w49c,
+// T: fp32, or fp16 in AND out (the fp16 inference walk): the typed load of stage_tile widens exactly, the LDS image, the activation and the
+// sums are those of the fp32 kernel, and the store rounds the sum once to fp16 (round to nearest even, overflow to infinity; a sum that was
+// finite and is stored as infinity is counted into `overflow`).  So the fp16 kernel's result is the fp32 kernel's on the widened input, rounded.
+__device__ __forceinline__ void store_quad(float* p, f32x4 v, int&) { *reinterpret_cast<f32x4*>(p) = v; }
+__device__ __forceinline__ void store_quad(_Float16* p, f32x4 v, int& events) {
+  f16x4 h;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    h[e] = (_Float16)v[e];
+    events += f16_overflowed(v[e], h[e]) ? 1 : 0;
+  }
+  *reinterpret_cast<f16x4*>(p) = h;
+}
+
+template <class T>
+__global__ void __launch_bounds__(DW_THREADS) dwconv7_nhwc_kernel(const T* __restrict__ x, const float* __restrict__ w49c,
                                                                   const float* __restrict__ act_scale, const float* __restrict__ act_bias,
-                                                                  int H, int W, int C, int tiles_x, float* __restrict__ y) {
+                                                                  int H, int W, int C, int tiles_x, T* __restrict__ y, int* overflow) {
   __shared__ f32x4 in_s[DW_IH * DW_PITCH * DW_QUADS];
   __shared__ f32x4 w_s[49 * DW_QUADS];
   const int tid = threadIdx.x;
@@ -46,10 +61,12 @@ __global__ void __launch_bounds__(DW_THREADS) dwconv7_nhwc_kernel(const float* _
   if (oy >= H || ox0 >= W) return;
   f32x4 acc[DW_RUN];
   dw_tile_body(in_s, w_s, q, run, row, acc);
-  float* out = y + (img + (size_t)oy * W + ox0) * C + c0 + 4 * q;
+  T* out = y + (img + (size_t)oy * W + ox0) * C + c0 + 4 * q;
+  int events = 0;
 #pragma unroll
   for (int r = 0; r < DW_RUN; ++r)
-    if (ox0 + r < W) *reinterpret_cast<f32x4*>(out + (size_t)r * C) = acc[r];
+    if (ox0 + r < W) store_quad(out + (size_t)r * C, acc[r], events);
+  if (events && overflow) atomicAdd(overflow, events);
 }
 
 constexpr int SR_THREADS = 256;
@@ -97,6 +114,49 @@ __global__ void __launch_bounds__(256) conv_patches_kernel(const float* __restri
   *reinterpret_cast<f32x4*>(rows + row * ld + col0) = v;
 }
 
+// The same gather with fp16 rows: one thread per eight columns (one 16-byte word of the row).  LAYOUT 0: fp32 planes, each value rounded to
+// fp16 as it is gathered (an image value that was finite and is stored as infinity is counted into `overflow`); LAYOUT 1: fp16 channel-last
+// rows with C % 8 == 0 -- the eight columns are one 16-byte word of one pixel, copied as it is.
+template <int LAYOUT>
+__global__ void __launch_bounds__(256) conv_patches_f16_kernel(const void* __restrict__ xv, int C, int H, int W, int Ho, int Wo, int k, int stride,
+                                                               int pad, int ld, size_t total8, _Float16* __restrict__ rows, int* overflow) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total8) return;
+  const int ld8 = ld / 8;
+  const size_t row = i / ld8;
+  const int col0 = (int)(i - row * ld8) * 8;
+  const int ox = (int)(row % Wo), oy = (int)((row / Wo) % Ho);
+  const size_t b = row / ((size_t)Wo * Ho);
+  const int kkc = k * k * C;
+  u32x4 out = {0u, 0u, 0u, 0u};
+  if (LAYOUT == 1) {
+    const _Float16* x = static_cast<const _Float16*>(xv);
+    if (col0 < kkc) {
+      const int tap = col0 / C, c = col0 - tap * C, ky = tap / k, kx = tap - ky * k;
+      const int iy = oy * stride - pad + ky, ix = ox * stride - pad + kx;
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) out = *reinterpret_cast<const u32x4*>(x + ((b * H + iy) * W + ix) * C + c);
+    }
+  } else {
+    const float* x = static_cast<const float*>(xv);
+    f16x8 h = {0, 0, 0, 0, 0, 0, 0, 0};
+    int events = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int col = col0 + j;
+      if (col >= kkc) continue;
+      const int tap = col / C, c = col - tap * C, ky = tap / k, kx = tap - ky * k;
+      const int iy = oy * stride - pad + ky, ix = ox * stride - pad + kx;
+      if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
+      const float v = x[((b * C + c) * H + iy) * W + ix];
+      h[j] = (_Float16)v;
+      events += f16_overflowed(v, h[j]) ? 1 : 0;
+    }
+    out = __builtin_bit_cast(u32x4, h);
+    if (events && overflow) atomicAdd(overflow, events);
+  }
+  *reinterpret_cast<u32x4*>(rows + row * ld + col0) = out;
+}
+
 constexpr int TR_TILE = 64;
 
 // y[b][c][p] = x[b][p][c]: a 64 x 64 tile through LDS (pitch 65 words: the column reads touch 64 banks); 16-byte reads along c, the lanes of
@@ -129,7 +189,18 @@ extern "C" int nm_dwconv7_nhwc(const float* x, const float* w49c, const float* a
   NM_CHECK_ARG(aligned16(x) && aligned16(w49c) && aligned16(y));
   if (!dw_supported(B, H, W, C)) return NM_ERR_UNSUPPORTED;
   const DwTiles t = dw_tiles(H, W, DW_TH);
-  dwconv7_nhwc_kernel<<<dim3(t.x * t.y, C / DW_CS, B), DW_THREADS, 0, (hipStream_t)stream>>>(x, w49c, act_scale, act_bias, H, W, C, t.x, y);
+  dwconv7_nhwc_kernel<float><<<dim3(t.x * t.y, C / DW_CS, B), DW_THREADS, 0, (hipStream_t)stream>>>(x, w49c, act_scale, act_bias, H, W, C, t.x, y, nullptr);
+  return nm_launch_status();
+}
+
+extern "C" int nm_dwconv7_nhwc_f16(const void* x, const float* w49c, const float* act_scale, const float* act_bias, int B, int H, int W, int C,
+                                   void* y, int* overflow, nmStream_t stream) {
+  NM_CHECK_ARG(x && w49c && y && x != y && B > 0 && H > 0 && W > 0 && C > 0 && (act_scale != nullptr) == (act_bias != nullptr));
+  NM_CHECK_ARG(aligned16(x) && aligned16(w49c) && aligned16(y));
+  if (!dw_supported(B, H, W, C)) return NM_ERR_UNSUPPORTED;
+  const DwTiles t = dw_tiles(H, W, DW_TH);
+  dwconv7_nhwc_kernel<_Float16><<<dim3(t.x * t.y, C / DW_CS, B), DW_THREADS, 0, (hipStream_t)stream>>>(
+      static_cast<const _Float16*>(x), w49c, act_scale, act_bias, H, W, C, t.x, static_cast<_Float16*>(y), overflow);
   return nm_launch_status();
 }
 
@@ -154,6 +225,20 @@ extern "C" int nm_conv_patches(const float* x, int layout, int B, int C, int H, 
     conv_patches_kernel<true><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, layout, C, H, W, Ho, Wo, k, stride, pad, ld, total4, rows);
   else
     conv_patches_kernel<false><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, layout, C, H, W, Ho, Wo, k, stride, pad, ld, total4, rows);
+  return nm_launch_status();
+}
+
+extern "C" int nm_conv_patches_f16(const void* x, int layout, int B, int C, int H, int W, int k, int stride, int pad, int ld, void* rows,
+                                   int* overflow, nmStream_t stream) {
+  // (layout 0: fp32 planes read as single floats, as nm_conv_patches reads them; layout 1: fp16 pixels read in 16-byte words)
+  const bool aligned = ((uintptr_t)x & 3) == 0 && (layout == 0 || aligned16(x)) && aligned16(rows);
+  int Ho, Wo;
+  if (const int err = conv_patch_args(x, rows, aligned, layout == 0 || C % 8 == 0, layout, B, C, H, W, k, stride, pad, ld, &Ho, &Wo)) return err;
+  const size_t total8 = (size_t)B * Ho * Wo * (ld / 8), blocks = (total8 + 255) / 256;
+  if (blocks > 0x7fffffffu) return NM_ERR_UNSUPPORTED;
+  _Float16* r16 = static_cast<_Float16*>(rows);
+  if (layout == 1) conv_patches_f16_kernel<1><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, C, H, W, Ho, Wo, k, stride, pad, ld, total8, r16, overflow);
+  else conv_patches_f16_kernel<0><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, C, H, W, Ho, Wo, k, stride, pad, ld, total8, r16, overflow);
   return nm_launch_status();
 }
 

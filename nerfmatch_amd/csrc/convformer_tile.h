@@ -36,8 +36,15 @@ __device__ __forceinline__ f32x4 star_relu4(f32x4 v, float scale, float bias) {
 // others activated when `act` (the padding comes behind the activation).  Without branches: every load is issued, at the address
 // clamped into the image, and a word from outside is replaced by zeros behind the activation.  DW_LOADS global loads of a thread are in
 // flight together: one at a time, a 22 x 22 tile's 16 rounds each wait out a memory latency.
-template <int ROWS, int COLS, int PITCH>
-__device__ __forceinline__ void stage_tile(const float* __restrict__ src, size_t img, int y0, int x0, int c0, int H, int W, int C, bool act,
+// `src` is fp32 or fp16 (load_quad: fp16 -> fp32 is exact); the LDS image is fp32 either way.
+__device__ __forceinline__ f32x4 load_quad(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 load_quad(const _Float16* p) {
+  const f16x4 h = *reinterpret_cast<const f16x4*>(p);
+  return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+}
+
+template <int ROWS, int COLS, int PITCH, class T>
+__device__ __forceinline__ void stage_tile(const T* __restrict__ src, size_t img, int y0, int x0, int c0, int H, int W, int C, bool act,
                                            float sc, float bi, f32x4* __restrict__ dst_s, int tid) {
   constexpr int N = ROWS * COLS * DW_QUADS;
   constexpr int LOADS = N < DW_LOADS * DW_THREADS ? (N + DW_THREADS - 1) / DW_THREADS : DW_LOADS;
@@ -53,7 +60,7 @@ __device__ __forceinline__ void stage_tile(const float* __restrict__ src, size_t
       dst[u] = (py * PITCH + px) * DW_QUADS + q;
       inside[u] = gy >= 0 && gy < H && gx >= 0 && gx < W;
       const int cy = min(max(gy, 0), H - 1), cx = min(max(gx, 0), W - 1);
-      v[u] = *reinterpret_cast<const f32x4*>(src + (img + (size_t)cy * W + cx) * C + c0 + 4 * q);
+      v[u] = load_quad(src + (img + (size_t)cy * W + cx) * C + c0 + 4 * q);
     }
 #pragma unroll
     for (int u = 0; u < LOADS; ++u) {

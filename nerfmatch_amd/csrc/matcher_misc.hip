@@ -148,12 +148,36 @@ __global__ void fine_windows_batch_kernel(const float* __restrict__ ffeat, int C
       }
 }
 
-// one wavefront per row; dim = 64 * PER
+// a row's LayerNorm results to memory: as they are, or (the backbone's fp16 walk) rounded to fp16 -- to nearest even, overflow to infinity, a
+// finite value stored as infinity counted
 template <int PER>
-__device__ __forceinline__ void layernorm_row(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b, int rows, float eps,
-                                              float* __restrict__ y, int row) {
+__device__ __forceinline__ void ln_store_row(float* yr, const float (&o)[PER], int lane, int&) {
+#pragma unroll
+  for (int i = 0; i < PER; ++i) yr[lane + 64 * i] = o[i];
+}
+// fp16: neighbouring lanes trade one value per pair of 64-column pieces, so that a lane stores two neighbouring columns as one word -- the
+// even lanes columns (lane, lane + 1) of piece i, the odd lanes columns (lane - 1, lane) of piece i + 1
+template <int PER>
+__device__ __forceinline__ void ln_store_row(_Float16* yr, const float (&o)[PER], int lane, int& events) {
+  static_assert(PER % 2 == 0, "pairs of 64-column pieces");
+  const bool odd = lane & 1;
+#pragma unroll
+  for (int i = 0; i < PER; i += 2) {
+    const _Float16 h0 = (_Float16)o[i], h1 = (_Float16)o[i + 1];
+    events += (f16_overflowed(o[i], h0) ? 1 : 0) + (f16_overflowed(o[i + 1], h1) ? 1 : 0);
+    const unsigned b0 = __builtin_bit_cast(unsigned short, h0), b1 = __builtin_bit_cast(unsigned short, h1);
+    const unsigned got = (unsigned)__shfl_xor((int)(odd ? b0 : b1), 1, 64);
+    const unsigned word = odd ? (got | (b1 << 16)) : (b0 | (got << 16));
+    *reinterpret_cast<unsigned*>(yr + (odd ? lane - 1 + 64 * (i + 1) : lane + 64 * i)) = word;
+  }
+}
+
+// one wavefront per row; dim = 64 * PER; returns the row's overflow events of this lane (fp16 rows only)
+template <int PER, class T>
+__device__ __forceinline__ int layernorm_row(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b, int rows, float eps,
+                                             T* __restrict__ y, int row) {
   const int lane = threadIdx.x & 63;
-  if (row >= rows) return;
+  if (row >= rows) return 0;
   const int dim = 64 * PER;
   const float* xr = x + (size_t)row * dim;
   float v[PER];
@@ -172,16 +196,27 @@ __device__ __forceinline__ void layernorm_row(const float* __restrict__ x, const
   }
   const float var = wave_sum(q) / (float)dim;
   const float rstd = 1.0f / sqrtf(var + eps);
+  float o[PER];
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int c = lane + 64 * i;
-    y[(size_t)row * dim + c] = (v[i] - mean) * rstd * g[c] + b[c];
+    o[i] = (v[i] - mean) * rstd * g[c] + b[c];
   }
+  int events = 0;
+  ln_store_row<PER>(y + (size_t)row * dim, o, lane, events);
+  return events;
 }
 template <int PER>
 __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                         const float* __restrict__ b, int rows, float eps, float* __restrict__ y) {
   layernorm_row<PER>(x, g, b, rows, eps, y, blockIdx.x * 4 + (threadIdx.x >> 6));
+}
+// the same rows stored as fp16 (nm_layernorm_f16): the row arithmetic is layernorm_row's, so the result is nm_layernorm's rounded once
+template <int PER>
+__global__ void __launch_bounds__(256) layernorm_f16_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
+                                                            int rows, float eps, _Float16* __restrict__ y, int* overflow) {
+  const int events = layernorm_row<PER>(x, g, b, rows, eps, y, blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (events && overflow) atomicAdd(overflow, events);
 }
 // two tensors with their own affine parameters in one launch (round 5: the two pre-norms of a cross-attention layer): workgroups [0, g0) take
 // the first, the rest the second; a row's arithmetic is layernorm_kernel's
@@ -425,6 +460,21 @@ extern "C" int nm_layernorm(const float* x, const float* gamma, const float* bet
     case 128: layernorm_kernel<2><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y); break;
     case 256: layernorm_kernel<4><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y); break;
     case 512: layernorm_kernel<8><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y); break;
+    default: return NM_ERR_UNSUPPORTED;
+  }
+  return nm_launch_status();
+}
+
+extern "C" int nm_layernorm_f16(const float* x, const float* gamma, const float* beta, int rows, int dim, float eps, void* y, int* overflow,
+                                nmStream_t stream) {
+  NM_CHECK_ARG(x && gamma && beta && y && (const void*)x != y && rows > 0 && dim > 0 && ((uintptr_t)y & 3) == 0);
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = (rows + 3) / 4;
+  _Float16* y16 = static_cast<_Float16*>(y);
+  switch (dim) {
+    case 128: layernorm_f16_kernel<2><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y16, overflow); break;
+    case 256: layernorm_f16_kernel<4><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y16, overflow); break;
+    case 512: layernorm_f16_kernel<8><<<grid, 256, 0, s>>>(x, gamma, beta, rows, eps, y16, overflow); break;
     default: return NM_ERR_UNSUPPORTED;
   }
   return nm_launch_status();

@@ -393,7 +393,8 @@ class NeRFMatcherMS(_MatcherBase):
     def __init__(self, config):
         super().__init__()
         self.coarse_ds, self.fine_ds = 8, 2
-        self.backbone = init_backbone_8_2(config.backbone, pretrained=getattr(config, "pretrained", False))
+        self.backbone = init_backbone_8_2(config.backbone, pretrained=getattr(config, "pretrained", False),
+                                          precision=getattr(config, "backbone_precision", "same"))
         self._init_common(config)
         self.ffeat_dim = getattr(config, "ffeat_dim", 128)
         bd = self.backbone.feat_dim
@@ -825,7 +826,8 @@ class NeRFMatcherCoarse(_MatcherBase):
     def __init__(self, config):
         super().__init__()
         self.coarse_ds = 8
-        self.backbone = init_backbone(config.backbone, pretrained=getattr(config, "pretrained", False), downsample=self.coarse_ds)
+        self.backbone = init_backbone(config.backbone, pretrained=getattr(config, "pretrained", False), downsample=self.coarse_ds,
+                                      precision=getattr(config, "backbone_precision", "same"))
         self._init_common(config)
         bd = self.backbone.feat_dim
         self.cfeat_proj = nn.Linear(bd, self.cfeat_dim, bias=True) if bd != self.cfeat_dim else None

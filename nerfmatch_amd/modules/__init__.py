@@ -61,19 +61,28 @@ def _convformer_name(name):
                               "ConvFormer/CAFormer-B36, modules/convformer.py) and 'stub'; or pass a module via model.backbone = ...")
 
 
-def init_backbone_8_2(backbone="stub", pretrained=False):
+def _stub_precision(precision):
+    """The stand-in has one arithmetic: "same" passes, anything else is refused like an unknown value (ValueError)."""
+    if precision != "same":
+        raise ValueError(f"backbone 'stub' has no inference precision {precision!r}: \"fp16\" is a mode of the native ConvFormer stages")
+
+
+def init_backbone_8_2(backbone="stub", pretrained=False, precision="same"):
+    """precision: ConvFormerStages.inference_precision ("same", or the opt-in "fp16" inference walk)."""
     if backbone == "stub":
+        _stub_precision(precision)
         return StubBackbone(two_scales=True)
     _convformer_name(backbone)
     from .convformer import ConvFormerMS, pretrained_notice
 
     if pretrained:
         pretrained_notice(backbone)
-    return ConvFormerMS()
+    return ConvFormerMS(precision)
 
 
-def init_backbone(backbone="stub", pretrained=False, downsample=8):
+def init_backbone(backbone="stub", pretrained=False, downsample=8, precision="same"):
     if backbone == "stub":
+        _stub_precision(precision)
         return StubBackbone(two_scales=False)
     _convformer_name(backbone)
     if downsample != 8:
@@ -82,6 +91,6 @@ def init_backbone(backbone="stub", pretrained=False, downsample=8):
 
     if pretrained:
         pretrained_notice(backbone)
-    m = ConvFormerStages(4, 2, 2, (1,))
+    m = ConvFormerStages(4, 2, 2, (1,), precision)
     m.feat_dim = 256
     return m

@@ -20,7 +20,8 @@ Two arithmetics compute it, the first on two operation sets:
     Device tensors without autograd run it on `ops.*` (`_INFERENCE`), a chunk of images at a time.  Device tensors inside
     `autograd.training()` with a trainable parameter run the same walk on the Functions of nerfmatch_amd/autograd.py, whose backward
     is csrc/convformer_bwd.hip and the GEMM / LayerNorm backward kernels: the whole batch in one piece (the ordered
-    parameter-gradient sums run over the batch), every block's intermediates kept;
+    parameter-gradient sums run over the batch), every block's intermediates kept.  With `inference_precision = "fp16"` (opt-in) inference
+    runs the walk on a third set, `_fp16_ops`: fp16 GEMM operands and intermediates around an fp32 residual stream (DESIGN.md 3.8k);
   * host tensors, an image that requires grad, torch's grad mode outside `autograd.training()`, or `train_native = False` -- the same
     architecture with torch.nn.functional (the behaviour without a GPU, and the yardstick of scripts/perf_backbone_train.py).
 Parameters require grad by default, so a DIRECT call `backbone(img)` on the device under torch's default grad mode takes the plain-torch
@@ -46,6 +47,21 @@ STEM_LD = 152        # 7 * 7 * 3 = 147 patch columns, padded to the GEMM's K gra
 _INFERENCE = SimpleNamespace(linear=ops.linear, layernorm=ops.layernorm, dwconv7_nhwc=ops.dwconv7_nhwc, conv_weight_rows=ops.conv_weight_rows,
                              star_relu=lambda x, scale, bias: ops.star_relu(x, scale, bias, inplace=True),
                              conv_patches=lambda *args: ops.conv_patches(*args)[0])
+PRECISIONS = ("same", "fp16")
+
+
+def _fp16_ops(events):
+    """The third operation set: the fp16 inference walk (`inference_precision = "fp16"`) on the overflow counter `events`.
+    The residual stream stays fp32 rows: the GEMMs that end a branch (a residual) or a convolution (a bias) write fp32, and so does the stem's
+    norm, whose output IS the stream (`stream_norm`).  Every other GEMM, every other LayerNorm, the depthwise convolution and the patch
+    gathers store fp16, and the channel MLP's StarReLU rides fc1's epilogue (`star`), so the set has no star_relu."""
+    def linear(x, weight, bias=None, residual=None, star=None):
+        wide = residual is not None or bias is not None
+        return ops.linear_f16(x, weight, bias, residual, star, torch.float32 if wide else torch.float16, events)
+    return SimpleNamespace(linear=linear, stream_norm=ops.layernorm, conv_weight_rows=ops.conv_weight_rows,
+                           layernorm=lambda *args: ops.layernorm_f16(*args, events=events),
+                           dwconv7_nhwc=lambda *args: ops.dwconv7_nhwc_f16(*args, events=events),
+                           conv_patches=lambda *args: ops.conv_patches_f16(*args, events=events)[0])
 
 
 class _Conv(nn.Module):
@@ -135,8 +151,9 @@ class ConvFormerStages(nn.Module):
     (B,256,.,.); sizes follow conv arithmetic floor((n + 2p - k) / s) + 1 at the stem (k 7) and the downsample (k 3, padding 1).
     No norm on the returned maps."""
 
-    def __init__(self, stem_stride, stem_pad, down_stride, out_stages):
+    def __init__(self, stem_stride, stem_pad, down_stride, out_stages, inference_precision="same"):
         super().__init__()
+        self.inference_precision = inference_precision
         self.stem_stride, self.stem_pad, self.down_stride = int(stem_stride), int(stem_pad), int(down_stride)
         self.out_stages = tuple(int(s) for s in out_stages)
         if not self.out_stages or any(s not in (0, 1) for s in self.out_stages):
@@ -149,6 +166,33 @@ class ConvFormerStages(nn.Module):
         self.chunk_bytes = 512 << 20
         # Training inside autograd.training() records through the HIP forward / backward kernels; False: through torch.nn.functional.
         self.train_native = True
+
+    # ---- inference arithmetic -------------------------------------------------------------------------------------------------------
+    @property
+    def inference_precision(self):
+        """"same": the inference walk on ops.linear's arithmetic (ops.LINEAR_PRECISION), fp32 rows throughout.  "fp16" (opt-in): the walk on
+        the fp16 operation set -- fp16 GEMM operands and intermediates, fp32 residual stream, statistics and accumulation.
+        Device tensors outside autograd only: recording inside autograd.training() and the plain-torch path ignore it."""
+        return self._inference_precision
+
+    @inference_precision.setter
+    def inference_precision(self, value):
+        if value not in PRECISIONS:
+            raise ValueError(f"ConvFormerStages.inference_precision must be one of {PRECISIONS}, got {value!r}")
+        self._inference_precision = value
+
+    def _events(self, dev):
+        """This module's overflow counter on `dev` (a device int32; not a buffer: it is no part of the state dict)."""
+        cache = self.__dict__.setdefault("_f16_events", {})
+        if dev not in cache:
+            cache[dev] = ops.f16_events(dev)
+        return cache[dev]
+
+    def overflow_events(self):
+        """Values the fp16 walk has stored as infinity (or NaN) from a finite fp32 value since the module was built, over all devices it ran
+        on.  fp16 conversions do not saturate, so an activation beyond 65504 shows in the returned maps as inf / NaN; this count says that the
+        conversions are where it came from.  Synchronises the device: a diagnostic, not part of a pass."""
+        return sum(int(c.item()) for c in self.__dict__.get("_f16_events", {}).values())
 
     # ---- loading -------------------------------------------------------------------------------------------------------------------
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
@@ -198,8 +242,11 @@ class ConvFormerStages(nn.Module):
         t = K.linear(K.layernorm(x, blk.norm1.weight, zero, EPS), tm.pwconv1.weight.view(2 * d, d))
         t = K.dwconv7_nhwc(t.view(*shape, 2 * d), tm.dwconv.weight, tm.act1.scale, tm.act1.bias)
         x = K.linear(t.view(-1, 2 * d), tm.pwconv2.weight.view(d, 2 * d), residual=x)
-        t = K.linear(K.layernorm(x, blk.norm2.weight, zero, EPS), mlp.fc1.weight.view(4 * d, d))
-        t = K.star_relu(t, mlp.act.scale, mlp.act.bias)
+        t = K.layernorm(x, blk.norm2.weight, zero, EPS)
+        if hasattr(K, "star_relu"):
+            t = K.star_relu(K.linear(t, mlp.fc1.weight.view(4 * d, d)), mlp.act.scale, mlp.act.bias)
+        else:  # (the fp16 set: the activation is fc1's epilogue)
+            t = K.linear(t, mlp.fc1.weight.view(4 * d, d), star=(mlp.act.scale, mlp.act.bias))
         return K.linear(t, mlp.fc2.weight.view(d, 4 * d), residual=x)
 
     def _forward_kernels(self, img, recording):
@@ -219,19 +266,21 @@ class ConvFormerStages(nn.Module):
             def emit(s, x, b0):
                 outs[s] = ag.nhwc_to_nchw(x)
         else:          # a chunk of images at a time, each chunk's planes written straight into the preallocated maps
-            per_image = max(h0 * w0 * 4 * DIMS[0], h1 * w1 * 4 * DIMS[1]) * 4
-            K, step = _INFERENCE, max(1, int(self.chunk_bytes) // per_image)
+            fp16 = self.inference_precision == "fp16"
+            per_image = max(h0 * w0 * 4 * DIMS[0], h1 * w1 * 4 * DIMS[1]) * (2 if fp16 else 4)
+            K, step = _fp16_ops(self._events(dev)) if fp16 else _INFERENCE, max(1, int(self.chunk_bytes) // per_image)
             outs = {s: torch.empty(B, DIMS[s], *hw[s], device=dev, dtype=torch.float32) for s in set(self.out_stages)}
 
             def emit(s, x, b0):
                 ops.nhwc_to_nchw(x, out=outs[s][b0:b0 + x.shape[0]])
         ds = self.stages_1.downsample
+        stream_norm = getattr(K, "stream_norm", K.layernorm)  # (the stem's norm makes the residual stream: fp32 on every set)
         for b0 in range(0, B, step):
             n = min(step, B - b0)
             rows = K.conv_patches(img[b0:b0 + n], 7, self.stem_stride, self.stem_pad, STEM_LD)
             x = K.linear(rows, K.conv_weight_rows(self.stem.conv.weight, STEM_LD), self.stem.conv.bias)
             del rows
-            x = K.layernorm(x, self.stem.norm.weight, self._zeros(DIMS[0], dev), EPS)
+            x = stream_norm(x, self.stem.norm.weight, self._zeros(DIMS[0], dev), EPS)
             for blk in self.stages_0.blocks:
                 x = self._block(K, x, blk, (n, h0, w0))
             if 0 in self.out_stages:
@@ -265,10 +314,10 @@ class ConvFormerMS(nn.Module):
     """The multi-scale wrapper (the reference's MetaFormer_MS): `.model` holds the stages with the stem at stride 2 / padding 3 and the
     downsample at stride 4; forward(img) -> (cfeat (B,256,H/8,W/8), ffeat (B,128,H/2,W/2))."""
 
-    def __init__(self):
+    def __init__(self, inference_precision="same"):
         super().__init__()
         self.feat_dim = [DIMS[1], DIMS[0]]
-        self.model = ConvFormerStages(2, 3, 4, (0, 1))
+        self.model = ConvFormerStages(2, 3, 4, (0, 1), inference_precision)
 
     def forward(self, img):
         ffeat, cfeat = self.model(img)

@@ -912,8 +912,11 @@ def load_nerfmatch_from_ckpt(ckpt_path, args=None, root_dir=".", arg_mask=None, 
     config.ckpt = ckpt_path
     if args:
         config = merge_configs(config, args)
+    if getattr(config, "backbone_precision", None) is not None:  # (benchmark_nerfmatch --backbone_precision: over the checkpoint's own)
+        config.model.backbone_precision = config.backbone_precision
     if backbone is not None:
         config.model.backbone = "stub"  # placeholder while the model is built; replaced below
+        config.model.backbone_precision = "same"  # (the caller's module has the arithmetic the caller gave it)
     evaluator = NeRFMatchEvaluator(config, data_loader=data_loader)
     state = dict(ckpt["state_dict"])
     if backbone is not None:

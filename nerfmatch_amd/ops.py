@@ -811,6 +811,85 @@ def star_relu(x, scale, bias, inplace=False):
     return y
 
 
+# ---- the backbone's fp16 inference walk: fp16 tensors are torch.float16, `events` a device int32 tensor of one element
+# (or None) onto which a kernel adds the values it stored as non-finite fp16 from a finite fp32 value
+def f16_events(dev):
+    """A zeroed overflow-event counter for the fp16 kernels."""
+    return torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def _linear_blob_f16(weight):
+    """fp16-rounded, re-ordered copy of a weight matrix for nm_linear_f16, cached until the tensor changes like the bf16x3 blobs."""
+    N, K = weight.shape
+
+    def make(w):
+        blob = torch.empty(lib().nm_linear_blob_bytes_f16(N, K), dtype=torch.uint8, device=w.device)
+        check(lib().nm_linear_pack_f16(dptr(w.contiguous()), N, K, dptr(blob, torch.uint8), stream()), "nm_linear_pack_f16")
+        return blob
+    return _linear_cached(("f16",), weight, make)
+
+
+def linear_f16(x, weight, bias=None, residual=None, star=None, out_dtype=torch.float16, events=None):
+    """y = star(x @ fp16(weight).T + bias) + residual for fp16 rows x (..., K) (nm_linear_f16: one fp16 MFMA product per K-step, fp32
+    accumulation); weight (N, K) fp32 as stored, bias (N,) and residual (..., N) fp32.  star: StarReLU's (scale, bias) 1-element device
+    tensors, applied to the fp32 accumulator.  out_dtype torch.float16 (rounded once, no saturation) or torch.float32; a residual needs
+    fp32 output.  K and N multiples of 8."""
+    K = x.shape[-1]
+    N = weight.shape[0]
+    if out_dtype not in (torch.float16, torch.float32):
+        raise _lib.NerfmatchAmdError(f"linear_f16: out_dtype must be torch.float16 or torch.float32, got {out_dtype}")
+    if residual is not None and out_dtype != torch.float32:
+        raise _lib.NerfmatchAmdError("linear_f16: a residual is added in fp32: ask for out_dtype=torch.float32")
+    x2 = x.reshape(-1, K).contiguous()
+    M = x2.shape[0]
+    y = torch.empty(M, N, device=x.device, dtype=out_dtype)
+    if M:
+        r2 = None if residual is None else residual.reshape(-1, N).contiguous()
+        sc, sb = (None, None) if star is None else star
+        check(lib().nm_linear_f16(dptr(x2, torch.float16), dptr(_linear_blob_f16(weight), torch.uint8), dptr(bias), dptr(sc), dptr(sb), dptr(r2),
+                                  M, N, K, int(out_dtype == torch.float16), dptr(y, out_dtype), dptr(events, torch.int32), stream()), "nm_linear_f16")
+    return y.reshape(*x.shape[:-1], N)
+
+
+def layernorm_f16(x, gamma, beta, eps=1e-5, events=None):
+    """ops.layernorm(x, ...) rounded to fp16, bit for bit, in one kernel (nm_layernorm_f16); x fp32, dim in {128, 256, 512}."""
+    dim = x.shape[-1]
+    x2 = x.reshape(-1, dim).contiguous()
+    y = torch.empty(x2.shape, device=x.device, dtype=torch.float16)
+    if x2.shape[0]:
+        check(lib().nm_layernorm_f16(dptr(x2), dptr(gamma), dptr(beta), x2.shape[0], dim, float(eps), dptr(y, torch.float16),
+                                     dptr(events, torch.int32), stream()), "nm_layernorm_f16")
+    return y.reshape(x.shape)
+
+
+def dwconv7_nhwc_f16(x, weight, act_scale=None, act_bias=None, taps=None, events=None):
+    """ops.dwconv7_nhwc on fp16 channel-last x (B,H,W,C) with an fp16 result (nm_dwconv7_nhwc_f16): the fp32 kernel's sums on the widened input,
+    rounded once.  weight / taps, act_scale / act_bias: fp32, as for dwconv7_nhwc."""
+    B, H, W, Cc = x.shape
+    w49 = dwconv_weight_taps(weight) if taps is None else taps
+    assert tuple(w49.shape) == (49, Cc)
+    y = torch.empty_like(x)
+    check(lib().nm_dwconv7_nhwc_f16(dptr(x, torch.float16), dptr(w49), dptr(act_scale), dptr(act_bias), B, H, W, Cc, dptr(y, torch.float16),
+                                    dptr(events, torch.int32), stream()), "nm_dwconv7_nhwc_f16")
+    return y
+
+
+def conv_patches_f16(x, k, stride, pad, ld, channel_last=False, events=None):
+    """ops.conv_patches with fp16 rows (nm_conv_patches_f16): from an fp32 image (B,C,H,W), rounded as it is gathered, or -- channel_last -- from
+    fp16 rows (B,H,W,C) with C % 8 == 0, copied.  Returns (rows (B*Ho*Wo, ld) fp16, (Ho, Wo))."""
+    if channel_last:
+        B, H, W, Cc = x.shape
+    else:
+        B, Cc, H, W = x.shape
+    Ho, Wo = conv_out_size(H, k, stride, pad), conv_out_size(W, k, stride, pad)
+    if Ho < 1 or Wo < 1:
+        raise _lib.NerfmatchAmdError(f"conv_patches_f16: a {H}x{W} image is smaller than the {k}x{k} kernel with padding {pad}")
+    rows = torch.empty(B * Ho * Wo, int(ld), device=x.device, dtype=torch.float16)
+    check(lib().nm_conv_patches_f16(dptr(x, torch.float16 if channel_last else torch.float32), int(bool(channel_last)), B, Cc, H, W, int(k), int(stride),
+                                    int(pad), int(ld), dptr(rows, torch.float16), dptr(events, torch.int32), stream()), "nm_conv_patches_f16")
+    return rows, (Ho, Wo)
+
+
 _DWCONV_BWD_INPUT_WS = {}
 _DWCONV_BWD_WEIGHT_WS = {}
 _STAR_RELU_BWD_WS = {}
