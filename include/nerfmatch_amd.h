@@ -618,6 +618,38 @@ int nm_dwconv7_nhwc_f16(const void* x, const float* w49c, const float* act_scale
 int nm_conv_patches_f16(const void* x, int layout, int B, int C, int H, int W, int k, int stride, int pad, int ld, void* rows,
                         int* overflow, nmStream_t stream);
 
+/* ---- NeRF scene training: the kernels of the fp16 mixed-precision walk (csrc/gemm_f16_train.hip, nerf_train.hip) ----------
+ * Same conventions as the section above: fp16 buffers are `void*`, one rounding to nearest even that overflows to infinity, `overflow`
+ * (device int32, may be NULL) counts stored fp16 values that are not finite while the fp32 value they were rounded from was; operands
+ * 16-byte aligned, every check before anything is enqueued.
+ *
+ * nm_linear_chain_f16: y[M,N] = alpha * [gate > 0] * (act(x[M,K] . w^T + x2[M,K2] . w2^T + bias) + residual): x, x2 fp16 rows; blob, blob2
+ *   in nm_linear_pack_f16's layout (nm_linear_blob_bytes_f16(N, K) / (N, K2) bytes; written by nm_linear_pack_f16 or nm_linear_pack_t_f16);
+ *   x2 / blob2 both or neither (K2 = 0 without); bias [N] fp32 (the accumulators' start value) or NULL; act = ReLU on the fp32 accumulator
+ *   when relu = 1; residual, gate [M,N] fp16 or NULL.  out_f16 = 1: y fp16 rows, counted; 0: fp32 rows, never counted.  One product per
+ *   K-step on v_mfma_f32_32x32x16_f16, fp32 accumulation.  Row m's result does not depend on M.  K, K2, N multiples of 8
+ *   (NM_ERR_UNSUPPORTED otherwise).
+ * nm_linear_pack_t_f16: the blob of w^T (N, K) from the stored w [K,N] fp32: the dX product dy . w of a linear layer.
+ * nm_linear_wgrad_f16: dw[N,K] (+)= alpha * dy[M,N]^T . x[M,K] and, db not NULL, db[N] (+)= alpha * column sums of dy, from one pass over
+ *   dy: fp16 operands, fp32 accumulation, fp32 results; accumulate = 1 adds onto dw / db.  M is split into slices of
+ *   nm_linear_wgrad_f16_slice_rows(M) rows (a multiple of 64; 64 up to M = 16384), one workgroup each per 128 x 128 tile of dw, whose
+ *   partials are kept in `workspace` (nm_linear_wgrad_f16_workspace_bytes, else NM_ERR_WORKSPACE) and added in slice order: no atomics,
+ *   the same bits on every run.  N, K multiples of 8, dy / x / dw 16-byte aligned (NM_ERR_UNSUPPORTED otherwise).
+ * nm_nerf_g4_split_f16: g4[n,4] fp32 (d loss / d (rgb logits, sigma), nm_nerf_composite4_bwd) times the loss scale -> the two zero-padded
+ *   fp16 operand rows g_logit[n,8] (columns 0..2) and g_sig[n,8] (column 0) of the backward chain; counted.
+ * nm_nerf_train_encode_f16: nm_nerf_train_encode with xi / xd stored as fp16: the fp32 kernel's values, each rounded once. */
+int nm_linear_pack_t_f16(const float* w, int N, int K, void* blob, nmStream_t stream);
+int nm_linear_chain_f16(const void* x, const void* blob, int K, const void* x2, const void* blob2, int K2, const float* bias,
+                        const void* residual, const void* gate, float alpha, int relu, int M, int N, int out_f16, void* y, int* overflow,
+                        nmStream_t stream);
+int nm_linear_wgrad_f16_slice_rows(int M);
+size_t nm_linear_wgrad_f16_workspace_bytes(int M, int N, int K);
+int nm_linear_wgrad_f16(const void* dy, const void* x, int M, int N, int K, float alpha, int accumulate, float* dw, float* db,
+                        void* workspace, size_t workspace_bytes, nmStream_t stream);
+int nm_nerf_g4_split_f16(const float* g4, size_t n, float scale, void* g_logit, void* g_sig, int* overflow, nmStream_t stream);
+int nm_nerf_train_encode_f16(const float* rays, const float* t, int R, int S, const long long* ray_id, const long long* ray_id_host,
+                             const float* table, int V, float var_scale, void* xi, void* xd, int* status, nmStream_t stream);
+
 /* ---- ConvFormer image backbone: backward of the kernels above (csrc/convformer_bwd.hip) ----------------------------------------
  * Same conventions: fp32, caller's buffers, 16-byte aligned, every check before anything is enqueued, NM_ERR_UNSUPPORTED beyond the
  * forward kernel's limits.  a(x) = scale * relu(x)^2 + bias, r = relu(x).  Every reduction (dw49c, dscale, dbias) is the sum, in a fixed

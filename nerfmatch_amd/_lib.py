@@ -107,6 +107,14 @@ SIGNATURES = {
     "nm_layernorm_f16": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp]),
     "nm_dwconv7_nhwc_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "nm_conv_patches_f16": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    # NeRF scene training, fp16 mixed-precision walk (gemm_f16_train.hip, nerf_train.hip)
+    "nm_linear_pack_t_f16": (i32, [vp, i32, i32, vp, vp]),
+    "nm_linear_chain_f16": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp, vp]),
+    "nm_linear_wgrad_f16_slice_rows": (i32, [i32]),
+    "nm_linear_wgrad_f16_workspace_bytes": (sz, [i32, i32, i32]),
+    "nm_linear_wgrad_f16": (i32, [vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, sz, vp]),
+    "nm_nerf_g4_split_f16": (i32, [vp, sz, f32, vp, vp, vp, vp]),
+    "nm_nerf_train_encode_f16": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, f32, vp, vp, vp, vp]),
     "nm_dwconv7_nhwc_bwd_input_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "nm_dwconv7_nhwc_bwd_input": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "nm_dwconv7_nhwc_bwd_weight_workspace_bytes": (sz, [i32, i32, i32, i32]),

@@ -119,8 +119,17 @@ __device__ __forceinline__ float view_row_value(int f, float v_ax, const float* 
 // xd [XD] = view_row_value.  16 threads per sample: thread i < 15 writes the six IPE columns of frequency 2^i (3 axes x {sin, sin(. + pi/2)}),
 // thread 15 the view row and the padding of xi.  `dir` is the direction the MEAN reads (lift_var's comment: rays[3:6] for the training
 // render, rays[8:11] for the refinement); the covariance is always that of rays[3:6].
+// T: the rows' type, float or _Float16: the FINISHED fp32 value rounded once as it is stored.  The empty asm hides the value's origin from the
+// compiler, which otherwise folds the conversion into the product in front of it (v_fma_mixlo_f16 rounds the exact product once): the fp16
+// rows would then not be the fp32 rows rounded.
+template <class T>
+__device__ __forceinline__ T row_value(float v) {
+  if constexpr (sizeof(T) == 2) asm volatile("" : "+v"(v));
+  return (T)v;
+}
+template <class T>
 __device__ __forceinline__ void write_sample_rows(const float* rp, const float* dir, float t0, float t1, float var_scale, const float* app_row, int i,
-                                                  float* __restrict__ xi, float* __restrict__ xd) {
+                                                  T* __restrict__ xi, T* __restrict__ xd) {
   if (i < 15) {
     float t_mean, t_var, r_var, dsq[3], nul[3], dnorm, var[3];
     frustum(t0, t1, rp[11], t_mean, t_var, r_var);
@@ -131,13 +140,13 @@ __device__ __forceinline__ void write_sample_rows(const float* rp, const float* 
     for (int ax = 0; ax < 3; ++ax) {
       const float mean = dir[ax] * t_mean + rp[ax];
       const float xe = mean * sc;
-      xi[i * 3 + ax] = ipe_exact(xe, var[ax], sc);
-      xi[45 + i * 3 + ax] = ipe_exact(xe + HALF_PI_F32, var[ax], sc);
+      xi[i * 3 + ax] = row_value<T>(ipe_exact(xe, var[ax], sc));
+      xi[45 + i * 3 + ax] = row_value<T>(ipe_exact(xe + HALF_PI_F32, var[ax], sc));
     }
   } else {
 #pragma unroll
-    for (int f = 90; f < XI; ++f) xi[f] = 0.f;
-    for (int c = 0; c < XD; ++c) xd[c] = view_row_value(c, rp[8 + c % 3], app_row);
+    for (int f = 90; f < XI; ++f) xi[f] = (T)0.f;
+    for (int c = 0; c < XD; ++c) xd[c] = row_value<T>(view_row_value(c, rp[8 + c % 3], app_row));
   }
 }
 

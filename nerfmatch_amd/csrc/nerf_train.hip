@@ -18,9 +18,11 @@ constexpr int MAX_S = 1024;  // samples per ray of nm_nerf_distortion(_bwd): a w
 
 __device__ __forceinline__ int clamp_id(long long id, int V) { return id < 0 ? 0 : (id >= V ? V - 1 : (int)id); }
 
-// 16 threads per sample, write_sample_rows' roles; thread 15 also looks up the ray's appearance row
+// 16 threads per sample, write_sample_rows' roles; thread 15 also looks up the ray's appearance row.  T = float, or _Float16: the same values
+// rounded once (the fp16 training walk's input rows)
+template <class T>
 __global__ void train_encode_kernel(const float* __restrict__ rays, const float* __restrict__ t, int R, int S, const long long* __restrict__ ray_id,
-                                    const float* __restrict__ table, int V, float var_scale, float* __restrict__ xi, float* __restrict__ xd,
+                                    const float* __restrict__ table, int V, float var_scale, T* __restrict__ xi, T* __restrict__ xd,
                                     int* __restrict__ status) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t n = idx >> 4;
@@ -205,7 +207,18 @@ extern "C" int nm_nerf_train_encode(const float* rays, const float* t, int R, in
   if (table && ray_id_host)
     for (int r = 0; r < R; ++r) NM_CHECK_ARG(ray_id_host[r] >= 0 && ray_id_host[r] < V);
   const size_t total = (size_t)R * S * 16;
-  train_encode_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(rays, t, R, S, ray_id, table, V, var_scale, xi, xd, status);
+  train_encode_kernel<float><<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(rays, t, R, S, ray_id, table, V, var_scale, xi, xd, status);
+  return nm_launch_status();
+}
+
+extern "C" int nm_nerf_train_encode_f16(const float* rays, const float* t, int R, int S, const long long* ray_id, const long long* ray_id_host,
+                                        const float* table, int V, float var_scale, void* xi, void* xd, int* status, nmStream_t stream) {
+  NM_CHECK_ARG(rays && t && xi && xd && R > 0 && S > 0 && (!table || V > 0) && (size_t)R * S * 16 / 256 < 0x7fffffffu);
+  if (table && ray_id_host)
+    for (int r = 0; r < R; ++r) NM_CHECK_ARG(ray_id_host[r] >= 0 && ray_id_host[r] < V);
+  const size_t total = (size_t)R * S * 16;
+  train_encode_kernel<_Float16><<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(rays, t, R, S, ray_id, table, V, var_scale, (_Float16*)xi,
+                                                                                                (_Float16*)xd, status);
   return nm_launch_status();
 }
 

@@ -20,7 +20,7 @@ class FineField:
     (90 IPE + padding), xd 48 (27 dir PE + 16 appearance + padding); the density / rgb heads are padded to 8 outputs.
     The ReLU derivatives of the backward pass are the `gate` of the same epilogue (no elementwise passes)."""
 
-    def __init__(self, nerf_fine, dev):
+    def __init__(self, nerf_fine, dev, transposes=True):
         sd = {k: v.detach().to(dev, torch.float32) for k, v in nerf_fine.state_dict().items()}
         z = lambda *s: torch.zeros(*s, device=dev)
 
@@ -43,6 +43,8 @@ class FineField:
         self.Wr, self.br = z(8, 128), z(8)
         self.Wr[:3] = sd["rgb_linear.weight"]
         self.br[:3] = sd["rgb_linear.bias"]
+        if not transposes:  # (the fp16 training walk packs its transposed operands straight from the stored tensors)
+            return
         t = lambda w: w.t().contiguous()
         self.WT = [t(w) for w in W]
         self.W5xT, self.WaT, self.WfT, self.WvfT, self.WvdT, self.WrT = t(self.W5x), t(self.Wa), t(self.Wf), t(self.Wvf), t(self.Wvd), t(self.Wr)

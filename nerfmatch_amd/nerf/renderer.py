@@ -95,6 +95,41 @@ class NerfRenderer(nn.Module):
         # tests/test_nerf_gpu.py::test_surface_fp16x1_coarse_pass_measured and stated in DESIGN.md 3.1d.  A coarse pass whose own
         # outputs are returned always uses `precision`.
         self.coarse_precision = "same"
+        # Arithmetic of the MLPs in a TRAINING render (render_rays(validation=False) on device tensors; nothing else reads it): "same"
+        # (default) = the GEMM chain under ops.LINEAR_PRECISION; "f16" = OPT-IN mixed precision: fp16 encodings,
+        # activations and gradient rows, one fp16 MFMA product per K-step, the backward pass on train_loss_scale times the loss (the
+        # gradients that come out are unscaled fp32).  Non-finite fp16 stores are counted: train_overflow_events().
+        self.train_precision = getattr(config, "train_precision", "same")
+        self.train_loss_scale = 65536.0  # a power of two; NerfTrainer owns and adapts it
+
+    TRAIN_PRECISIONS = ("same", "f16")
+
+    @property
+    def train_precision(self):
+        return self.__dict__["_train_precision"]
+
+    @train_precision.setter
+    def train_precision(self, value):
+        if value not in self.TRAIN_PRECISIONS:
+            raise ValueError(f"train_precision must be one of {self.TRAIN_PRECISIONS}, got {value!r}")
+        self.__dict__["_train_precision"] = value
+
+    def _train_events(self, dev):
+        ev = self.__dict__.get("_train_f16_events")
+        if ev is None or ev.device != dev:
+            ev = self.__dict__["_train_f16_events"] = torch.zeros(2, dtype=torch.int32, device=dev)
+        return ev
+
+    def train_overflow_events(self, reset=False):
+        """(forward, backward) fp16 stores of the "f16" training renders so far that were not finite while the fp32 value they were rounded
+        from was; one synchronisation (an 8-byte read).  reset=True zeroes the counters behind the read."""
+        ev = self.__dict__.get("_train_f16_events")
+        if ev is None:
+            return 0, 0
+        fwd, bwd = ev.tolist()
+        if reset:
+            ev.zero_()
+        return fwd, bwd
 
     def set_training_mode(self, state):
         self.training = state
@@ -281,7 +316,9 @@ class NerfRenderer(nn.Module):
             noise_coarse=(f32(noise_coarse) if noise_coarse is not None else torch.randn(R, S, device=dev)) if noisy else None,
             noise_fine=(f32(noise_fine) if noise_fine is not None else torch.randn(R, S, device=dev)) if noisy else None,
             noise_std=float(self.noise_std) if noisy else 0.0, white_bg=bool(self.white_bg), var_scale=float(self.mip_var_scale),
-            padding=self.resample_padding, chunk_rays=self.train_chunk_rays or tr.chunk_rays_for(S, self.train_chunk_bytes))
+            padding=self.resample_padding, precision=self.train_precision, loss_scale=float(self.train_loss_scale),
+            events=self._train_events(dev) if self.train_precision == "f16" else None,
+            chunk_rays=self.train_chunk_rays or tr.chunk_rays_for(S, self.train_chunk_bytes, 2 if self.train_precision == "f16" else 4))
         params = tr.net_parameters(self.nerf_coarse) + tr.net_parameters(self.nerf_fine)
         if self.appearance_embedding:
             params.append(self.embedding_a.weight)

@@ -12,7 +12,12 @@ One coarse -> fine render with gradients towards the parameters of both networks
               written into the column blocks of the reference-shaped gradient; padded columns / head rows are dropped
   per ray     nm_nerf_composite4(_bwd) (gemm_field.composite: density noise, either background), nm_nerf_distortion(_bwd), nm_nerf_photo_loss,
               nm_nerf_app_grad (fixed summation order)
-Rays are processed in chunks whose saved activations stay below `chunk_bytes`; weight gradients accumulate over the chunks."""
+Rays are processed in chunks whose saved activations stay below `chunk_bytes`; weight gradients accumulate over the chunks.
+
+RenderArgs.precision == "f16" (NerfRenderer.train_precision) swaps the MLP for Chain16: fp16 encodings, activations and
+gradient rows, one fp16 MFMA product per K-step (ops.linear_chain_f16, ops.linear_wgrad_f16), the backward pass on RenderArgs.loss_scale
+times the loss; the gradients that leave TrainRender are unscaled fp32 either way.  Non-finite fp16 stores are counted into
+RenderArgs.events (device int32[2]: forward, backward)."""
 import ctypes as C
 
 import torch
@@ -37,18 +42,30 @@ def net_parameters(net):
 
 
 # ---- kernel wrappers -------------------------------------------------------------------------------------------------------------------
-def encode(rays, t, ray_id=None, table=None, var_scale=-1.0, status=None, ray_id_host=None):
-    """-> xi (R*S, 96), xd (R*S, 48).  ray_id: int64 (R,) on the device; ray_id_host: the same ids on the host (checked there)."""
+def encode(rays, t, ray_id=None, table=None, var_scale=-1.0, status=None, ray_id_host=None, dtype=torch.float32):
+    """-> xi (R*S, 96), xd (R*S, 48).  ray_id: int64 (R,) on the device; ray_id_host: the same ids on the host (checked there).
+    dtype torch.float16: the same values rounded once (nm_nerf_train_encode_f16)."""
     R, S = t.shape[0], t.shape[1] - 1
-    xi, xd = _new(R * S, XI, dev=rays.device), _new(R * S, XD, dev=rays.device)
+    xi, xd = (torch.empty(R * S, c, device=rays.device, dtype=dtype) for c in (XI, XD))
     hp = C.c_void_p(0)
     if ray_id_host is not None:
         ray_id_host = ray_id_host.to(torch.int64).contiguous()
         hp = C.c_void_p(ray_id_host.data_ptr())
     V = 0 if table is None else table.shape[0]
-    check(lib().nm_nerf_train_encode(dptr(rays), dptr(t), R, S, dptr(ray_id, torch.int64), hp, dptr(table), V, float(var_scale), dptr(xi), dptr(xd),
-                                     dptr(status, torch.int32), stream()), "nm_nerf_train_encode")
+    name = "nm_nerf_train_encode" if dtype == torch.float32 else "nm_nerf_train_encode_f16"
+    check(getattr(lib(), name)(dptr(rays), dptr(t), R, S, dptr(ray_id, torch.int64), hp, dptr(table), V, float(var_scale), dptr(xi, dtype),
+                               dptr(xd, dtype), dptr(status, torch.int32), stream()), name)
     return xi, xd
+
+
+def g4_split_f16(g4, scale, events=None):
+    """g4 (n,4) fp32 -> fp16(scale * g4) as the backward chain's two zero-padded operands g_logit (n,8), g_sig (n,8) (nm_nerf_g4_split_f16)."""
+    n = g4.shape[0]
+    g_logit, g_sig = (torch.empty(n, 8, device=g4.device, dtype=torch.float16) for _ in range(2))
+    if n:
+        check(lib().nm_nerf_g4_split_f16(dptr(g4), n, float(scale), dptr(g_logit, torch.float16), dptr(g_sig, torch.float16),
+                                         dptr(events, torch.int32), stream()), "nm_nerf_g4_split_f16")
+    return g_logit, g_sig
 
 
 def _distortion(t, t_is_s, weights, want_mean=True):
@@ -209,6 +226,54 @@ class Chain(FineField):
         return out
 
 
+class Chain16(Chain):
+    """Chain in the fp16 mixed-precision arithmetic: fp16 encodings, activations and gradient rows, weights rounded to fp16
+    as they are packed, one MFMA product per K-step with fp32 accumulation; the two layers with a concatenated input are one launch with a
+    two-source K loop; the heads store fp32.  The backward pass runs on `scale` times the loss and hands back unscaled fp32 gradients
+    (alpha = 1 / scale in the weight-gradient launches and the one product towards xd).  ev_f / ev_b: device int32[1] counters of the
+    forward / backward stores that were not finite."""
+
+    def __init__(self, P, ev_f=None, ev_b=None):
+        FineField.__init__(self, _Params(P), P[0].device, transposes=False)
+        self.app = P[20].shape[1] - 283
+        self.ev_f, self.ev_b = ev_f, ev_b
+
+    def forward(self, xi, xd):
+        lin, ev = ops.linear_chain_f16, self.ev_f
+        h = [lin(xi, self.W[0], self.b[0], relu=True, events=ev)]
+        for l in range(1, 8):
+            x2, w2 = (xi, self.W5x) if l == 5 else (None, None)
+            h.append(lin(h[-1], self.W[l], self.b[l], x2=x2, weight2=w2, relu=True, events=ev))
+        sig = lin(h[7], self.Wa, self.ba, out_dtype=torch.float32)
+        feat = lin(h[7], self.Wf, self.bf, events=ev)
+        hv = lin(feat, self.Wvf, self.bv, x2=xd, weight2=self.Wvd, relu=True, events=ev)
+        logit = lin(hv, self.Wr, self.br, out_dtype=torch.float32)
+        return torch.cat([logit[:, :3], sig[:, :1]], 1), (xi, xd, h, feat, hv)
+
+    def backward(self, g4, saved, grads, want_g_xd=False, scale=1.0):
+        ev, inv = self.ev_b, 1.0 / float(scale)
+        lin = lambda dy, w, **kw: ops.linear_chain_f16(dy, w, transposed=True, events=ev, **kw)
+        wg = lambda dy, x, dw, db=None: ops.linear_wgrad_f16(dy, x, out=(dw, db), alpha=inv, bias=db is not None)
+        xi, xd, h, feat, hv = saved
+        g_logit, g_sig = g4_split_f16(g4.contiguous(), scale, ev)
+        wg(g_logit, hv, grads["Wr"], grads["br"])
+        dy_v = lin(g_logit, self.Wr, gate=hv)
+        wg(dy_v, feat, grads["Wvf"], grads["bv"])
+        wg(dy_v, xd, grads["Wvd"])
+        g_xd = lin(dy_v, self.Wvd, alpha=inv, out_dtype=torch.float32) if want_g_xd else None
+        g_feat = lin(dy_v, self.Wvf)
+        wg(g_feat, h[7], grads["Wf"], grads["bf"])
+        wg(g_sig, h[7], grads["Wa"], grads["ba"])
+        g = lin(g_feat, self.Wf, residual=lin(g_sig, self.Wa), gate=h[7])
+        for l in range(7, 0, -1):
+            wg(g, h[l - 1], grads["W"][l], grads["b"][l])
+            if l == 5:
+                wg(g, xi, grads["W5x"])
+            g = lin(g, self.W[l], gate=h[l - 1])
+        wg(g, xi, grads["W"][0], grads["b"][0])
+        return g_xd
+
+
 class RenderArgs:
     """The non-tensor-parameter inputs of one training render (everything that carries no gradient)."""
 
@@ -224,7 +289,12 @@ class TrainRender(torch.autograd.Function):
     def forward(ctx, a, *params):
         P = [p.detach() for p in params]
         table = P[48] if len(P) > 48 else None
-        nets = (Chain(P[:24]), Chain(P[24:48]))
+        f16 = getattr(a, "precision", "same") == "f16"
+        if f16:
+            ev = a.events
+            nets = (Chain16(P[:24], ev[0:1], ev[1:2]), Chain16(P[24:48], ev[0:1], ev[1:2]))
+        else:
+            nets = (Chain(P[:24]), Chain(P[24:48]))
         rays, S = a.rays, a.S
         R = rays.shape[0]
         step = max(1, int(a.chunk_rays))
@@ -235,7 +305,7 @@ class TrainRender(torch.autograd.Function):
             for lo, hi in chunks:
                 ids = None if a.ray_id is None else a.ray_id[lo:hi]
                 ids_host = None if a.ray_id_host is None else a.ray_id_host[lo:hi]
-                xi, xd = encode(rays[lo:hi], t[lo:hi], ids, table, a.var_scale, a.status, ids_host)
+                xi, xd = encode(rays[lo:hi], t[lo:hi], ids, table, a.var_scale, a.status, ids_host, torch.float16 if f16 else torch.float32)
                 o, sv = net.forward(xi, xd)
                 out4.append(o)
                 saved.append(sv)
@@ -268,7 +338,8 @@ class TrainRender(torch.autograd.Function):
         for k, (lo, hi) in enumerate(ctx.chunks):
             g_xd = []
             for i in (0, 1):
-                g_xd.append(nets[i].backward(g4[i][lo * S:hi * S], ctx.saved[i][k], grads[i], want_g_xd=table is not None))
+                kw = dict(scale=a.loss_scale) if isinstance(nets[i], Chain16) else {}
+                g_xd.append(nets[i].backward(g4[i][lo * S:hi * S], ctx.saved[i][k], grads[i], want_g_xd=table is not None, **kw))
                 ctx.saved[i][k] = None  # (a chunk's activations are released as soon as its gradients are in)
             if table is not None:
                 app_grad(g_xd[0], g_xd[1], None if a.ray_id is None else a.ray_id[lo:hi], hi - lo, S, g_table)
@@ -278,6 +349,7 @@ class TrainRender(torch.autograd.Function):
         return tuple(out)
 
 
-def chunk_rays_for(S, chunk_bytes):
-    """rays per chunk such that one chunk's saved activations of one network stay below chunk_bytes"""
-    return max(1, int(chunk_bytes) // (S * SAVED_FLOATS * 4))
+def chunk_rays_for(S, chunk_bytes, elem_size=4):
+    """rays per chunk such that one chunk's saved activations of one network (elem_size bytes each: 4, or 2 in the fp16 walk) stay below
+    chunk_bytes"""
+    return max(1, int(chunk_bytes) // (S * SAVED_FLOATS * int(elem_size)))

@@ -27,6 +27,42 @@ def init_pfeat_mask(img_wh, ds=8, sample_num=1):
     return pfeat_mask
 
 
+class LossScale:
+    """Loss-scale state of the "f16" training mode with torch.cuda.amp.GradScaler's rule and defaults: initial scale 65536; a step that counted
+    a BACKWARD overflow event is skipped and the scale halved; after 2000 consecutive clean steps the scale doubles.  The scale stays a
+    power of two, so multiplying by it and by its inverse is exact.  A FORWARD event (an activation stored as non-finite fp16 from a finite
+    accumulator) skips the step as well but leaves the scale alone -- no scale cures it -- and warns once."""
+
+    def __init__(self, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+        self.scale, self.growth_factor, self.backoff_factor, self.growth_interval = float(init_scale), growth_factor, backoff_factor, growth_interval
+        self.clean_steps = self.skipped_steps = 0
+        self.overflow_events = [0, 0]  # forward, backward
+        self._warned = False
+
+    def update(self, forward_events, backward_events):
+        """The step's event counts -> True when the optimiser step must be skipped."""
+        self.overflow_events[0] += int(forward_events)
+        self.overflow_events[1] += int(backward_events)
+        if forward_events and not self._warned:
+            self._warned = True
+            import warnings
+
+            warnings.warn(f"NeRF training (train_precision='f16'): {int(forward_events)} activations left fp16's range in the forward pass; the step "
+                          "is skipped and the loss scale kept (it does not act on the forward pass).  If this repeats, train this scene with "
+                          "train_precision='same'.", RuntimeWarning, stacklevel=3)
+        if not (forward_events or backward_events):
+            self.clean_steps += 1
+            if self.clean_steps >= self.growth_interval:
+                self.scale *= self.growth_factor
+                self.clean_steps = 0
+            return False
+        if backward_events:
+            self.scale *= self.backoff_factor
+        self.clean_steps = 0
+        self.skipped_steps += 1
+        return True
+
+
 class NerfTrainer(_TrainerBase):
     def __init__(self, config, num_frames=300, device="cuda", bucket_mb=64, optimizer_factory=None, scheduler_factory=None, closest_ind=None):
         self.config = config
@@ -42,6 +78,12 @@ class NerfTrainer(_TrainerBase):
         self._opt_factory, self._sched_factory = optimizer_factory, scheduler_factory
         nmdist.broadcast_module(self.model, src=0)
         self.buckets = nmdist.GradBuckets(self.model.parameters(), bucket_mb=bucket_mb)
+        self.scaler = LossScale()  # (read only under model.train_precision == "f16")
+
+    # the loss-scale state of the "f16" mode (LossScale): master parameters, .grad, the optimiser and checkpoints stay fp32
+    loss_scale = property(lambda self: self.scaler.scale, lambda self, v: setattr(self.scaler, "scale", float(v)))
+    skipped_steps = property(lambda self: self.scaler.skipped_steps)
+    overflow_events = property(lambda self: tuple(self.scaler.overflow_events))
 
     @staticmethod
     def _rows(x, cols):
@@ -49,7 +91,9 @@ class NerfTrainer(_TrainerBase):
 
     def training_step(self, data, batch_idx=0, **render_kw):
         """forward + backward + gradient all-reduce + optimiser step (reference :140-158); returns the step's metrics (detached).
-        render_kw: explicit random draws for the render (t_rand, jitter, noise_coarse, noise_fine)."""
+        render_kw: explicit random draws for the render (t_rand, jitter, noise_coarse, noise_fine).
+        Under model.train_precision == "f16" the backward pass runs on loss_scale times the loss (the gradients that reach .grad are
+        unscaled fp32) and a step that counted an fp16 overflow is skipped: no optimiser step, see LossScale."""
         if self.optimizer is None:
             self.configure_optimizers()
         m = self.model
@@ -57,6 +101,10 @@ class NerfTrainer(_TrainerBase):
         m.set_training_mode(True)
         rays = self._rows(data["rays"], data["rays"].shape[-1])
         dev = next(m.parameters()).device
+        f16 = m.train_precision == "f16"
+        if f16:
+            m.train_loss_scale = self.scaler.scale
+            m._train_events(dev).zero_()
         with torch.enable_grad():
             preds = m.forward(rays.to(dev), step=self.global_step, ray_id=data["ts"].reshape(-1) if "ts" in data else None, **render_kw)
             mask = data["mask"].to(dev) if self.mask_loss else None
@@ -65,7 +113,14 @@ class NerfTrainer(_TrainerBase):
             self.buckets.start()
             metrics["loss"].backward()
         self.buckets.finish()
-        self.optimizer.step()  # (in-place updates bump the parameters' versions: the inference blobs are re-packed on their next use)
+        skip = False
+        if f16:  # one read of the two counters per step (what torch's GradScaler does with its found-inf flag)
+            ev = m._train_events(dev)
+            if nmdist.world()[1] > 1:
+                torch.distributed.all_reduce(ev)  # every rank takes the same decision
+            skip = self.scaler.update(*ev.tolist())
+        if not skip:
+            self.optimizer.step()  # (in-place updates bump the parameters' versions: the inference blobs are re-packed on their next use)
         self.global_step += 1
         return {k: v.detach() for k, v in metrics.items()}
 

@@ -851,6 +851,80 @@ def linear_f16(x, weight, bias=None, residual=None, star=None, out_dtype=torch.f
     return y.reshape(*x.shape[:-1], N)
 
 
+def _linear_blob_t_f16(weight):
+    """nm_linear_pack_f16's blob of weight.T made straight from the stored (N_out, K_in) fp32 tensor (nm_linear_pack_t_f16), cached under its
+    own key prefix: the dX product of the fp16 training walk."""
+    K, N = weight.shape  # stored (out = K of the product, in = N of the product): the packed matrix is (N, K)
+
+    def make(w):
+        blob = torch.empty(lib().nm_linear_blob_bytes_f16(N, K), dtype=torch.uint8, device=w.device)
+        check(lib().nm_linear_pack_t_f16(dptr(w.contiguous()), N, K, dptr(blob, torch.uint8), stream()), "nm_linear_pack_t_f16")
+        return blob
+    return _linear_cached(("f16T",), weight, make)
+
+
+def linear_chain_f16(x, weight, bias=None, x2=None, weight2=None, relu=False, residual=None, gate=None, alpha=1.0, transposed=False,
+                     out_dtype=torch.float16, events=None):
+    """y = alpha * [gate > 0] * (relu?(x @ W.T + x2 @ W2.T + bias) + residual) for fp16 rows x (M, K), x2 (M, K2) (nm_linear_chain_f16: one
+    fp16 MFMA product per K-step, fp32 accumulation, the two sources in ONE K loop).  weight / weight2: fp32 as stored, rounded to fp16 when
+    packed (cached); transposed=True: W = weight.T for a stored weight (K, N) -- a layer's dX product.  bias fp32 (N,), residual and gate
+    fp16 (M, N).  out_dtype torch.float16 (rounded once, no saturation, non-finite stores counted into `events`) or torch.float32."""
+    if out_dtype not in (torch.float16, torch.float32):
+        raise _lib.NerfmatchAmdError(f"linear_chain_f16: out_dtype must be torch.float16 or torch.float32, got {out_dtype}")
+    if (x2 is None) != (weight2 is None):
+        raise _lib.NerfmatchAmdError("linear_chain_f16: x2 and weight2 come together")
+    if transposed and x2 is not None:
+        raise _lib.NerfmatchAmdError("linear_chain_f16: the transposed form takes one source")
+    M, K = x.shape
+    N = weight.shape[1] if transposed else weight.shape[0]
+    if (weight.shape[0] if transposed else weight.shape[1]) != K:
+        raise _lib.NerfmatchAmdError(f"linear_chain_f16: x has {K} columns, the weight {tuple(weight.shape)} (transposed={transposed})")
+    K2 = 0
+    if x2 is not None:
+        K2 = x2.shape[1]
+        if tuple(weight2.shape) != (N, K2) or x2.shape[0] != M:
+            raise _lib.NerfmatchAmdError(f"linear_chain_f16: second source {tuple(x2.shape)} x {tuple(weight2.shape)} for {M} rows of {N}")
+    for name, t in (("residual", residual), ("gate", gate)):
+        if t is not None and tuple(t.shape) != (M, N):
+            raise _lib.NerfmatchAmdError(f"linear_chain_f16: {name} {tuple(t.shape)} for an output of {(M, N)}")
+    y = torch.empty(M, N, device=x.device, dtype=out_dtype)
+    if M:
+        blob = _linear_blob_t_f16(weight) if transposed else _linear_blob_f16(weight)
+        blob2 = None if x2 is None else _linear_blob_f16(weight2)
+        f16 = torch.float16
+        check(lib().nm_linear_chain_f16(dptr(x, f16), dptr(blob, torch.uint8), K, dptr(x2, f16), dptr(blob2, torch.uint8), K2, dptr(bias),
+                                        dptr(residual, f16), dptr(gate, f16), float(alpha), int(bool(relu)), M, N, int(out_dtype == f16),
+                                        dptr(y, out_dtype), dptr(events, torch.int32), stream()), "nm_linear_chain_f16")
+    return y
+
+
+_WGRAD_F16_WS = {}
+
+
+def linear_wgrad_f16_slice_rows(M):
+    """Rows of one workgroup's slice of M in nm_linear_wgrad_f16 (64 up to M = 16384)."""
+    return int(lib().nm_linear_wgrad_f16_slice_rows(int(M)))
+
+
+def linear_wgrad_f16(dy, x, out=None, alpha=1.0, bias=True):
+    """(dw, db) = alpha * (dy.T @ x, column sums of dy) for fp16 rows dy (M, N), x (M, K): fp32 accumulation, fp32 results, partial sums
+    added in a fixed order (nm_linear_wgrad_f16).  out = (dw, db): both are added onto.  bias=False: db is not formed (-> None)."""
+    f16 = torch.float16
+    M, N = dy.shape
+    K = x.shape[1]
+    if x.shape[0] != M:
+        raise _lib.NerfmatchAmdError(f"linear_wgrad_f16: dy has {M} rows, x {x.shape[0]}")
+    acc = out is not None
+    dw = out[0] if acc else torch.empty(N, K, device=dy.device, dtype=torch.float32)
+    db = None if not bias else (out[1] if acc else torch.empty(N, device=dy.device, dtype=torch.float32))
+    if M == 0:
+        return (dw, db) if acc else (dw.zero_(), None if db is None else db.zero_())
+    ws = _scratch(_WGRAD_F16_WS, dy.device, lib().nm_linear_wgrad_f16_workspace_bytes(M, N, K))
+    check(lib().nm_linear_wgrad_f16(dptr(dy, f16), dptr(x, f16), M, N, K, float(alpha), int(acc), dptr(dw), dptr(db), dptr(ws, torch.uint8),
+                                    ws.numel(), stream()), "nm_linear_wgrad_f16")
+    return dw, db
+
+
 def layernorm_f16(x, gamma, beta, eps=1e-5, events=None):
     """ops.layernorm(x, ...) rounded to fp16, bit for bit, in one kernel (nm_layernorm_f16); x fp32, dim in {128, 256, 512}."""
     dim = x.shape[-1]

@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Step time of a NeRF training step (render + losses + backward, no optimiser) at the reference's batch -- 9216 rays x (128 + 128) samples,
-configs/nerf/*.yaml -- in HIP events, for both ops.LINEAR_PRECISION values, split into encode / chain forward / per-ray kernels / chain dX /
-dW, and beside it the same step with the two MLPs and the compositing done by torch autograd (fp32, rocBLAS GEMMs) on the same device from
+configs/nerf/*.yaml -- in HIP events, for both ops.LINEAR_PRECISION values and for the opt-in fp16 mixed-precision walk
+(NerfRenderer.train_precision = "f16") IN THIS PROCESS, side by side, each with its peak device memory and split into encode /
+chain forward / per-ray kernels / chain dX / dW, and beside it the same step with the two MLPs and the compositing done by torch autograd (fp32, rocBLAS GEMMs) on the same device from
 the same encoded inputs: what the reference's stack would run for that part.  No pass / fail: prints one JSON line per configuration.
 
-    python scripts/perf_nerf_train.py [--rays 9216] [--samples 128] [--steps 5] [--warmup 2] [--app] [--out FILE]
+    python scripts/perf_nerf_train.py [--rays 9216] [--samples 128] [--steps 5] [--warmup 2] [--app] [--converge STEPS] [--out FILE]
+
+--converge STEPS adds a short convergence leg: a student scene model trained by NerfTrainer for STEPS steps on the colours a fixed teacher
+model renders for a pool of rays -- same pool, same initial weights, same seeds and therefore the same draws -- once under bf16x3 and once
+under "f16"; it reports the mean rgb_fine_psnr of the last ten steps of both, the skipped steps and the final loss scale.
 
 The split comes from a separate run with an event pair around every call (which serialises host and device: its parts add up to more than
 the un-instrumented step time, which is the figure to quote)."""
@@ -88,10 +93,18 @@ class Split:
         self.wrap(ops, "linear", lambda s: "chain_forward" if s.phase == "forward" else "chain_dX")
         self.wrap(ops, "linear_wgrad_bias", "dW")
         self.wrap(ops, "linear_wgrad", "dW")
+        self.wrap(ops, "linear_chain_f16", lambda s: "chain_forward" if s.phase == "forward" else "chain_dX")
+        self.wrap(ops, "linear_wgrad_f16", "dW")
+        self.wrap(tr, "g4_split_f16", "per_ray")
         for name in ("composite", "composite_bwd", "_distortion", "distortion_bwd", "app_grad"):
             self.wrap(tr, name, "per_ray")
-        back = tr.Chain.backward
-        self.saved.append((tr.Chain, "backward", back))
+        for cls in (tr.Chain, tr.Chain16):
+            self.wrap_backward(cls)
+        return self
+
+    def wrap_backward(self, cls):
+        back = cls.backward
+        self.saved.append((cls, "backward", back))
 
         def backward(chain, *a, **kw):
             self.phase = "backward"
@@ -99,8 +112,7 @@ class Split:
                 return back(chain, *a, **kw)
             finally:
                 self.phase = "forward"
-        tr.Chain.backward = backward
-        return self
+        cls.backward = backward
 
     def __exit__(self, *exc):
         for mod, name, fn in reversed(self.saved):
@@ -147,6 +159,43 @@ def torch_step(P, enc, b, t, noise, loss_cfg, white_bg):
     return loss
 
 
+def converge(a, dev):
+    """bf16x3 against "f16": the same student trained on a teacher's colours with the same draws -> one JSON line per mode"""
+    from argparse import Namespace
+
+    from nerfmatch_amd.nerf_trainer import NerfTrainer
+
+    S, n, batches = a.samples, a.converge_rays, 8
+    cfg = synth.nerf_config("7scenes", num_pts=S)
+    cfg.optim = Namespace(optimizer="adam", lr=5e-4, weight_decay=0.0, lr_scheduler=None)
+    pool = bundle(n * batches, S, dev, False)["rays"]
+    teacher = NerfRenderer(cfg, training=False)
+    teacher.load_state_dict(synth.nerf_state_dict(seed=1, density_bias=3.0))
+    teacher.to(dev).eval()
+    g = torch.Generator().manual_seed(7)
+    with torch.no_grad():
+        gt = torch.cat([teacher.render_rays(pool[i * n:(i + 1) * n], validation=True, t_rand=torch.rand(n, S + 1, generator=g).to(dev),
+                                            jitter=synth.resample_jitter((n, S + 1), 11 + i).to(dev))["rgb_fine"] for i in range(batches)])
+    out = []
+    for mode in ("bf16x3", "f16"):
+        nerfmatch_amd.set_precision("bf16x3")
+        cfg.train_precision = "f16" if mode == "f16" else "same"
+        trainer = NerfTrainer(cfg, device=dev)
+        trainer.model.load_state_dict(synth.nerf_state_dict(seed=0, density_bias=3.0))
+        torch.manual_seed(0)  # the renders draw t_rand / jitter / noise on the device: the same sequence in both modes
+        psnr = []
+        for i in range(a.converge):
+            k = i % batches
+            m = trainer.training_step(dict(rays=pool[None, k * n:(k + 1) * n], rgbs=gt[None, k * n:(k + 1) * n]), i)
+            psnr.append(float(m["rgb_fine_psnr"]))
+        out.append(dict(path="converge", mode=mode, steps=a.converge, rays=n, samples=S, first_rgb_fine_psnr=round(psnr[0], 3),
+                        final_rgb_fine_psnr=round(sum(psnr[-10:]) / len(psnr[-10:]), 3), skipped_steps=trainer.skipped_steps,
+                        final_loss_scale=trainer.loss_scale, overflow_events=list(trainer.overflow_events)))
+        print(json.dumps(out[-1]), flush=True)
+    nerfmatch_amd.set_precision("fp32")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rays", type=int, default=9216)
@@ -154,6 +203,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--app", action="store_true", help="appearance embedding, white background, loss mask (the cambridge yaml)")
+    ap.add_argument("--converge", type=int, default=0, help="steps of the convergence leg (0: none)")
+    ap.add_argument("--converge-rays", type=int, default=1024)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -167,16 +218,25 @@ def main():
     ren.to(dev)
     b = bundle(a.rays, a.samples, dev, a.app)
     lines = []
-    for precision in ("fp32", "bf16x3"):
-        nerfmatch_amd.set_precision(precision)
+    for precision in ("fp32", "bf16x3", "f16"):
+        f16 = precision == "f16"
+        nerfmatch_amd.set_precision("bf16x3" if f16 else precision)  # (the "f16" walk does not read ops.LINEAR_PRECISION)
+        ren.train_precision = "f16" if f16 else "same"
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
         whole = timed(lambda: hip_step(ren, b, cfg.loss), a.steps, a.warmup)
+        peak = torch.cuda.max_memory_allocated()
         with Split() as sp:
             hip_step(ren, b, cfg.loss)
             parts = sp.totals()
-        lines.append(dict(path="hip", precision=precision, rays=a.rays, samples=a.samples, app=a.app, step=whole,
+        lines.append(dict(path="hip", precision=precision, rays=a.rays, samples=a.samples, app=a.app, step=whole, peak_memory_mib=round(peak / 2**20, 1),
                           split_ms={k: round(v, 3) for k, v in sorted(parts.items())}, split_sum_ms=round(sum(parts.values()), 3),
-                          chunk_rays=ren.train_chunk_rays or tr.chunk_rays_for(a.samples, ren.train_chunk_bytes)))
+                          chunk_rays=ren.train_chunk_rays or tr.chunk_rays_for(a.samples, ren.train_chunk_bytes, 2 if f16 else 4)))
+        if f16:
+            lines[-1]["overflow_events"] = list(ren.train_overflow_events())
         print(json.dumps(lines[-1]), flush=True)
+    ren.train_precision = "same"
     nerfmatch_amd.set_precision("fp32")
     # the torch-autograd step on the HIP step's own fence posts and encodings
     with torch.no_grad():
@@ -193,6 +253,8 @@ def main():
     lines.append(dict(path="torch_autograd_from_encoded_inputs", precision="fp32", rays=a.rays, samples=a.samples, app=a.app, step=whole,
                       note="MLPs, compositing, losses and backward in torch; sampling and encoding not included"))
     print(json.dumps(lines[-1]), flush=True)
+    if a.converge:
+        lines += converge(a, dev)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("\n".join(json.dumps(x) for x in lines) + "\n")
